@@ -16,7 +16,20 @@ recipe; no checkpoints exist upstream) and synthetic N(0,1) images (the
 post-standardisation statistics of predict.py:162-184).  ``--config c3|c4|c5`` picks
 the other BASELINE configs (c4 = 8 pairs per GPU of the 64-pair global batch).
 
-Extras in the JSON line:
+A plain run does only what the headline figure needs: it builds the model, captures
+and warms up the forward, times ``--steps`` steps and prints the line (``metric``,
+``value``, ``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step``, the step
+statistics and the configuration).  ``--dump-outputs DIR`` writes what the last timed
+step returned (rank 0's disparities, float32, ``DIR/disparity.npy``; a fixed seeded
+sample when larger than 64 MB) before the line is printed: the inputs and weights are
+seeded, so two builds run with the same arguments can be compared output for output.
+Everything else the benchmark measures or checks -- the rooflines and ``--breakdown``
+(launch-probed forwards of their own), the per-pair check, the golden EPE, the CPU and
+GPU-eager baselines and the extra configs -- runs under ``--full`` only, where
+``--pair-check``, ``--epe``, ``--cpu-baseline``, ``--gpu-eager`` and
+``--extra-configs`` select among them as before.
+
+Extras in the JSON line under ``--full``:
   roofline       the dominant conv kernel instantiation timed with HIP events inside
                  the timed region; ``achieved`` counts the MFMA products the kernel
                  issues (Winograd products, padded cout blocks), so ``frac`` is the
@@ -94,6 +107,11 @@ def parse(argv=None):
     p.add_argument("--height", type=int, default=576)
     p.add_argument("--width", type=int, default=960)
     p.add_argument("--maxdisp", type=int, default=192)
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline figure: rooflines, per-pair check, golden "
+                        "EPE, CPU / GPU-eager baselines, extra configs (the switches below pick among them)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's output (rank 0) to DIR/disparity.npy")
     p.add_argument("--cpu-baseline", type=int, default=1, help="time the CPU oracle (rank 0, N=1)")
     p.add_argument("--cpu-timed", type=int, default=3, help="timed CPU forwards per config (+1 warm-up)")
     p.add_argument("--cpu-configs", default="c2,c1", help="CPU baseline configs (c2 = this workload)")
@@ -126,6 +144,8 @@ def parse(argv=None):
                         "path on fewer GPUs: every rank on cuda:0 when the box has fewer GPUs than ranks)")
     p.add_argument("--stub", type=int, default=0, help=argparse.SUPPRESS)  # tests: no GPU, gloo
     a = p.parse_args(argv)
+    if a.breakdown and not a.full:
+        p.error("--breakdown probes a forward of its own: run it with --full")
     if a.config:
         for k, v in CONFIGS[a.config].items():
             setattr(a, k, v)
@@ -480,12 +500,13 @@ def run_stub(args, info):
     parallel.finalize()
 
 
-def measure(a, info, device, *, steps, warmup, pair_check, epe):
+def measure(a, info, device, *, steps, warmup, pair_check, epe, full=True):
     """One configuration on this rank: build the model, capture the forward (``a.graph``),
     ``warmup`` untimed steps, one probed eager forward (the path roofline and the dominant
     conv kernel), then EXACTLY ``steps`` timed steps bracketed by barrier + synchronize on
     both sides, the max over ranks; after the timed region the per-pair check of this
-    rank's shard and the golden EPE.  Returns the pieces ``run`` assembles."""
+    rank's shard and the golden EPE.  ``full=False`` leaves out the probed forwards, the
+    check and the EPE (a plain run).  Returns the pieces ``run`` assembles."""
     world, rank = info.world, info.rank
     model = build_model(a.maxdisp, device, a.precision)
     model.check_shape(a.height, a.width)
@@ -512,23 +533,27 @@ def measure(a, info, device, *, steps, warmup, pair_check, epe):
     with torch.no_grad():
         for _ in range(max(warmup, 1)):
             out = step()
-        # every launch of one (untimed) eager forward: the path roofline, and the
-        # dominant conv kernel instantiation
-        with kernels.KernelProbe() as probe:
-            model(left, right)
-        per_kernel = probe.summary()
-        t_roof_ms, t_hbm_ms, t_mat_ms, n_launch = path_roofline(probe.records)
-        convs = {n: d for n, d in per_kernel.items() if d["mfma_flops"] > 0}
-        dominant = max(convs, key=lambda n: convs[n]["ms"])
-        if getattr(a, "breakdown", 0) and info.is_main:
-            for n, d in sorted(per_kernel.items(), key=lambda kv: -kv[1]["ms"]):
-                log(f"{n:48s} launches {d['launches']:3d}  {d['ms']:8.3f} ms  "
-                    f"{d['mfma_flops'] / d['ms'] / 1e9:8.1f} TFLOP/s issued  "
-                    f"{d['bytes'] / d['ms'] / 1e6:8.1f} GB/s")
+        roof = {}
+        if full:
+            # every launch of one (untimed) eager forward: the path roofline, and the
+            # dominant conv kernel instantiation
+            with kernels.KernelProbe() as probe:
+                model(left, right)
+            per_kernel = probe.summary()
+            t_roof_ms, t_hbm_ms, t_mat_ms, n_launch = path_roofline(probe.records)
+            convs = {n: d for n, d in per_kernel.items() if d["mfma_flops"] > 0}
+            dominant = max(convs, key=lambda n: convs[n]["ms"])
+            roof = dict(dominant=dominant, t_roof_ms=t_roof_ms, t_hbm_ms=t_hbm_ms, t_mat_ms=t_mat_ms,
+                        n_launch=n_launch)
+            if getattr(a, "breakdown", 0) and info.is_main:
+                for n, d in sorted(per_kernel.items(), key=lambda kv: -kv[1]["ms"]):
+                    log(f"{n:48s} launches {d['launches']:3d}  {d['ms']:8.3f} ms  "
+                        f"{d['mfma_flops'] / d['ms'] / 1e9:8.1f} TFLOP/s issued  "
+                        f"{d['bytes'] / d['ms'] / 1e6:8.1f} GB/s")
 
         parallel.barrier()
         torch.cuda.synchronize()
-        with kernels.KernelProbe([dominant]) as probe:
+        with (kernels.KernelProbe([roof["dominant"]]) if full else contextlib.nullcontext()) as probe:
             # per-step latency: HIP events between consecutive steps (SURVEY §8d's
             # median and p10/p90), on the stream the forward is launched on
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
@@ -540,11 +565,12 @@ def measure(a, info, device, *, steps, warmup, pair_check, epe):
             torch.cuda.synchronize()
             parallel.barrier()
             elapsed = time.perf_counter() - t0
-        if a.graph:  # replays bypass the launch-time probe: time one eager forward after
-            with kernels.KernelProbe([dominant]) as probe:
-                model(left, right)
-        dom = probe.summary()[dominant]
-        dom_shapes = probe.by_shape(dominant)
+        if full:
+            if a.graph:  # replays bypass the launch-time probe: time one eager forward after
+                with kernels.KernelProbe([roof["dominant"]]) as probe:
+                    model(left, right)
+            roof["dom"] = probe.summary()[roof["dominant"]]
+            roof["dom_shapes"] = probe.by_shape(roof["dominant"])
         step_ms = sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(steps))
     elapsed = parallel.max_over_ranks(elapsed, device)
     per_rank_steps = gather_step_stats(step_ms, device)
@@ -577,9 +603,28 @@ def measure(a, info, device, *, steps, warmup, pair_check, epe):
         e = torch.tensor([golden_epe(device, a.precision)], device=device, dtype=torch.float32)
         epe_v = [float(v) for v in parallel.gather_per_pair(e).cpu()]
     return dict(model=model, left=left, right=right, out=out, elapsed=elapsed, step_ms=step_ms,
-                per_rank_steps=per_rank_steps, dominant=dominant, dom=dom, dom_shapes=dom_shapes,
-                t_roof_ms=t_roof_ms, t_hbm_ms=t_hbm_ms, t_mat_ms=t_mat_ms, n_launch=n_launch,
-                pair=pair, epe=epe_v, steps=steps)
+                per_rank_steps=per_rank_steps, pair=pair, epe=epe_v, steps=steps, **roof)
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+NPY_HEADER_BYTES = 128
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES):
+    """``--dump-outputs``: each named tensor as ``dirname/<name>.npy`` (float64 stays,
+    everything else as float32).  The files take at most ``limit`` bytes in all: an array
+    over its even share is written as a fixed sample of its flattened elements (seed 0,
+    sorted indices, the same for every run of the same shape)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = limit // max(1, len(arrays)) - NPY_HEADER_BYTES
+    for name, t in arrays.items():
+        t = t.detach()
+        x = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        if x.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).integers(0, x.size, share // x.itemsize))
+            x = x.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), x)
 
 
 def roofline_fields(a, m):
@@ -681,9 +726,11 @@ def run(args, info):
     torch.backends.cudnn.allow_tf32 = False
     torch.backends.cuda.matmul.allow_tf32 = False
 
+    full = args.full
     m = measure(args, info, device, steps=args.steps, warmup=args.warmup,
-                pair_check=args.pair_check, epe=args.epe)
-    roof, path = roofline_fields(args, m)
+                pair_check=full and args.pair_check, epe=full and args.epe, full=full)
+    if args.dump_outputs and info.is_main:
+        dump_outputs(args.dump_outputs, {"disparity": m["out"]})
     ms_step = m["elapsed"] / args.steps * 1e3
     step_ms = m["step_ms"]
     cfg = config_name(args)
@@ -714,6 +761,14 @@ def run(args, info):
                    "parallelism": f"dp{world} (pairs sharded over ranks, no collective in the step)",
                    "launch": "hip graph replay" if args.graph else "eager",
                    "dist_backend": backend if world > 1 else None},
+    }
+    if not full:
+        if info.is_main:
+            print(json.dumps(result), flush=True)
+        parallel.finalize()
+        return
+    roof, path = roofline_fields(args, m)
+    result.update({
         "roofline": roof,
         "path_roofline": path,
         "pair_epe_px": m["pair"],
@@ -721,7 +776,7 @@ def run(args, info):
             "vs": "reference LEAStereo fp32 disparity (tests/golden e2e b1_h96_w192_md48)"
                   + (" (bf16 matching net: no upstream tolerance; see DESIGN.md)" if bf16 else ""),
             "max_over_ranks": max(m["epe"]), "per_rank": m["epe"]},
-    }
+    })
     if info.is_main and world == 1 and args.cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args, m["model"], m["left"][:1], m["right"][:1], m["out"][:1],
                                               float(_quantile(step_ms, 0.5)) * 1e-3, device)

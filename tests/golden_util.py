@@ -1,5 +1,7 @@
 """Shared fixture helpers: load golden vectors and regenerate their inputs/weights."""
 import functools
+import glob
+import io
 import json
 import os
 
@@ -18,9 +20,40 @@ def meta():
         return json.load(f)
 
 
+PART_BYTES = 900 * 1024  # a committed fixture file stays under 1 MiB: larger sets are split
+
+
 @functools.lru_cache(None)
 def golden(name):
-    return dict(np.load(os.path.join(GOLD, name + ".npz"), allow_pickle=False))
+    """The arrays of ``name.npz`` and of its continuation files ``name.partN.npz``."""
+    out = {}
+    for path in [os.path.join(GOLD, name + ".npz")] + sorted(glob.glob(os.path.join(GOLD, name + ".part*.npz"))):
+        out.update(np.load(path, allow_pickle=False))
+    return out
+
+
+def save_golden(name, arrays):
+    """Write ``arrays`` compressed as ``name.npz`` and, where that would pass PART_BYTES,
+    ``name.part2.npz``, ... (keys in order, each array whole in one file); ``golden(name)``
+    reads them back as one dict.  Returns the paths written."""
+    def packed(a):
+        buf = io.BytesIO()
+        np.savez_compressed(buf, x=a)
+        return buf.tell()
+    for old in glob.glob(os.path.join(GOLD, name + ".part*.npz")):
+        os.remove(old)
+    parts, size = [{}], 0
+    for k, a in arrays.items():
+        n = packed(a) + len(k)
+        if parts[-1] and size + n > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = a
+        size += n
+    paths = [os.path.join(GOLD, name + (".npz" if i == 0 else f".part{i + 1}.npz")) for i in range(len(parts))]
+    for path, part in zip(paths, parts):
+        np.savez_compressed(path, **part)
+    return paths
 
 
 def shapes():

@@ -29,13 +29,32 @@ def _fractions_are_fractions(d):
     assert 0 < d["path_roofline"]["hbm_frac"] <= d["path_roofline"]["frac"]
 
 
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run (no --full) at the golden e2e size: the headline fields only, exactly
+    --steps timed steps behind ms_per_step, and --dump-outputs writes the last step's
+    disparities as float32."""
+    import numpy as np
+    out = tmp_path / "dump"
+    d = _bench("--gpus", "1", "--height", "96", "--width", "192", "--maxdisp", "48", "--steps", "2",
+               "--warmup", "1", "--dump-outputs", str(out))
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["n_gpus"] == 1
+    assert d["unit"] == "pairs/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    for moved in ("roofline", "path_roofline", "pair_epe_px", "epe_px", "cpu_baseline", "configs"):
+        assert moved not in d, moved
+    assert [p.name for p in out.iterdir()] == ["disparity.npy"]
+    disp = np.load(out / "disparity.npy")
+    assert disp.dtype == np.float32 and disp.shape == (1, 96, 192)
+    assert np.isfinite(disp).all() and disp.min() >= 0 and disp.max() <= 48 and disp.std() > 0
+
+
 @pytest.mark.timeout(400)
 def test_bench_c4_one_gpu_shard():
     """Config 4's per-GPU shard (8 pairs, bf16) through bench.py --gpus 1: n_gpus 1, eight
     per-pair EPEs vs the f32 HIP path, none above the reference network's own bf16 worst
     pair at this config (tests/golden/bf16_noise.json; tests/test_gpu_bf16.py)."""
     from tests.test_gpu_bf16 import _bf16_noise
-    d = _bench("--gpus", "1", "--config", "c4", "--steps", "2", "--warmup", "1", "--cpu-baseline", "0",
+    d = _bench("--gpus", "1", "--full", "--config", "c4", "--steps", "2", "--warmup", "1", "--cpu-baseline", "0",
                "--extra-configs", "")
     assert "configs" not in d
     assert d["n_gpus"] == 1 and d["config"]["global_batch"] == 8 and d["dtype"] == "bf16"
@@ -49,7 +68,7 @@ def test_bench_c4_one_gpu_shard():
 def test_bench_c2_default_workload():
     """The default workload (C2 fp32, batch 1): the per-pair check against the direct-conv
     engine is at the f32 bar, and so is the golden EPE."""
-    d = _bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--cpu-baseline", "0", "--extra-steps", "3")
+    d = _bench("--gpus", "1", "--full", "--steps", "3", "--warmup", "1", "--cpu-baseline", "0", "--extra-steps", "3")
     assert d["n_gpus"] == 1 and d["config"]["global_batch"] == 1 and d["dtype"] == "f32"
     # the other single-GPU BASELINE configs ride in the same line (VERDICT r05 #4)
     assert sorted(d["configs"]) == ["c3", "c5"], d.get("configs")
@@ -72,7 +91,7 @@ def test_bench_world2_gloo_on_one_gpu():
     8 pairs per rank): two per-rank step entries, 16 per-pair EPEs within the reference
     network's own bf16 worst pair, one line from rank 0.  Only RCCL itself is not exercised."""
     from tests.test_gpu_bf16 import _bf16_noise
-    d = _bench("--gpus", "2", "--dist-backend", "gloo", "--config", "c4", "--steps", "2", "--warmup", "1",
+    d = _bench("--gpus", "2", "--full", "--dist-backend", "gloo", "--config", "c4", "--steps", "2", "--warmup", "1",
                "--extra-configs", "")
     assert d["n_gpus"] == 2 and d["config"]["global_batch"] == 16 and d["config"]["dist_backend"] == "gloo"
     assert [r["rank"] for r in d["per_rank_step_ms"]] == [0, 1]

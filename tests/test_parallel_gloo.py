@@ -124,6 +124,38 @@ def test_bench_parse_presets():
     assert h["physical_cores_in_affinity"] <= h["logical_cpus_in_affinity"]
 
 
+def test_bench_full_is_opt_in_and_dump_outputs(tmp_path):
+    """--full is off by default and --breakdown (a probed forward of its own) needs it;
+    dump_outputs writes float32 / float64 .npy files, whole below the byte limit and as
+    the same sorted seeded sample of the flattened array above it."""
+    import importlib.util
+
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    a = bench.parse(["--gpus", "1", "--steps", "4", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 4
+    a = bench.parse(["--full", "--breakdown", "1", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+    with pytest.raises(SystemExit):
+        bench.parse(["--breakdown", "1"])
+    assert bench.DUMP_LIMIT_BYTES == 64 * 10 ** 6
+    x = torch.arange(600, dtype=torch.float32).reshape(2, 10, 30)
+    arrays = {"a": x.to(torch.bfloat16), "b": x.double()}
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    got = np.load(tmp_path / "whole" / "a.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x.to(torch.bfloat16).float().numpy())
+    got = np.load(tmp_path / "whole" / "b.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, x.numpy())
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), arrays, limit=1856)  # 800 data bytes per array
+    for name, item in (("a", 4), ("b", 8)):
+        s1, s2 = np.load(tmp_path / "s1" / f"{name}.npy"), np.load(tmp_path / "s2" / f"{name}.npy")
+        assert s1.shape == (800 // item,) and np.array_equal(s1, s2) and np.all(np.diff(s1) >= 0)
+    assert sum(f.stat().st_size for f in (tmp_path / "s1").iterdir()) <= 1856
+
+
 def test_bench_extra_legs():
     """The configs timed after the headline one: c3 + c5 at N = 1, c4 at
     N > 1, never the headline config itself; an explicit list or none on request."""

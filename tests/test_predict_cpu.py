@@ -12,7 +12,7 @@ from oracle import predict_ref as PR
 from oracle import torch_ref as ref
 from tests.golden_util import arch, c1_inputs, golden, meta, state_dict
 
-SF = "/root/reference/dataset/sceneflow_part/frames_finalpass/35mm_forward_fast"
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def _write_pfm(path, img, little=True):
@@ -60,11 +60,12 @@ def test_sceneflow_list_names():
     assert g == "/d/disparity/TEST/A/0000/left/0006.pfm"
 
 
-@pytest.mark.skipif(not os.path.isdir(SF), reason="reference sample images absent")
 def test_load_data_matches_fixture_statistics():
-    """Restated load_data on the reference's sample PNGs == the fixture's crop
-    standardised with its stored whole-image statistics (container only)."""
-    full = PR.load_data(f"{SF}/left/0001.png", f"{SF}/right/0001.png")
+    """Restated load_data on the reference's sample PNGs (SceneFlow 35mm_forward_fast
+    pair 0001, stored under tests/golden) == the fixture's crop standardised with its
+    stored whole-image statistics."""
+    full = PR.load_data(os.path.join(GOLD, "c1_sceneflow_left_0001.png"),
+                        os.path.join(GOLD, "c1_sceneflow_right_0001.png"))
     left, right, _, _ = PR.test_transform(full, 288, 576)
     want_l, want_r = c1_inputs()
     assert torch.equal(left, want_l) and torch.equal(right, want_r)

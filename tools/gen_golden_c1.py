@@ -6,7 +6,8 @@ preprocessed by the restated predict.py steps (oracle/predict_ref.py), centre-
 cropped to 288x576, run through the *reference* LEAStereo (imported from
 /root/reference, CPU, maxdisp 96, the synthetic weight recipe).  Container only.
 
-Stored (tests/golden/c1_sceneflow.npz; the full images are not needed later):
+Stored (tests/golden/c1_sceneflow.npz and its continuation c1_sceneflow.part2.npz, each
+under 1 MiB, read back as one set by tests/golden_util.golden):
   left_u8 / right_u8   the 288x576 RGB crops of the two PNGs
   mean / std           float64 per-channel statistics of the FULL images (load_data
                        standardises with whole-image statistics before the crop)
@@ -34,6 +35,7 @@ import torch  # noqa: E402
 from leastereo_amd import predict as P  # noqa: E402
 from oracle import predict_ref as PR  # noqa: E402
 from leastereo_amd.weights import synthetic_state_dict  # noqa: E402
+from tests.golden_util import save_golden  # noqa: E402
 from tools.gen_golden import GOLD, ref_model  # noqa: E402
 
 SF = os.path.join(REF, "dataset", "sceneflow_part")
@@ -74,11 +76,10 @@ def main():
         for c in range(3):
             x = img[:, :, c]
             stats.append((np.mean(x[:]), np.std(x[:])))
-    np.savez_compressed(
-        os.path.join(GOLD, "c1_sceneflow.npz"),
+    save_golden("c1_sceneflow", dict(
         left_u8=left[y0:y0 + CROP[0], x0:x0 + CROP[1]], right_u8=right[y0:y0 + CROP[0], x0:x0 + CROP[1]],
         mean=np.array([s[0] for s in stats], np.float64), std=np.array([s[1] for s in stats], np.float64),
-        gt=gt_crop, disp=disp)
+        gt=gt_crop, disp=disp))
     meta_path = os.path.join(GOLD, "meta.json")
     meta = json.load(open(meta_path))
     meta["c1"] = {"pair": "dataset/sceneflow_part/frames_finalpass/" + PAIR, "full_hw": [h, w],

@@ -34,7 +34,7 @@ timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun
 rc=$?; echo "prof rc=$rc"; [ $rc -eq 0 ] || exit $rc
 python3 tools/trace_report.py gpurun_out/prof_$TAG > gpurun_out/prof_${TAG}_forward.txt; head -8 gpurun_out/prof_${TAG}_forward.txt
 for c in ${BENCH_CONFIGS:-c2 c3 c4 c5}; do
-  timeout -k 10 500 python3 bench.py --config $c --steps 20 --warmup 5 --breakdown 1 --cpu-baseline $([ $c = c2 ] && echo 1 || echo 0) \
+  timeout -k 10 500 python3 bench.py --full --config $c --steps 20 --warmup 5 --breakdown 1 --cpu-baseline $([ $c = c2 ] && echo 1 || echo 0) \
     $([ $c = c2 ] || echo --extra-configs=) \
     > gpurun_out/bench_${TAG}_$c.json 2> gpurun_out/bench_${TAG}_$c.err
   rc=$?; echo "bench $c rc=$rc"; [ $rc -eq 0 ] || { tail -5 gpurun_out/bench_${TAG}_$c.err; exit $rc; }
