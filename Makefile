@@ -44,8 +44,17 @@ build/asan/capi_asan_main.o: tests/asan/capi_asan.cpp include/leastereo_hip.h in
 build/asan/capi_asan: build/asan/capi_asan_main.o $(ASANOBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -fno-gpu-sanitize -fsanitize=address -o $@ $^
 
-asan: build/asan/capi_asan
+# the confidence head's entry (lea_disparity_regression_stats) has a driver of its own
+build/asan/disp_stats_asan_main.o: tests/asan/disp_stats_asan.cpp include/leastereo_hip.h
+	@mkdir -p build/asan
+	$(HIPCC) $(ASANFLAGS) -c $< -o $@
+
+build/asan/disp_stats_asan: build/asan/disp_stats_asan_main.o $(ASANOBJ)
+	$(HIPCC) --offload-arch=$(ARCH) -fno-gpu-sanitize -fsanitize=address -o $@ $^
+
+asan: build/asan/capi_asan build/asan/disp_stats_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/capi_asan
+	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/disp_stats_asan
 
 clean:
 	rm -rf build $(LIB)

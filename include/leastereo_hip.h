@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define LEA_ABI_VERSION 13
+#define LEA_ABI_VERSION 14
 
 #define LEA_F32 0
 #define LEA_BF16 1
@@ -202,6 +202,32 @@ int lea_tapsum_upsample(const void* q, int64_t q_bstride, void* y, int64_t y_bst
  * dtype LEA_BF16 (the bf16 path; cost still f32) uses the hardware exp. */
 int lea_disparity_regression(const void* cost, float* disp, int B, int D3, int H3, int W3,
                              int maxdisp, int dtype, void* stream);
+
+/* Disparity regression with per-pixel confidence (ABI 14).  lea_disparity_regression's
+ * fused head (build_model_2d.py:52-57) that also writes what the distribution it forms
+ * says about each pixel -- what the reference's unused DispEntropy (build_model_2d.py:11-24;
+ * as written: softmax instead of softmin, then a softmin over the image height) set out
+ * to give.  Per pixel, with U[od], od in [0, maxdisp), the up-sampled cost as above,
+ * p = softmax(-U) and v[k], k in [0, D3), the bilinearly (H, W) interpolated cost planes:
+ *   disp       = sum_od od p[od]: lea_disparity_regression's output, bit for bit under its
+ *                default form at the configured depths D3 in {4, 8, 16, 32, 64, 88}
+ *   entropy    = -sum_od p ln p, nats, in [0, ln maxdisp] (p == 0 contributes 0)
+ *   winner     k* = the first index of min_k v[k], od* = 3 k* + 1 (od = 3k + 1 lies on
+ *                plane k; defined on the planes because U[0] == U[1] and U[maxdisp-2],
+ *                U[maxdisp-1] tie up to rounding: an argmin over od flips at the ends)
+ *   peak       = sum_{|od - od*| <= radius} p[od], in (0, 1]: the mass around the mode
+ *   disp_local = sum_{|od - od*| <= radius} od p[od] / peak: the soft-argmin of the
+ *                winner's window, which does not average two modes
+ * the window clipped to [0, maxdisp); radius in 1..16 (4 = the nine samples of planes
+ * k* - 1 .. k* + 1).  cost: [B, 1, D3, H3, W3] f32; every output [B, 3H3, 3W3] f32.
+ * entropy, peak, disp_local: NULL = not wanted (never written); at least one non-NULL.
+ * maxdisp must be 3 * D3 (else LEA_E_UNSUPPORTED; lea_disparity_regression takes the
+ * rest).  No output may overlap another or cost (LEA_E_INVALID).  dtype as for
+ * lea_disparity_regression.  One launch; lea_disparity_set_register_form does not
+ * affect it. */
+int lea_disparity_regression_stats(const void* cost, float* disp, float* entropy, float* peak,
+                                   float* disp_local, int B, int D3, int H3, int W3, int maxdisp,
+                                   int radius, int dtype, void* stream);
 
 /* ---- bf16 path (BASELINE configs 3 and 4) ----
  * Activations are bf16 in the "c8" layout: NCDHW with channels blocked by 8

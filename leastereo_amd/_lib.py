@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get(
     "LEASTEREO_HIP_LIB",
     os.path.join(os.path.dirname(os.path.abspath(__file__)), "libleastereo_hip.so"))
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 LEA_F32 = 0
 LEA_BF16 = 1
 LEA_RELU = 1
@@ -56,6 +56,7 @@ SIGNATURES = {
     "lea_tapsum_upsample": (_i, [_p, _i64, _p, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _u,
                                  _p, _i, _p]),
     "lea_disparity_regression": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "lea_disparity_regression_stats": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     # bf16 path (c8 layout)
     "lea_conv3d_packed_elems_bf16": (ctypes.c_size_t, [_i, _i, _i]),
     "lea_conv3d_pack_weights_bf16": (_i, [_p, _p, _i, _i, _i, _p]),

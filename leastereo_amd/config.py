@@ -71,5 +71,11 @@ def obtain_predict_args(argv=None):
         parser.add_argument("--" + flag, type=int, default=0)
     parser.add_argument("--precision", choices=("f32", "bf16"), default="f32",
                         help="matching-net arithmetic (bf16: configs 3/4; not in the reference)")
+    parser.add_argument("--confidence", choices=("none", "entropy", "peak"), default="none",
+                        help="also write a per-pixel confidence map in [0, 1]: 1 - entropy / ln(maxdisp) "
+                             "of the disparity distribution, or the probability mass within "
+                             "--conf_radius of its winner (not in the reference)")
+    parser.add_argument("--conf_radius", type=int, default=4,
+                        help="window radius in disparities for --confidence=peak (1..16)")
     add_leastereo_args(parser)
     return parser.parse_args(argv)

@@ -31,9 +31,12 @@ from .arch import scale_dimension
 def _stacked(fl: torch.Tensor, fr: torch.Tensor) -> torch.Tensor:
     """[fl; fr] along the batch: a view when fr directly follows fl in one buffer (the
     forward's stacked feature batch, LEAStereo.forward), else a copy (torch.cat) -- the
-    r05 C4 forward's two copyBuffer launches were this cat of adjacent views."""
+    r05 C4 forward's two copyBuffer launches were this cat of adjacent views.  One buffer
+    means one storage: two separate tensors that the caching allocator happened to place
+    back to back have adjacent addresses too, and a view of the first cannot span both."""
     if (fl.is_contiguous() and fr.is_contiguous() and fl.shape == fr.shape and fl.dtype == fr.dtype
             and fl.device == fr.device
+            and fl.untyped_storage().data_ptr() == fr.untyped_storage().data_ptr()
             and fr.data_ptr() == fl.data_ptr() + fl.numel() * fl.element_size()):
         return fl.as_strided((2 * fl.shape[0],) + tuple(fl.shape[1:]), fl.stride())
     return torch.cat((fl, fr), 0)

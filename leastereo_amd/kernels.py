@@ -7,7 +7,9 @@ tensor or a missing library raises.
 """
 from __future__ import annotations
 
+import collections
 import contextlib
+import math
 import os
 
 import torch
@@ -505,6 +507,54 @@ def disparity_regression(cost: torch.Tensor, maxdisp: int, fast_exp: bool = Fals
           "lea_disparity_regression")
     _probe_end(rec)
     return disp
+
+
+class DisparityStats(collections.namedtuple("DisparityStats", "disp entropy peak disp_local")):
+    """What ``disparity_regression_stats`` returns: the disparity and, per pixel, what the
+    softmin distribution over ``maxdisp`` says about it (``None`` where not asked for).
+    All [B, 3H3, 3W3] float32, none differentiable.
+      entropy     -sum p ln p, nats, [0, ln maxdisp]
+      peak        the probability mass within ``radius`` of the winner, (0, 1]
+      disp_local  the soft-argmin of that window
+    ``maxdisp`` (an attribute, not a field) is what ``confidence`` normalises by."""
+
+    def __new__(cls, disp, entropy=None, peak=None, disp_local=None, maxdisp=None):
+        self = super().__new__(cls, disp, entropy, peak, disp_local)
+        self.maxdisp = maxdisp
+        return self
+
+    @property
+    def confidence(self) -> torch.Tensor:
+        """``1 - entropy / ln(maxdisp)``: 0 = a flat distribution, 1 = a single disparity."""
+        if self.entropy is None or not self.maxdisp:
+            raise ValueError("confidence needs the entropy output (entropy=True) and maxdisp")
+        return 1.0 - self.entropy / math.log(self.maxdisp)
+
+
+def disparity_regression_stats(cost: torch.Tensor, maxdisp: int, radius: int = 4, fast_exp: bool = False,
+                               entropy: bool = True, peak: bool = True, local: bool = True) -> DisparityStats:
+    """``disparity_regression`` that also returns the per-pixel confidence measures of
+    ``lea_disparity_regression_stats`` (include/leastereo_hip.h) from the same launch:
+    [B,1,D3,H3,W3] -> DisparityStats of [B,3H3,3W3].  ``disp`` is ``disparity_regression``'s
+    bit for bit at the configured depths.  ``maxdisp`` must be 3 * D3."""
+    _require_cuda(cost)
+    if cost.dim() != 5 or cost.shape[1] != 1:
+        raise ValueError("cost must be [B, 1, D3, H3, W3]")
+    if not (entropy or peak or local):
+        raise ValueError("disparity_regression_stats: ask for at least one of entropy, peak, local "
+                         "(disparity_regression gives the disparity alone)")
+    cost = cost.contiguous()
+    b, _, d3, h3, w3 = cost.shape
+    # one allocation per output: a hole (an output not asked for) is a null pointer
+    outs = [torch.empty((b, 3 * h3, 3 * w3), device=cost.device, dtype=torch.float32) if want else None
+            for want in (True, entropy, peak, local)]
+    rec = None if _probe is None else _probe_launch(
+        "disparity_regression_stats", 0.0, 4.0 * (cost.numel() + sum(o.numel() for o in outs if o is not None)))
+    check(_lib.load().lea_disparity_regression_stats(
+        cost.data_ptr(), *(None if o is None else o.data_ptr() for o in outs), b, d3, h3, w3, maxdisp,
+        radius, _lib.LEA_BF16 if fast_exp else LEA_F32, _stream()), "lea_disparity_regression_stats")
+    _probe_end(rec)
+    return DisparityStats(*outs, maxdisp)
 
 
 # ------------------------------------------------------------------ bf16 path (c8)

@@ -211,6 +211,11 @@ class Disp(nn.Module):
     def forward(self, x, fast_exp=False):
         return kernels.disparity_regression(x, self.maxdisp, fast_exp)
 
+    def stats(self, x, radius=4, fast_exp=False):
+        """``forward`` plus the per-pixel entropy, peak mass and winner-window disparity of
+        the same softmin distribution, in the same launch (``kernels.DisparityStats``)."""
+        return kernels.disparity_regression_stats(x, self.maxdisp, radius, fast_exp)
+
 
 class LEAStereo(nn.Module):
     """retrain/LEAStereo.py:12-52 with the hot path on MI355X kernels."""
@@ -260,6 +265,22 @@ class LEAStereo(nn.Module):
         cost = self.matching.executor().run_features(fx, fy, self.maxdisp)
         return self.disp(cost, fast_exp=self.precision == "bf16")
 
+    def forward_with_confidence(self, x, y, radius=4):
+        """``forward`` that returns ``kernels.DisparityStats``: the same disparity (bit for
+        bit) with the per-pixel entropy, peak mass and winner-window disparity of the head's
+        softmin distribution (``DisparityStats.confidence``: 1 - entropy / ln maxdisp).
+        Inference only: the outputs are not differentiable."""
+        if not x.is_cuda:
+            raise RuntimeError("leastereo_amd.LEAStereo runs the matching net on a ROCm device only")
+        if self.training or (torch.is_grad_enabled() and (x.requires_grad or y.requires_grad)):
+            raise RuntimeError("forward_with_confidence is inference only (its outputs have no backward): "
+                               "call model.eval() and pass inputs that do not require grad")
+        self.check_shape(x.shape[2], x.shape[3])
+        f = self.feature(x, y) if STEM_PAIR else self.feature(torch.cat((x, y), 0))
+        fx, fy = f[: x.shape[0]], f[x.shape[0]:]
+        cost = self.matching.executor().run_features(fx, fy, self.maxdisp)
+        return self.disp.stats(cost, radius, fast_exp=self.precision == "bf16")
+
     def set_precision(self, precision: str):
         """Switch the arithmetic ("f32" / "bf16" / "f32_direct"); weights are re-packed
         on the next forward."""
@@ -267,20 +288,23 @@ class LEAStereo(nn.Module):
         self.feature.set_precision(precision)
         self.precision = precision
 
-    def graphed(self, batch: int, height: int, width: int):
+    def graphed(self, batch: int, height: int, width: int, confidence: bool = False, radius: int = 4):
         """``forward`` for one input shape captured into a HIP graph (SURVEY.md §7:
         one host call per batch instead of ~140 launches, for serving and for ranks
         that share a node's host CPUs).  The forward issues only library kernels on
-        the current stream and never synchronises, so it captures as is."""
-        return GraphedForward(self, batch, height, width)
+        the current stream and never synchronises, so it captures as is.
+        ``confidence=True`` captures ``forward_with_confidence(..., radius)`` instead."""
+        return GraphedForward(self, batch, height, width, confidence, radius)
 
 
 class GraphedForward:
     """``forward`` captured once into a torch.cuda.CUDAGraph (a hipGraph on ROCm)
     with static input/output buffers; ``__call__(x, y)`` copies the inputs in,
-    replays, and returns the static output (overwritten by the next call)."""
+    replays, and returns the static output (overwritten by the next call): the disparity,
+    or with ``confidence`` the ``DisparityStats`` of ``forward_with_confidence``."""
 
-    def __init__(self, model: LEAStereo, batch: int, height: int, width: int):
+    def __init__(self, model: LEAStereo, batch: int, height: int, width: int, confidence: bool = False,
+                 radius: int = 4):
         if not torch.cuda.is_available():
             raise RuntimeError("HIP graphs need a ROCm device")
         if model.training:
@@ -290,17 +314,18 @@ class GraphedForward:
         model.check_shape(height, width)
         dev = next(model.parameters()).device
         self.model = model
+        run = (lambda a, b: model.forward_with_confidence(a, b, radius)) if confidence else model
         self.x = torch.zeros(batch, 3, height, width, device=dev)
         self.y = torch.zeros_like(self.x)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.no_grad(), torch.cuda.stream(side):
             for _ in range(2):  # packs the weights and warms the allocator outside the capture
-                model(self.x, self.y)
+                run(self.x, self.y)
         torch.cuda.current_stream(dev).wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
         with torch.no_grad(), torch.cuda.graph(self.graph):
-            self.out = model(self.x, self.y)
+            self.out = run(self.x, self.y)
 
     def __call__(self, x, y):
         self.x.copy_(x, non_blocking=True)

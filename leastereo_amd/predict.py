@@ -82,13 +82,36 @@ def crop_output(pred: np.ndarray, height: int, width: int, crop_height: int, cro
     return pred[0]
 
 
-def predict_pair(model, leftname, rightname, crop_height, crop_width, device="cuda"):
-    """test() of predict.py:213-243 without the plotting: disparity [h', w'] numpy."""
+def predict_pair(model, leftname, rightname, crop_height, crop_width, device="cuda", confidence="none",
+                 radius=4):
+    """test() of predict.py:213-243 without the plotting: disparity [h', w'] numpy.
+    ``confidence`` "entropy" or "peak" (not in the reference): returns (disparity, conf, local)
+    instead -- conf in [0, 1], ``DisparityStats.confidence`` or the peak mass within ``radius``
+    of the winner; local the winner-window disparity under "peak", else None -- from
+    ``model.forward_with_confidence``, each cropped like the disparity."""
     left, right, h, w = load_transform(*load_images(leftname, rightname), crop_height, crop_width,
                                        device)
+    if confidence in (None, "none"):
+        with torch.no_grad():
+            pred = model(left, right)
+        return crop_output(pred.cpu().numpy(), h, w, crop_height, crop_width)
+    if confidence not in ("entropy", "peak"):
+        raise ValueError(f"confidence {confidence!r}: one of none, entropy, peak")
     with torch.no_grad():
-        pred = model(left, right)
-    return crop_output(pred.cpu().numpy(), h, w, crop_height, crop_width)
+        st = model.forward_with_confidence(left, right, radius)
+    conf = st.confidence if confidence == "entropy" else st.peak
+    disp, conf, local = (crop_output(t.cpu().numpy(), h, w, crop_height, crop_width)
+                         for t in (st.disp, conf, st.disp_local))
+    return disp, conf, (local if confidence == "peak" else None)
+
+
+def save_confidence(prefix, conf, local=None):
+    """<prefix>_conf.npy (float32) and <prefix>_conf.png (8-bit, values in [0, 1] scale by 255);
+    <prefix>_local.npy when the winner-window disparity came with it (--confidence=peak)."""
+    np.save(prefix + "_conf.npy", conf.astype(np.float32))
+    save_float_png(prefix + "_conf.png", np.clip(conf, 0.0, 1.0))
+    if local is not None:
+        np.save(prefix + "_local.npy", local.astype(np.float32))
 
 
 def plot_disparity(savename, data, max_disp=192):
@@ -147,11 +170,17 @@ def satellite_names(data_path, save_path, line):
             save_path + cur + ".png", save_path + cur + "_in.png")
 
 
-def test_satellite(model, leftname, rightname, savename, in_savename, crop_height, crop_width):
+def test_satellite(model, leftname, rightname, savename, in_savename, crop_height, crop_width,
+                   confidence="none", radius=4):
     """predict.py:187-211: the disparity as a PNG (min-max 8-bit, as skimage writes a
-    float image) and the left input cropped / padded to the crop."""
+    float image) and the left input cropped / padded to the crop.  With ``confidence``
+    also <name>_conf.png beside <name>.png."""
     from PIL import Image
-    disp = predict_pair(model, leftname, rightname, crop_height, crop_width)
+    disp = predict_pair(model, leftname, rightname, crop_height, crop_width, confidence=confidence,
+                        radius=radius)
+    if confidence not in (None, "none"):
+        disp, conf, _ = disp
+        save_float_png(os.path.splitext(savename)[0] + "_conf.png", np.clip(conf, 0.0, 1.0))
     save_float_png(savename, disp)
     save_float_png(in_savename, crop_image(Image.open(leftname), crop_height, crop_width))
     return disp
@@ -197,7 +226,7 @@ def main(argv=None):
     for index, line in enumerate(lines):
         if opt.satellite:  # predict.py:258-264
             test_satellite(model, *satellite_names(opt.data_path, opt.save_path, line),
-                           opt.crop_height, opt.crop_width)
+                           opt.crop_height, opt.crop_width, opt.confidence, opt.conf_radius)
         if not opt.sceneflow:
             continue
         print(f"Running for sceneflow {index}")
@@ -207,8 +236,12 @@ def main(argv=None):
             gt, _, _ = read_pfm(gtname)
             plot_disparity(opt.save_path + f"{index:d}_gt.png", gt, 192)
         t0 = time.time()
-        disp = predict_pair(model, leftname, rightname, opt.crop_height, opt.crop_width)
+        disp = predict_pair(model, leftname, rightname, opt.crop_height, opt.crop_width,
+                            confidence=opt.confidence, radius=opt.conf_radius)
         print(f"Processing time: {time.time() - t0:.4f}")
+        if opt.confidence != "none":
+            disp, conf, local = disp
+            save_confidence(os.path.join(opt.save_path, f"{index}"), conf, local)
         plot_disparity(opt.save_path + f"{index:d}.png", disp, 192)  # predict.py:240
         np.save(os.path.join(opt.save_path, f"{index}.npy"), disp.astype(np.float32))
         if gt is not None:

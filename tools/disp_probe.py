@@ -3,6 +3,7 @@
 3 / 2 / 1 / 0), f32 and fast exp: HIP-event microseconds and the largest difference from form 1.
 
   python tools/disp_probe.py [--iters 20]
+  python tools/disp_probe.py --stats [--iters 20] [--rounds 9]   the confidence head beside the plain one
 """
 import argparse
 import os
@@ -17,11 +18,66 @@ SHAPES = [("C2", 1, 64, 192, 320, 192), ("C4", 8, 64, 192, 320, 192), ("C3", 8, 
           ("C5", 1, 88, 336, 504, 264)]
 
 
+def _timed(fn, iters):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters * 1e3
+
+
+def stats_main(a, lib):
+    """lea_disparity_regression_stats (all four outputs, radius 4) next to the plain entry in
+    its default form: the same cost and disparity buffers, launched through the C ABI on one
+    stream, warmed up, then ``--rounds`` alternating windows of ``--iters`` launches each;
+    medians of the windows, and whether the two disparities are the same bits."""
+    g = torch.Generator(device="cuda").manual_seed(0)
+    stream = torch.cuda.current_stream().cuda_stream
+    for name, b, d3, h3, w3, md in SHAPES:
+        if name not in ("C2", "C4", "C5"):
+            continue
+        x = torch.randn(b, 1, d3, h3, w3, device="cuda", generator=g) * 3
+        disp, ent, peak, loc = (torch.empty(b, 3 * h3, 3 * w3, device="cuda") for _ in range(4))
+        for fast in (False, True):
+            dt = _lib.LEA_BF16 if fast else _lib.LEA_F32
+
+            def plain():
+                _lib.check(lib.lea_disparity_regression(x.data_ptr(), disp.data_ptr(), b, d3, h3, w3, md, dt,
+                                                        stream), "plain")
+
+            def stats():
+                _lib.check(lib.lea_disparity_regression_stats(
+                    x.data_ptr(), disp.data_ptr(), ent.data_ptr(), peak.data_ptr(), loc.data_ptr(), b, d3, h3,
+                    w3, md, 4, dt, stream), "stats")
+
+            plain()
+            want = disp.clone()
+            stats()
+            same = bool(torch.equal(want, disp))
+            for fn in (plain, stats):
+                _timed(fn, a.iters)
+            tp, ts = [], []
+            for _ in range(a.rounds):
+                tp.append(_timed(plain, a.iters))
+                ts.append(_timed(stats, a.iters))
+            mp, ms = sorted(tp)[len(tp) // 2], sorted(ts)[len(ts) // 2]
+            print(f"{name} B={b} D3={d3} {3 * h3}x{3 * w3} fast={int(fast)}  plain {mp:7.1f} us "
+                  f"[{min(tp):.1f}, {max(tp):.1f}]  stats {ms:7.1f} us [{min(ts):.1f}, {max(ts):.1f}]  "
+                  f"stats / plain {ms / mp:.2f}  disp same bits: {same}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--stats", action="store_true",
+                    help="time lea_disparity_regression_stats next to the plain entry (C2, C4, C5)")
+    ap.add_argument("--rounds", type=int, default=9, help="--stats: alternating timed windows per entry")
     a = ap.parse_args()
     lib = _lib.load()
+    if a.stats:
+        return stats_main(a, lib)
     g = torch.Generator(device="cuda").manual_seed(0)
     for name, b, d3, h3, w3, md in SHAPES:
         x = torch.randn(b, 1, d3, h3, w3, device="cuda", generator=g) * 3
