@@ -52,9 +52,18 @@ build/asan/disp_stats_asan_main.o: tests/asan/disp_stats_asan.cpp include/leaste
 build/asan/disp_stats_asan: build/asan/disp_stats_asan_main.o $(ASANOBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -fno-gpu-sanitize -fsanitize=address -o $@ $^
 
-asan: build/asan/capi_asan build/asan/disp_stats_asan
+# the left-right check's two entries (lea_disparity_regression_right, lea_disparity_lr_check)
+build/asan/lr_asan_main.o: tests/asan/lr_asan.cpp include/leastereo_hip.h
+	@mkdir -p build/asan
+	$(HIPCC) $(ASANFLAGS) -c $< -o $@
+
+build/asan/lr_asan: build/asan/lr_asan_main.o $(ASANOBJ)
+	$(HIPCC) --offload-arch=$(ARCH) -fno-gpu-sanitize -fsanitize=address -o $@ $^
+
+asan: build/asan/capi_asan build/asan/disp_stats_asan build/asan/lr_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/capi_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/disp_stats_asan
+	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/lr_asan
 
 clean:
 	rm -rf build $(LIB)

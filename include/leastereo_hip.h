@@ -229,6 +229,47 @@ int lea_disparity_regression_stats(const void* cost, float* disp, float* entropy
                                    float* disp_local, int B, int D3, int H3, int W3, int maxdisp,
                                    int radius, int dtype, void* stream);
 
+/* Left-right check (additive: the ABI number stays 14; a library without these symbols
+ * fails to load).  The matching cost already scores every (left pixel, disparity) pair, so
+ * the right view's distribution is the up-sampled cost read along its diagonals -- right
+ * pixel xr at disparity od is left pixel xr + od -- one more head-sized launch on the cost
+ * the forward has produced, not a second forward on the mirrored pair.
+ *
+ * Right-view disparity.  U[od, y, x] as for lea_disparity_regression: the trilinear
+ * align_corners=False up-sampling of cost[b, 0] to [MD, Ho, Wo]; MD = maxdisp = 3 D3 is
+ * required, Ho = 3 H3, Wo = 3 W3.  For a right-image pixel (y, xr):
+ *   candidate od is in view iff xr + od <= Wo - 1 (at least od = 0 always is)
+ *   n = min(MD, Wo - xr)
+ *   p_R[od] = softmax over od < n of (-U[od, y, xr + od])
+ *   disp_right[b, y, xr] = sum_{od < n} od p_R[od]
+ * The last column is therefore exactly 0; MD > Wo is legal.
+ * cost: [B, 1, D3, H3, W3] f32; disp_right: [B, 3H3, 3W3] f32.  Any D3 >= 1.
+ * maxdisp != 3 D3: LEA_E_UNSUPPORTED.  A null pointer, a non-positive size or an output
+ * that overlaps the cost: LEA_E_INVALID.  dtype as for lea_disparity_regression (LEA_BF16:
+ * the hardware exponential; anything else unknown: LEA_E_UNSUPPORTED).  One launch, no
+ * allocation, no synchronisation. */
+int lea_disparity_regression_right(const void* cost, float* disp_right, int B, int D3, int H3,
+                                   int W3, int maxdisp, int dtype, void* stream);
+
+/* The check and the scanline fill, per left pixel (y, x) with dL = disp_left[b, y, x] and
+ * threshold > 0:
+ *   xi = floor(x - dL + 0.5), in f32 without contraction
+ *   state (uint8) = 2 (out of view)   if xi < 0 or xi > W - 1
+ *                   1 (inconsistent)  otherwise, if dL is not finite or
+ *                                     !(|dL - disp_right[b, y, xi]| <= threshold)
+ *                   0 (consistent)    otherwise
+ *   disp_filled   = dL bit for bit where state == 0; elsewhere the dL of the nearest
+ *                   state-0 pixel to the left on the same row and of the nearest one to the
+ *                   right, the smaller of the two (the background is the smaller
+ *                   disparity); the one that exists if only one does; dL unchanged if the
+ *                   row has none.
+ * disp_left, disp_right, disp_filled: [B, H, W] f32; state: [B, H, W] bytes.  state or
+ * disp_filled may be NULL (not wanted, never written); both NULL: LEA_E_INVALID.  Any
+ * W >= 1.  threshold not > 0 or not finite: LEA_E_INVALID.  No output may overlap an input
+ * or the other output (LEA_E_INVALID).  One launch. */
+int lea_disparity_lr_check(const float* disp_left, const float* disp_right, uint8_t* state,
+                           float* disp_filled, int B, int H, int W, float threshold, void* stream);
+
 /* ---- bf16 path (BASELINE configs 3 and 4) ----
  * Activations are bf16 in the "c8" layout: NCDHW with channels blocked by 8
  * innermost, x[b][c/8][d][h][w][c%8] (one voxel's 8 channels = one 16-byte word;

@@ -57,6 +57,8 @@ SIGNATURES = {
                                  _p, _i, _p]),
     "lea_disparity_regression": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "lea_disparity_regression_stats": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "lea_disparity_regression_right": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "lea_disparity_lr_check": (_i, [_p, _p, _p, _p, _i, _i, _i, ctypes.c_float, _p]),
     # bf16 path (c8 layout)
     "lea_conv3d_packed_elems_bf16": (ctypes.c_size_t, [_i, _i, _i]),
     "lea_conv3d_pack_weights_bf16": (_i, [_p, _p, _i, _i, _i, _p]),

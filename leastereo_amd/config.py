@@ -77,5 +77,9 @@ def obtain_predict_args(argv=None):
                              "--conf_radius of its winner (not in the reference)")
     parser.add_argument("--conf_radius", type=int, default=4,
                         help="window radius in disparities for --confidence=peak (1..16)")
+    parser.add_argument("--lr_check", type=float, default=0.0, metavar="THR",
+                        help="left-right check with this threshold in pixels (0 = off): also write the "
+                             "right-view disparity, the occlusion mask and the filled disparity "
+                             "(not in the reference)")
     add_leastereo_args(parser)
     return parser.parse_args(argv)

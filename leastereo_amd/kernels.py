@@ -557,6 +557,62 @@ def disparity_regression_stats(cost: torch.Tensor, maxdisp: int, radius: int = 4
     return DisparityStats(*outs, maxdisp)
 
 
+LR_CONSISTENT, LR_INCONSISTENT, LR_OUT_OF_VIEW = 0, 1, 2
+
+DisparityLR = collections.namedtuple("DisparityLR", "disp disp_right state disp_filled")
+DisparityLR.__doc__ = """What ``LEAStereo.forward_lr`` / ``lr_check`` return (``None`` where not asked for):
+  disp         the left-view disparity, [B, H, W] float32
+  disp_right   the right-view disparity read off the same cost (``disparity_regression_right``)
+  state        uint8: LR_CONSISTENT, LR_INCONSISTENT (occluded or mismatched), LR_OUT_OF_VIEW
+  disp_filled  ``disp`` where consistent, elsewhere the smaller of the nearest consistent
+               disparities to the left and right on the row
+None differentiable."""
+
+
+def disparity_regression_right(cost: torch.Tensor, maxdisp: int, fast_exp: bool = False) -> torch.Tensor:
+    """The right view's disparity from the left view's matching cost
+    (``lea_disparity_regression_right``, include/leastereo_hip.h): the up-sampled cost read
+    along its diagonals, right pixel xr at disparity od being left pixel xr + od, soft-argmin
+    over the candidates in view.  [B,1,D3,H3,W3] -> [B,3H3,3W3]; ``maxdisp`` must be 3 * D3."""
+    _require_cuda(cost)
+    if cost.dim() != 5 or cost.shape[1] != 1:
+        raise ValueError("cost must be [B, 1, D3, H3, W3]")
+    cost = cost.contiguous()
+    b, _, d3, h3, w3 = cost.shape
+    out = torch.empty((b, 3 * h3, 3 * w3), device=cost.device, dtype=torch.float32)
+    rec = None if _probe is None else _probe_launch(
+        "disparity_regression_right", 0.0, 4.0 * (cost.numel() + out.numel()))
+    check(_lib.load().lea_disparity_regression_right(
+        cost.data_ptr(), out.data_ptr(), b, d3, h3, w3, maxdisp, _lib.LEA_BF16 if fast_exp else LEA_F32,
+        _stream()), "lea_disparity_regression_right")
+    _probe_end(rec)
+    return out
+
+
+def lr_check(disp_left: torch.Tensor, disp_right: torch.Tensor, threshold: float = 1.0, want_state: bool = True,
+             want_filled: bool = True) -> DisparityLR:
+    """The left-right consistency check and scanline fill of ``lea_disparity_lr_check``
+    (include/leastereo_hip.h) in one launch: two [B, H, W] float32 disparities ->
+    ``DisparityLR(disp_left, disp_right, state, disp_filled)``."""
+    _require_cuda(disp_left, disp_right)
+    if disp_left.dim() != 3 or disp_left.shape != disp_right.shape:
+        raise ValueError("disp_left and disp_right must be [B, H, W] of one shape")
+    if not (want_state or want_filled):
+        raise ValueError("lr_check: ask for at least one of state, filled")
+    dl, dr = disp_left.contiguous(), disp_right.contiguous()
+    b, h, w = dl.shape
+    state = torch.empty((b, h, w), device=dl.device, dtype=torch.uint8) if want_state else None
+    filled = torch.empty((b, h, w), device=dl.device, dtype=torch.float32) if want_filled else None
+    rec = None if _probe is None else _probe_launch(
+        "disparity_lr_check", 0.0, dl.numel() * (8.0 + (1.0 if want_state else 0.0) + (16.0 if want_filled else 0.0)))
+    check(_lib.load().lea_disparity_lr_check(
+        dl.data_ptr(), dr.data_ptr(), None if state is None else state.data_ptr(),
+        None if filled is None else filled.data_ptr(), b, h, w, float(threshold), _stream()),
+        "lea_disparity_lr_check")
+    _probe_end(rec)
+    return DisparityLR(disp_left, disp_right, state, filled)
+
+
 # ------------------------------------------------------------------ bf16 path (c8)
 # Activations: torch.bfloat16 [B, C/8, D, H, W, 8] ("c8": 8 channels per voxel word).
 

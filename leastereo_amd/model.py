@@ -216,6 +216,11 @@ class Disp(nn.Module):
         the same softmin distribution, in the same launch (``kernels.DisparityStats``)."""
         return kernels.disparity_regression_stats(x, self.maxdisp, radius, fast_exp)
 
+    def right(self, x, fast_exp=False):
+        """The right view's disparity from the same cost: the up-sampled cost read along its
+        diagonals (``kernels.disparity_regression_right``)."""
+        return kernels.disparity_regression_right(x, self.maxdisp, fast_exp)
+
 
 class LEAStereo(nn.Module):
     """retrain/LEAStereo.py:12-52 with the hot path on MI355X kernels."""
@@ -281,6 +286,25 @@ class LEAStereo(nn.Module):
         cost = self.matching.executor().run_features(fx, fy, self.maxdisp)
         return self.disp.stats(cost, radius, fast_exp=self.precision == "bf16")
 
+    def forward_lr(self, x, y, threshold=1.0):
+        """``forward`` with the left-right check, as ``kernels.DisparityLR``: the same disparity
+        (bit for bit: the same feature, matching and head calls), the right view's disparity
+        from the right head on the same cost (no second forward on the mirrored pair), the
+        per-pixel state (``kernels.LR_CONSISTENT`` / ``LR_INCONSISTENT`` / ``LR_OUT_OF_VIEW``)
+        and the scanline-filled disparity.  Inference only: the outputs are not differentiable."""
+        if not x.is_cuda:
+            raise RuntimeError("leastereo_amd.LEAStereo runs the matching net on a ROCm device only")
+        if self.training or (torch.is_grad_enabled() and (x.requires_grad or y.requires_grad)):
+            raise RuntimeError("forward_lr is inference only (its outputs have no backward): "
+                               "call model.eval() and pass inputs that do not require grad")
+        self.check_shape(x.shape[2], x.shape[3])
+        f = self.feature(x, y) if STEM_PAIR else self.feature(torch.cat((x, y), 0))
+        fx, fy = f[: x.shape[0]], f[x.shape[0]:]
+        cost = self.matching.executor().run_features(fx, fy, self.maxdisp)
+        fast = self.precision == "bf16"
+        disp = self.disp(cost, fast_exp=fast)
+        return kernels.lr_check(disp, self.disp.right(cost, fast_exp=fast), threshold)
+
     def set_precision(self, precision: str):
         """Switch the arithmetic ("f32" / "bf16" / "f32_direct"); weights are re-packed
         on the next forward."""
@@ -288,23 +312,29 @@ class LEAStereo(nn.Module):
         self.feature.set_precision(precision)
         self.precision = precision
 
-    def graphed(self, batch: int, height: int, width: int, confidence: bool = False, radius: int = 4):
+    def graphed(self, batch: int, height: int, width: int, confidence: bool = False, radius: int = 4,
+                lr_threshold=None):
         """``forward`` for one input shape captured into a HIP graph (SURVEY.md §7:
         one host call per batch instead of ~140 launches, for serving and for ranks
         that share a node's host CPUs).  The forward issues only library kernels on
         the current stream and never synchronises, so it captures as is.
-        ``confidence=True`` captures ``forward_with_confidence(..., radius)`` instead."""
-        return GraphedForward(self, batch, height, width, confidence, radius)
+        ``confidence=True`` captures ``forward_with_confidence(..., radius)`` instead, a number
+        for ``lr_threshold`` captures ``forward_lr(..., lr_threshold)``; not both in one capture."""
+        return GraphedForward(self, batch, height, width, confidence, radius, lr_threshold)
 
 
 class GraphedForward:
     """``forward`` captured once into a torch.cuda.CUDAGraph (a hipGraph on ROCm)
     with static input/output buffers; ``__call__(x, y)`` copies the inputs in,
     replays, and returns the static output (overwritten by the next call): the disparity,
-    or with ``confidence`` the ``DisparityStats`` of ``forward_with_confidence``."""
+    with ``confidence`` the ``DisparityStats`` of ``forward_with_confidence``, or with
+    ``lr_threshold`` the ``DisparityLR`` of ``forward_lr``."""
 
     def __init__(self, model: LEAStereo, batch: int, height: int, width: int, confidence: bool = False,
-                 radius: int = 4):
+                 radius: int = 4, lr_threshold=None):
+        if confidence and lr_threshold is not None:
+            raise ValueError("graphed(): confidence=True and lr_threshold in one capture is not supported; "
+                             "capture two graphs")
         if not torch.cuda.is_available():
             raise RuntimeError("HIP graphs need a ROCm device")
         if model.training:
@@ -314,7 +344,8 @@ class GraphedForward:
         model.check_shape(height, width)
         dev = next(model.parameters()).device
         self.model = model
-        run = (lambda a, b: model.forward_with_confidence(a, b, radius)) if confidence else model
+        run = ((lambda a, b: model.forward_with_confidence(a, b, radius)) if confidence else
+               (lambda a, b: model.forward_lr(a, b, lr_threshold)) if lr_threshold is not None else model)
         self.x = torch.zeros(batch, 3, height, width, device=dev)
         self.y = torch.zeros_like(self.x)
         side = torch.cuda.Stream(device=dev)

@@ -15,6 +15,9 @@ Restates the host-side steps around ``LEAStereo.forward`` (predict.py:144-243):
   * ``main``           predict.py:249-286  the list-file loop: --sceneflow writes
                        {index}.png and {index}_gt.png (and {index}.npy, the raw
                        disparity), --satellite writes {name}.png and {name}_in.png
+  * ``predict_pair_lr`` / ``save_lr``  not in the reference: --lr_check THR adds the
+                       left-right check of ``LEAStereo.forward_lr`` ({index}_right.npy,
+                       {index}_occ.png, {index}_filled.npy / .png; {name}_occ.png)
 Arithmetic runs on the HIP kernels; what stays on the host is file I/O (PIL, PFM, PNG).
 
     python predict.py --sceneflow=1 --maxdisp=192 --crop_height=576 --crop_width=960 \
@@ -114,6 +117,32 @@ def save_confidence(prefix, conf, local=None):
         np.save(prefix + "_local.npy", local.astype(np.float32))
 
 
+def predict_pair_lr(model, leftname, rightname, crop_height, crop_width, threshold, device="cuda"):
+    """``predict_pair`` through ``model.forward_lr``: (disparity, right-view disparity, state
+    uint8, filled disparity), each cropped like the disparity.  The disparity is
+    ``predict_pair``'s bit for bit."""
+    left, right, h, w = load_transform(*load_images(leftname, rightname), crop_height, crop_width,
+                                       device)
+    with torch.no_grad():
+        lr = model.forward_lr(left, right, threshold)
+    return tuple(crop_output(t.cpu().numpy(), h, w, crop_height, crop_width) for t in lr)
+
+
+def occlusion_u8(state):
+    """The state map as an 8-bit image: consistent 0, inconsistent 127, out of view 255."""
+    state = np.asarray(state)
+    return np.where(state == 2, 255, state.astype(np.int32) * 127).astype(np.uint8)
+
+
+def save_lr(prefix, right, state, filled, max_disp=192):
+    """<prefix>_right.npy (float32), <prefix>_occ.png (``occlusion_u8``), <prefix>_filled.npy
+    (float32) and <prefix>_filled.png (coloured like the disparity)."""
+    np.save(prefix + "_right.npy", right.astype(np.float32))
+    save_float_png(prefix + "_occ.png", occlusion_u8(state))
+    np.save(prefix + "_filled.npy", filled.astype(np.float32))
+    plot_disparity(prefix + "_filled.png", filled, max_disp)
+
+
 def plot_disparity(savename, data, max_disp=192):
     """predict.py:246-247: ``plt.imsave(savename, data, vmin=0, vmax=max_disp, cmap='turbo')``."""
     import matplotlib
@@ -171,11 +200,14 @@ def satellite_names(data_path, save_path, line):
 
 
 def test_satellite(model, leftname, rightname, savename, in_savename, crop_height, crop_width,
-                   confidence="none", radius=4):
+                   confidence="none", radius=4, lr_threshold=0.0):
     """predict.py:187-211: the disparity as a PNG (min-max 8-bit, as skimage writes a
     float image) and the left input cropped / padded to the crop.  With ``confidence``
-    also <name>_conf.png beside <name>.png."""
+    also <name>_conf.png beside <name>.png, with ``lr_threshold`` > 0 <name>_occ.png."""
     from PIL import Image
+    if lr_threshold > 0:
+        state = predict_pair_lr(model, leftname, rightname, crop_height, crop_width, lr_threshold)[2]
+        save_float_png(os.path.splitext(savename)[0] + "_occ.png", occlusion_u8(state))
     disp = predict_pair(model, leftname, rightname, crop_height, crop_width, confidence=confidence,
                         radius=radius)
     if confidence not in (None, "none"):
@@ -209,6 +241,8 @@ def main(argv=None):
     from .config import default_arch_args, obtain_predict_args
     from .model import LEAStereo
     opt = default_arch_args(obtain_predict_args(argv))
+    if not opt.lr_check >= 0:
+        raise ValueError(f"--lr_check {opt.lr_check}: a threshold in pixels > 0, or 0 for off")
     if not torch.cuda.is_available():
         raise RuntimeError("leastereo_amd runs on a ROCm device only")
     model = LEAStereo(opt, "cuda")
@@ -226,7 +260,7 @@ def main(argv=None):
     for index, line in enumerate(lines):
         if opt.satellite:  # predict.py:258-264
             test_satellite(model, *satellite_names(opt.data_path, opt.save_path, line),
-                           opt.crop_height, opt.crop_width, opt.confidence, opt.conf_radius)
+                           opt.crop_height, opt.crop_width, opt.confidence, opt.conf_radius, opt.lr_check)
         if not opt.sceneflow:
             continue
         print(f"Running for sceneflow {index}")
@@ -236,9 +270,19 @@ def main(argv=None):
             gt, _, _ = read_pfm(gtname)
             plot_disparity(opt.save_path + f"{index:d}_gt.png", gt, 192)
         t0 = time.time()
-        disp = predict_pair(model, leftname, rightname, opt.crop_height, opt.crop_width,
-                            confidence=opt.confidence, radius=opt.conf_radius)
+        lr = None
+        if opt.lr_check > 0:
+            lr = predict_pair_lr(model, leftname, rightname, opt.crop_height, opt.crop_width, opt.lr_check)
+        if lr is None or opt.confidence != "none":  # with --confidence: its own call on the pair
+            disp = predict_pair(model, leftname, rightname, opt.crop_height, opt.crop_width,
+                                confidence=opt.confidence, radius=opt.conf_radius)
+        else:
+            disp = lr[0]
         print(f"Processing time: {time.time() - t0:.4f}")
+        if lr is not None:
+            save_lr(os.path.join(opt.save_path, f"{index}"), *lr[1:])
+            print(f"{index}: left-right check at {opt.lr_check:g} px flags {100.0 * float((lr[2] != 0).mean()):.2f} % "
+                  f"of the pixels ({100.0 * float((lr[2] == 2).mean()):.2f} % out of view)")
         if opt.confidence != "none":
             disp, conf, local = disp
             save_confidence(os.path.join(opt.save_path, f"{index}"), conf, local)
