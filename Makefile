@@ -60,10 +60,19 @@ build/asan/lr_asan_main.o: tests/asan/lr_asan.cpp include/leastereo_hip.h
 build/asan/lr_asan: build/asan/lr_asan_main.o $(ASANOBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -fno-gpu-sanitize -fsanitize=address -o $@ $^
 
-asan: build/asan/capi_asan build/asan/disp_stats_asan build/asan/lr_asan
+# the edge-aware loss's three entries (lea_median5x5_f32, lea_edge_loss_f32, lea_edge_loss_grad_f32)
+build/asan/loss_asan_main.o: tests/asan/loss_asan.cpp include/leastereo_hip.h
+	@mkdir -p build/asan
+	$(HIPCC) $(ASANFLAGS) -c $< -o $@
+
+build/asan/loss_asan: build/asan/loss_asan_main.o $(ASANOBJ)
+	$(HIPCC) --offload-arch=$(ARCH) -fno-gpu-sanitize -fsanitize=address -o $@ $^
+
+asan: build/asan/capi_asan build/asan/disp_stats_asan build/asan/lr_asan build/asan/loss_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/capi_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/disp_stats_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/lr_asan
+	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/loss_asan
 
 clean:
 	rm -rf build $(LIB)

@@ -270,6 +270,57 @@ int lea_disparity_regression_right(const void* cost, float* disp_right, int B, i
 int lea_disparity_lr_check(const float* disp_left, const float* disp_right, uint8_t* state,
                            float* disp_filled, int B, int H, int W, float threshold, void* stream);
 
+/* Edge-aware training loss (additive: the ABI number stays 14).  The reference's objective
+ * is train.py:107-118 combined_loss = smooth-L1 over the valid pixels + edge_loss_w *
+ * gradient_aware_loss2 (edge_detection.py:68-74), whose target is smoothed by two 5x5
+ * median passes on the host (edge_detection.py:7-11).  Three entries keep all of it on the
+ * device: the median, the forward sums and the gradient.  None synchronises the host,
+ * allocates or reads anything back; batch strides are in elements.
+ *
+ * 5x5 median, once or twice over.  y[b] = med(x[b]) for iterations = 1, med(med(x[b])) for
+ * iterations = 2, med being the exact 5x5 median (the 13th of the 25 window values) with
+ * the border replicated, as OpenCV's medianBlur documents (BORDER_REPLICATE).  The second
+ * pass replicates the first pass's outputs at the border.  One launch either way.
+ * x, y: [B, H, W] f32, batch strides >= H*W; H, W >= 1 (sizes below 5 are legal).
+ * x must hold no NaN (the result is then unspecified); +-inf is an ordinary value.
+ * A null pointer, iterations outside {1, 2}, a batch stride below H*W, a non-positive size
+ * or a y that overlaps x: LEA_E_INVALID, before any launch. */
+int lea_median5x5_f32(const float* x, int64_t x_bstride, float* y, int64_t y_bstride, int B,
+                      int H, int W, int iterations, void* stream);
+
+/* Forward sums.  pred, target, tsmooth (the twice-median target): [B, H, W] f32, H, W >= 3.
+ *   m = (target < maxdisp) & (target > 0.001),  d = pred - target
+ *   sums[0] = number of pixels in m
+ *   sums[1] = sum over m of smooth_l1(d), beta = 1: 0.5 d^2 if |d| < 1, else |d| - 0.5
+ *   sums[2] = sum over m of |d|                               (the train loop's EPE)
+ *   sums[3] = sum over the batch and the (H-2) x (W-2) positions of the valid 3x3
+ *             cross-correlation of |Sx pred| exp(-|Sx tsmooth|) + |Sy pred| exp(-|Sy tsmooth|),
+ *             Sx = [[-1,0,1],[-2,0,2],[-1,0,1]], Sy = [[1,2,1],[0,0,0],[-1,-2,-1]]; the
+ *             mask does not apply to it.
+ * The losses are sums[1] / sums[0] and sums[3] / (B (H-2)(W-2)); the weight between them
+ * is the caller's.  Terms in f32, summed in float64 in a fixed order: the same inputs give
+ * the same bits.  sums: 4 doubles on the device; workspace:
+ * lea_edge_loss_workspace_bytes(B, H, W) bytes on the device, both 8-byte aligned.  One
+ * pass over the maps and a one-workgroup reduction of its partials, in this call. */
+size_t lea_edge_loss_workspace_bytes(int B, int H, int W);
+int lea_edge_loss_f32(const float* pred, int64_t pred_bstride, const float* target,
+                      int64_t target_bstride, const float* tsmooth, int64_t tsmooth_bstride,
+                      int B, int H, int W, float maxdisp, double* sums, void* workspace,
+                      void* stream);
+
+/* Gradient with respect to pred of g_d * sums[1] / sums[0] + g_e * sums[3] / (B (H-2)(W-2)):
+ *   dpred = g_d m clamp(d, -1, 1) / n  +  g_e / (B (H-2)(W-2)) * sum over the positions that
+ *           cover the pixel of sign(Sx pred) exp(-|Sx tsmooth|) Sx[ky][kx]
+ *                            + sign(Sy pred) exp(-|Sy tsmooth|) Sy[ky][kx]
+ * with sign(0) = 0.  n = sums[0] (as lea_edge_loss_f32 left it) and scales = {g_d, g_e}
+ * (2 floats) are read on the device.  n = 0: the direct part is 0.  One launch, no atomics,
+ * every pixel of dpred written.  dpred may overlap none of the inputs. */
+int lea_edge_loss_grad_f32(const float* pred, int64_t pred_bstride, const float* target,
+                           int64_t target_bstride, const float* tsmooth, int64_t tsmooth_bstride,
+                           const double* sums, const float* scales, float* dpred,
+                           int64_t dpred_bstride, int B, int H, int W, float maxdisp,
+                           void* stream);
+
 /* ---- bf16 path (BASELINE configs 3 and 4) ----
  * Activations are bf16 in the "c8" layout: NCDHW with channels blocked by 8
  * innermost, x[b][c/8][d][h][w][c%8] (one voxel's 8 channels = one 16-byte word;

@@ -59,6 +59,12 @@ SIGNATURES = {
     "lea_disparity_regression_stats": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "lea_disparity_regression_right": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "lea_disparity_lr_check": (_i, [_p, _p, _p, _p, _i, _i, _i, ctypes.c_float, _p]),
+    # edge-aware training loss (csrc/median.hip, csrc/edge_loss.hip)
+    "lea_median5x5_f32": (_i, [_p, _i64, _p, _i64, _i, _i, _i, _i, _p]),
+    "lea_edge_loss_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "lea_edge_loss_f32": (_i, [_p, _i64, _p, _i64, _p, _i64, _i, _i, _i, ctypes.c_float, _p, _p, _p]),
+    "lea_edge_loss_grad_f32": (_i, [_p, _i64, _p, _i64, _p, _i64, _p, _p, _p, _i64, _i, _i, _i,
+                                    ctypes.c_float, _p]),
     # bf16 path (c8 layout)
     "lea_conv3d_packed_elems_bf16": (ctypes.c_size_t, [_i, _i, _i]),
     "lea_conv3d_pack_weights_bf16": (_i, [_p, _p, _i, _i, _i, _p]),

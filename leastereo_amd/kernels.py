@@ -613,6 +613,85 @@ def lr_check(disp_left: torch.Tensor, disp_right: torch.Tensor, threshold: float
     return DisparityLR(disp_left, disp_right, state, filled)
 
 
+# ---- edge-aware training loss (csrc/median.hip, csrc/edge_loss.hip) ----
+
+def _plane_view(t: torch.Tensor, name: str):
+    """[B, H, W] float32 whose (H, W) block is contiguous per batch (a copy if it is not);
+    returns the tensor and its batch stride in elements."""
+    b, h, w = t.shape
+    if t.stride()[1:] != (w, 1) or (b > 1 and t.stride(0) < h * w):
+        t = t.contiguous()
+    return t, (t.stride(0) if b > 1 else h * w)
+
+
+def median_blur5(x: torch.Tensor, iterations: int = 1) -> torch.Tensor:
+    """Exact 5x5 median with a replicated border (``lea_median5x5_f32``: OpenCV's
+    ``medianBlur(x, 5)``), applied ``iterations`` (1 or 2) times in one launch.
+    [B, H, W] or [H, W] float32 on the ROCm device, NaN-free; returns the same shape."""
+    _require_cuda(x)
+    if x.dim() not in (2, 3):
+        raise ValueError(f"median_blur5: [B, H, W] or [H, W] expected, got {tuple(x.shape)}")
+    if iterations not in (1, 2):
+        raise ValueError("median_blur5: iterations must be 1 or 2")
+    x3 = x.unsqueeze(0) if x.dim() == 2 else x
+    x3, xbs = _plane_view(x3, "x")
+    b, h, w = x3.shape
+    y = torch.empty((b, h, w), device=x.device, dtype=torch.float32)
+    rec = None if _probe is None else _probe_launch("median5x5", 0.0, 8.0 * y.numel())
+    check(_lib.load().lea_median5x5_f32(x3.data_ptr(), xbs, y.data_ptr(), h * w, b, h, w, int(iterations),
+                                        _stream()), "lea_median5x5_f32")
+    _probe_end(rec)
+    return y.squeeze(0) if x.dim() == 2 else y
+
+
+EDGE_LOSS_FIELDS = ("n_valid", "sum_smooth_l1", "sum_abs", "sum_edge")
+
+
+def _edge_maps(pred, target, tsmooth):
+    _require_cuda(pred, target, tsmooth)
+    if pred.dim() != 3 or pred.shape != target.shape or pred.shape != tsmooth.shape:
+        raise ValueError("pred, target and tsmooth must be [B, H, W] of one shape")
+    if pred.shape[1] < 3 or pred.shape[2] < 3:
+        raise ValueError("the edge term needs H >= 3 and W >= 3")
+    return _plane_view(pred, "pred"), _plane_view(target, "target"), _plane_view(tsmooth, "tsmooth")
+
+
+def edge_loss_sums(pred: torch.Tensor, target: torch.Tensor, tsmooth: torch.Tensor, maxdisp: float) -> torch.Tensor:
+    """The four sums of ``lea_edge_loss_f32`` (include/leastereo_hip.h), float64 [4] on the
+    device in the order of ``EDGE_LOSS_FIELDS``; nothing is read back."""
+    (p, pbs), (t, tbs), (s, sbs) = _edge_maps(pred, target, tsmooth)
+    b, h, w = p.shape
+    lib = _lib.load()
+    ws = torch.empty(lib.lea_edge_loss_workspace_bytes(b, h, w) // 8, device=p.device, dtype=torch.float64)
+    sums = torch.empty(4, device=p.device, dtype=torch.float64)
+    rec = None if _probe is None else _probe_launch("edge_loss", 0.0, 12.0 * p.numel())
+    check(lib.lea_edge_loss_f32(p.data_ptr(), pbs, t.data_ptr(), tbs, s.data_ptr(), sbs, b, h, w, float(maxdisp),
+                                sums.data_ptr(), ws.data_ptr(), _stream()), "lea_edge_loss_f32")
+    _probe_end(rec)
+    return sums
+
+
+def edge_loss_grad(pred: torch.Tensor, target: torch.Tensor, tsmooth: torch.Tensor, maxdisp: float,
+                   sums: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """``lea_edge_loss_grad_f32``: the gradient with respect to ``pred`` of
+    ``scales[0] * direct + scales[1] * edge``; ``sums`` is what ``edge_loss_sums`` returned
+    for the same maps, ``scales`` two float32 on the device."""
+    (p, pbs), (t, tbs), (s, sbs) = _edge_maps(pred, target, tsmooth)
+    _require_cuda(scales)
+    if not sums.is_cuda or sums.dtype != torch.float64 or sums.numel() != 4 or not sums.is_contiguous():
+        raise ValueError("sums: the contiguous float64 [4] device tensor of edge_loss_sums")
+    if scales.numel() != 2 or not scales.is_contiguous():
+        raise ValueError("scales: two contiguous float32 (g_direct, g_edge) on the device")
+    b, h, w = p.shape
+    dpred = torch.empty((b, h, w), device=p.device, dtype=torch.float32)
+    rec = None if _probe is None else _probe_launch("edge_loss_grad", 0.0, 16.0 * p.numel())
+    check(_lib.load().lea_edge_loss_grad_f32(p.data_ptr(), pbs, t.data_ptr(), tbs, s.data_ptr(), sbs,
+                                             sums.data_ptr(), scales.data_ptr(), dpred.data_ptr(), h * w, b, h, w,
+                                             float(maxdisp), _stream()), "lea_edge_loss_grad_f32")
+    _probe_end(rec)
+    return dpred
+
+
 # ------------------------------------------------------------------ bf16 path (c8)
 # Activations: torch.bfloat16 [B, C/8, D, H, W, 8] ("c8": 8 channels per voxel word).
 

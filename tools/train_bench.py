@@ -6,6 +6,7 @@ this GPU) -- a measurement tool, not part of the product.  Also times ConvBR3d
 forward + backward alone at the hot layer shapes.  One JSON line per measurement.
 
     python tools/train_bench.py [--height 288 --width 576 --maxdisp 96] [--steps 5]
+    python tools/train_bench.py --edge_loss_w 0.2 ...   the reference's combined_loss (train.py:107-113)
 """
 from __future__ import annotations
 
@@ -20,7 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
-from leastereo_amd import training  # noqa: E402
+from leastereo_amd import losses, training  # noqa: E402
 from leastereo_amd.config import LEAStereoArgs, default_arch_args  # noqa: E402
 from leastereo_amd.model import LEAStereo  # noqa: E402
 
@@ -52,7 +53,30 @@ def _torch_disp(cost, maxdisp):
     return torch.sum(p * torch.arange(maxdisp, device=cost.device, dtype=p.dtype).view(1, maxdisp, 1, 1), 1)
 
 
-def step_fn(model, fl, fr, target, impl):
+def _torch_combined_loss(disp, target, tsmooth, maxdisp, w):
+    """train.py:107-118 and edge_detection.py:68-74 from torch ops; ``tsmooth`` is the
+    twice-median target, formed once outside the timed region (the reference forms it on
+    the host with cv2 every step; cv2 is not available here, so that round trip is not part
+    of this leg -- tools/loss_probe.py times a scipy stand-in for it)."""
+    mask = (target < maxdisp) & (target > 0.001)
+    direct = F.smooth_l1_loss(disp[mask], target[mask], reduction="mean")
+    kx = disp.new_tensor([[-1, 0, 1], [-2, 0, 2], [-1, 0, 1]]).view(1, 1, 3, 3)
+    ky = disp.new_tensor([[1, 2, 1], [0, 0, 0], [-1, -2, -1]]).view(1, 1, 3, 3)
+    ox, oy = F.conv2d(disp.unsqueeze(1), kx), F.conv2d(disp.unsqueeze(1), ky)
+    tx, ty = F.conv2d(tsmooth.unsqueeze(1), kx), F.conv2d(tsmooth.unsqueeze(1), ky)
+    edge = torch.mean(torch.abs(ox) * torch.exp(-torch.abs(tx)) + torch.abs(oy) * torch.exp(-torch.abs(ty)))
+    return direct + edge * w
+
+
+def _loss(disp, target, tsmooth, maxdisp, edge_loss_w, impl):
+    if not edge_loss_w:
+        return None
+    if impl == "torch":
+        return _torch_combined_loss(disp, target, tsmooth, maxdisp, edge_loss_w)
+    return losses.combined_loss(disp, target, maxdisp, edge_loss_w)
+
+
+def step_fn(model, fl, fr, target, impl, edge_loss_w=0.0, tsmooth=None):
     if impl == "torch":
         saved = training._convbr, training.interpolate3d
         training._convbr, training.interpolate3d = _torch_convbr, _torch_interp
@@ -63,7 +87,9 @@ def step_fn(model, fl, fr, target, impl):
             training._convbr, training.interpolate3d = saved
     else:
         disp = training.cost_to_disparity_train(model, fl, fr)
-    loss = F.smooth_l1_loss(disp, target)
+    loss = _loss(disp, target, tsmooth, model.maxdisp, edge_loss_w, impl)
+    if loss is None:
+        loss = F.smooth_l1_loss(disp, target)
     loss.backward()
     return loss
 
@@ -87,7 +113,11 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--impl", default="hip,torch")
-    ap.add_argument("--whole", type=int, default=0, help="1: time only the whole-model train step")
+    ap.add_argument("--whole", type=int, default=0, help="1: time only the whole-model train step; 2: that step with the plain loss and with "
+                         "--edge_loss_w (0.2 if not given) in alternating windows of one process")
+    ap.add_argument("--edge_loss_w", type=float, default=0.0,
+                    help="> 0: the step's loss is the reference's combined_loss with this weight "
+                         "(leastereo_amd.losses on the hip impl, torch ops on the torch impl); 0: off")
     ap.add_argument("--torch-modes", default="default,benchmark",
                     help="MIOpen modes for the torch leg: default (immediate mode) and/or benchmark "
                          "(torch.backends.cudnn.benchmark=True: MIOpen's find per shape, more warm-up)")
@@ -113,13 +143,15 @@ def main():
     fl = torch.randn(1, 32, h3, w3, device=dev, generator=gen).requires_grad_(True)
     fr = torch.randn(1, 32, h3, w3, device=dev, generator=gen).requires_grad_(True)
     target = torch.rand(1, 3 * h3, 3 * w3, device=dev, generator=gen) * args.maxdisp
+    tsmooth = losses.smooth_target(target) if args.edge_loss_w else None
     for impl in args.impl.split(","):
         for mode in (args.torch_modes.split(",") if impl == "torch" else ["-"]):
             torch.backends.cudnn.benchmark = mode == "benchmark"
             warm = args.warmup + (3 if mode == "benchmark" else 0)
             t0 = time.perf_counter()
-            ms = timed(lambda: step_fn(model, fl, fr, target, impl), args.steps, warm)
+            ms = timed(lambda: step_fn(model, fl, fr, target, impl, args.edge_loss_w, tsmooth), args.steps, warm)
             print(json.dumps({"what": "matching_train_step", "impl": impl, "miopen_mode": mode,
+                              "edge_loss_w": args.edge_loss_w,
                               "height": args.height, "width": args.width, "maxdisp": args.maxdisp,
                               "ms": round(ms, 2), "warmup_steps": warm,
                               "wall_s": round(time.perf_counter() - t0, 1),
@@ -137,16 +169,37 @@ def whole_model(args, dev):
     right = torch.randn(1, 3, args.height, args.width, device=dev, generator=gen).requires_grad_(True)
     target = torch.rand(1, args.height, args.width, device=dev, generator=gen) * (args.maxdisp - 1)
 
-    def step():
+    def step(edge_loss_w=args.edge_loss_w):
         opt.zero_grad()
         disp = model(left, right)
-        mask = (target < args.maxdisp) & (target > 0.001)
-        F.smooth_l1_loss(disp[mask], target[mask], reduction="mean").backward()
+        if edge_loss_w:
+            losses.combined_loss(disp, target, args.maxdisp, edge_loss_w).backward()
+        else:
+            mask = (target < args.maxdisp) & (target > 0.001)
+            F.smooth_l1_loss(disp[mask], target[mask], reduction="mean").backward()
         opt.step()
     torch.cuda.reset_peak_memory_stats()
+    if args.whole == 2:
+        # processes differ by more than the loss costs: both steps in this one, in alternating
+        # windows of --steps steps, the order reversed every other round; medians of the windows
+        ws = (0.0, args.edge_loss_w or 0.2)
+        t = {w: [] for w in ws}
+        for w in ws:
+            timed(lambda: step(w), 1, args.warmup)
+        for r in range(7):
+            for w in (ws if r % 2 == 0 else ws[::-1]):
+                t[w].append(timed(lambda: step(w), args.steps, 0))
+        for w in ws:
+            v = sorted(t[w])
+            print(json.dumps({"what": "whole_model_train_step_ab", "impl": "hip", "height": args.height,
+                              "width": args.width, "maxdisp": args.maxdisp, "edge_loss_w": w,
+                              "ms_median": round(v[len(v) // 2], 2), "ms_min": round(v[0], 2),
+                              "ms_max": round(v[-1], 2), "windows": len(v), "steps_per_window": args.steps}),
+                  flush=True)
+        return
     ms = timed(step, args.steps, args.warmup)
     print(json.dumps({"what": "whole_model_train_step", "impl": "hip", "height": args.height, "width": args.width,
-                      "maxdisp": args.maxdisp, "ms": round(ms, 2),
+                      "maxdisp": args.maxdisp, "edge_loss_w": args.edge_loss_w, "ms": round(ms, 2),
                       "peak_gb": round(torch.cuda.max_memory_allocated() / 2 ** 30, 1)}), flush=True)
 
 
