@@ -68,11 +68,20 @@ build/asan/loss_asan_main.o: tests/asan/loss_asan.cpp include/leastereo_hip.h
 build/asan/loss_asan: build/asan/loss_asan_main.o $(ASANOBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -fno-gpu-sanitize -fsanitize=address -o $@ $^
 
-asan: build/asan/capi_asan build/asan/disp_stats_asan build/asan/lr_asan build/asan/loss_asan
+# the training transform's two entries (lea_train_transform_workspace_bytes, lea_train_transform_u8)
+build/asan/transform_asan_main.o: tests/asan/transform_asan.cpp include/leastereo_hip.h
+	@mkdir -p build/asan
+	$(HIPCC) $(ASANFLAGS) -c $< -o $@
+
+build/asan/transform_asan: build/asan/transform_asan_main.o $(ASANOBJ)
+	$(HIPCC) --offload-arch=$(ARCH) -fno-gpu-sanitize -fsanitize=address -o $@ $^
+
+asan: build/asan/capi_asan build/asan/disp_stats_asan build/asan/lr_asan build/asan/loss_asan build/asan/transform_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/capi_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/disp_stats_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/lr_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/loss_asan
+	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/transform_asan
 
 clean:
 	rm -rf build $(LIB)

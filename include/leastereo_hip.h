@@ -464,6 +464,42 @@ int lea_standardize_crop_u8(const void* left, const void* right, int B, int H, i
                             int pix_stride, float* out_left, float* out_right, int crop_h,
                             int crop_w, void* workspace, void* stream);
 
+/* set_rgb_layers + train_transform of the training loader, fused: replaces
+ * dataloaders/datasets/common.py:119-131 (the standardisation above, whole-image
+ * statistics) and :43-91 (pad, random crop, optional left-against-right shift, target
+ * cut).  The random draws stay on the host (leastereo_amd/data.py sample_train_params
+ * draws them in the reference's order); the call sees only their outcome:
+ *   params: device int32 [B][5] = {src_y0, src_x0_left, src_x0_right, target_sub, flags}
+ *     out_left[b][c][y][x] and out_target[b][0][y][x] read source pixel
+ *       (y + src_y0, x + src_x0_left), out_right (y + src_y0, x + src_x0_right);
+ *     a source pixel outside [0,H) x [0,W) is pad: 0 in the image planes, 1000 in the
+ *     left disparity, 0 in the right disparity;
+ *     out_target = source - (float)target_sub, one float32 subtraction, pad included;
+ *     flags bit 0 = swap: out_left is cut from the right image, out_right from the left
+ *     image, the target from disp_right (all pad when disp_right is NULL); other bits
+ *     are ignored.
+ *     With the reference's canvas Hc x Wc (image at its bottom-right, py = Hc - H,
+ *     px = Wc - W): src_y0 = start_y - py, src_x0_left = start_x + shift_x - px,
+ *     src_x0_right = start_x - px, target_sub = shift_x.
+ *     The rows are not validated (they live in device memory so that a captured graph
+ *     replays with fresh crops): coordinates are formed in 64 bits and bounds-tested
+ *     before every read, so any five ints are memory-safe and give pad.
+ *   left/right: B uint8 HWC images [B, H, W, pix_stride] (3 or 4)
+ *   disp_left, disp_right: [B, H, W] float32; disp_right may be NULL
+ *   out_left/out_right: [B, 3, crop_h, crop_w], out_target: [B, 1, crop_h, crop_w] float32
+ *     (16-byte aligned when crop_w % 4 == 0)
+ *   n_valid: optional device int32 [B], cleared by the call: the count of target pixels
+ *     with t < maxdisp && t > 0.001f (train.py:116-118), float32 compares
+ *   workspace: lea_train_transform_workspace_bytes(B) bytes, cleared by the call.
+ * The statistics launch and the crop launch, behind a one-workgroup launch that clears
+ * the workspace and n_valid (kernels only: a captured call holds no memset node); all
+ * on `stream`, no host sync.                                                          */
+size_t lea_train_transform_workspace_bytes(int B);
+int lea_train_transform_u8(const void* left, const void* right, int B, int H, int W, int pix_stride,
+                           const float* disp_left, const float* disp_right, const int* params,
+                           float* out_left, float* out_right, float* out_target, int crop_h,
+                           int crop_w, float maxdisp, int* n_valid, void* workspace, void* stream);
+
 /* Disparity metrics of one batch, per pair b (device out[b][8], float64):
  *   [0] n    of evaluation.py:287 mask (gt >= 0.001 & gt <= maxdisp)
  *   [1] sum |pred - gt| over that mask          (EPE = [1] / [0], evaluation.py:288)

@@ -131,6 +131,10 @@ SIGNATURES = {
     # host steps either side of forward: predict.py load_data/test_transform, metrics
     "lea_standardize_workspace_bytes": (ctypes.c_size_t, [_i]),
     "lea_standardize_crop_u8": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _i, _i, _p, _p]),
+    # the training loader's host steps: set_rgb_layers + train_transform (common.py)
+    "lea_train_transform_workspace_bytes": (ctypes.c_size_t, [_i]),
+    "lea_train_transform_u8": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _i, _i,
+                                    ctypes.c_float, _p, _p, _p]),
     "lea_disparity_metrics_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
     "lea_disparity_metrics": (_i, [_p, _i64, _p, _i64, _i, _i, _i, ctypes.c_float, _i, _i,
                                    _i, _i, _i, _p, _p, _p, _p]),

@@ -14,7 +14,13 @@
 //    difference is truncated toward zero, NaN / out-of-range become INT64_MIN).
 //    Per-workgroup partials in a caller workspace, then a fixed-order final pass:
 //    bit-reproducible from run to run.
-// Both are HBM-bound streaming passes (bytes in DESIGN.md §4).
+//  * lea_train_transform_u8: the training counterpart of the first, set_rgb_layers +
+//    train_transform (dataloaders/datasets/common.py:119-131, :43-91): the same statistics
+//    launch, then one crop launch whose window, shift and swap come from a per-sample
+//    params row in device memory, and which also cuts the disparity target and counts its
+//    valid pixels (integer atomics: order-free).
+// The first two are HBM-bound streaming passes; the third's statistics launch is latency-bound at
+// training sizes (bytes and measurements in DESIGN.md §4).
 #include <cmath>
 
 #include "common.h"
@@ -157,6 +163,105 @@ __global__ __launch_bounds__(256) void u8_standardize_kernel(
 #pragma unroll
           for (int c = 0; c < 3; ++c) dst[c * plane + (long long)y * cw + x0 + k] = v[c][k];
     }
+  }
+}
+
+// ---------------------------------------------------------------- training transform
+constexpr int kTrainThreads = 256;
+
+// zeroes the sums and the counts of one call: a launch instead of two memset nodes, so that a
+// captured call is kernels only (replayed memset nodes did not clear reliably)
+__global__ __launch_bounds__(256) void train_clear_kernel(unsigned long long* __restrict__ sums, int nsums,
+                                                          int* __restrict__ n_valid, int B) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nsums; i += gridDim.x * blockDim.x) sums[i] = 0ULL;
+  if (n_valid)
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < B; i += gridDim.x * blockDim.x) n_valid[i] = 0;
+}
+
+// train_transform (dataloaders/datasets/common.py:43-91) after set_rgb_layers (:119-131):
+// grid (G, 2B), blockIdx.y = output image (0..B-1 the network's left input and the target,
+// B..2B-1 its right input).  params[b] = {src_y0, src_x0_left, src_x0_right, target_sub,
+// flags} is read from device memory and trusted for nothing: source coordinates are formed
+// in 64 bits and tested against [0,H) x [0,W) before every read, so any five ints give pad.
+// Bit 0 of flags swaps the pair (the other view's image, table and disparity).
+__global__ __launch_bounds__(kTrainThreads) void u8_train_transform_kernel(
+    const uint8_t* __restrict__ left, const uint8_t* __restrict__ right, int B, int H, int W,
+    int pix_stride, const float* __restrict__ disp_l, const float* __restrict__ disp_r,
+    const int* __restrict__ params, const unsigned long long* __restrict__ sums,
+    float* __restrict__ out_l, float* __restrict__ out_r, float* __restrict__ out_t, int ch, int cw,
+    float maxdisp, int* __restrict__ n_valid) {
+  const bool out_is_left = blockIdx.y < B;
+  const int b = out_is_left ? blockIdx.y : blockIdx.y - B;
+  const int* p = params + (long long)b * 5;
+  const long long y0 = p[0];
+  const long long x0s = out_is_left ? p[1] : p[2];
+  const float tsub = (float)p[3];
+  const bool swap = (p[4] & 1) != 0;
+  const bool src_is_left = out_is_left != swap;
+  const int simg = src_is_left ? b : B + b;  // row of the statistics
+  __shared__ float lut[3][256];
+  for (int e = threadIdx.x; e < 3 * 256; e += blockDim.x) {
+    const int c = e / 256;
+    lut[c][e % 256] = standardized(sums[((long long)simg * 3 + c) * 2],
+                                   sums[((long long)simg * 3 + c) * 2 + 1], (long long)H * W, e % 256);
+  }
+  __syncthreads();
+  const uint8_t* src = (src_is_left ? left : right) + (long long)b * H * W * pix_stride;
+  float* dst = (out_is_left ? out_l : out_r) + (long long)b * 3 * ch * cw;
+  const long long plane = (long long)ch * cw;
+  // the target follows the left input's window; pad 1000 for the left disparity, 0 for the
+  // right (common.py:49,56); a swap without a right disparity is all pad
+  const float* dsp = swap ? disp_r : disp_l;
+  if (dsp) dsp += (long long)b * H * W;
+  const float tpad = swap ? 0.f : 1000.f;
+  float* dst_t = out_t + (long long)b * plane;
+  int count = 0;
+  const int qw = (cw + 3) / 4;  // float4 columns per crop row
+  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < ch * qw; t += gridDim.x * blockDim.x) {
+    const int y = t / qw, x0 = (t - y * qw) * 4;
+    const long long sy = y + y0;
+    const bool row_in = sy >= 0 && sy < H;
+    float v[3][4], tv[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const long long sx = x0 + k + x0s;
+      const bool in = row_in && sx >= 0 && sx < W;
+      const long long pix = in ? sy * W + sx : 0;  // < H * W < 2^31
+      const uint8_t* q = src + pix * pix_stride;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) v[c][k] = in ? lut[c][q[c]] : 0.f;
+      if (out_is_left) {
+        tv[k] = ((in && dsp) ? dsp[pix] : tpad) - tsub;
+        // train.py:116-118 on the finished crop
+        count += (x0 + k < cw) && (tv[k] < maxdisp) && (tv[k] > 0.001f);
+      }
+    }
+    const long long o = (long long)y * cw + x0;
+    if ((cw & 3) == 0) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        *reinterpret_cast<float4*>(dst + c * plane + o) = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
+      if (out_is_left) *reinterpret_cast<float4*>(dst_t + o) = make_float4(tv[0], tv[1], tv[2], tv[3]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (x0 + k < cw) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) dst[c * plane + o + k] = v[c][k];
+          if (out_is_left) dst_t[o + k] = tv[k];
+        }
+    }
+  }
+  if (!out_is_left || !n_valid) return;  // uniform over the workgroup
+  // integer counts: waves by shuffles, the workgroup through LDS, one atomic per workgroup
+  __shared__ int red[kTrainThreads / kWave];
+  for (int o = kWave / 2; o > 0; o >>= 1) count += __shfl_xor(count, o);
+  if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = count;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int total = 0;
+    for (int w = 0; w < kTrainThreads / kWave; ++w) total += red[w];
+    if (total) atomicAdd(n_valid + b, total);
   }
 }
 
@@ -322,6 +427,58 @@ extern "C" int lea_standardize_crop_u8(const void* left, const void* right, int 
       (const uint8_t*)left, (const uint8_t*)right, B, H, W, pix_stride,
       (const unsigned long long*)workspace, out_left, out_right, crop_h, crop_w, pad ? 1 : 0);
   return launch_status("lea_standardize_crop_u8");
+}
+
+extern "C" size_t lea_train_transform_workspace_bytes(int B) {
+  return lea_standardize_workspace_bytes(B);  // the same exact integer sums
+}
+
+extern "C" int lea_train_transform_u8(const void* left, const void* right, int B, int H, int W,
+                                      int pix_stride, const float* disp_left, const float* disp_right,
+                                      const int* params, float* out_left, float* out_right,
+                                      float* out_target, int crop_h, int crop_w, float maxdisp,
+                                      int* n_valid, void* workspace, void* stream) {
+  using namespace lea;
+  clear_error();
+  LEA_CHECK_ARG(left && right && disp_left && params && out_left && out_right && out_target && workspace,
+                "lea_train_transform_u8: null pointer");
+  LEA_CHECK_ARG(B > 0 && H > 0 && W > 0 && crop_h > 0 && crop_w > 0,
+                "lea_train_transform_u8: bad shape B=%d H=%d W=%d crop %dx%d", B, H, W, crop_h, crop_w);
+  LEA_CHECK_ARG(pix_stride >= 3 && pix_stride <= 4,
+                "lea_train_transform_u8: pixel stride %d (RGB = 3, RGBA = 4)", pix_stride);
+  LEA_CHECK_ARG((long long)H * W < (1LL << 31) && (long long)crop_h * crop_w < (1LL << 31),
+                "lea_train_transform_u8: image too large");
+  LEA_CHECK_ARG(!(maxdisp != maxdisp), "lea_train_transform_u8: maxdisp is NaN");
+  // the crop kernel stores float4 when crop_w % 4 == 0
+  LEA_CHECK_ARG((crop_w & 3) != 0 ||
+                    ((((uintptr_t)out_left) | ((uintptr_t)out_right) | ((uintptr_t)out_target)) & 15) == 0,
+                "lea_train_transform_u8: outputs must be 16-byte aligned when crop_w %% 4 == 0");
+  LEA_CHECK_ARG((((uintptr_t)params) & 3) == 0 && (((uintptr_t)n_valid) & 3) == 0 &&
+                    (((uintptr_t)workspace) & 7) == 0,
+                "lea_train_transform_u8: misaligned params, n_valid or workspace");
+  hipStream_t st = as_stream(stream);
+  const long long npix = (long long)H * W;
+  const int nsums = B * 2 * 3 * 2;
+  train_clear_kernel<<<(nsums + 255) / 256, 256, 0, st>>>((unsigned long long*)workspace, nsums, n_valid, B);
+  int rc = launch_status("lea_train_transform_u8 (clear)");
+  if (rc) return rc;
+  // the statistics launch of lea_standardize_crop_u8, as it is
+  long long g = (npix + kStatThreads * 16 - 1) / (kStatThreads * 16);
+  g = g > 1024 ? 1024 : g;
+  const long long gmin = (npix + ((long long)kStatThreads << 23) - 1) / ((long long)kStatThreads << 23);
+  g = g < gmin ? gmin : g;
+  u8_stats_kernel<<<dim3((unsigned)g, 2 * B), kStatThreads, 0, st>>>(
+      (const uint8_t*)left, (const uint8_t*)right, B, npix, pix_stride,
+      (unsigned long long*)workspace);
+  rc = launch_status("lea_train_transform_u8 (stats)");
+  if (rc) return rc;
+  const long long quads = (long long)crop_h * ((crop_w + 3) / 4);
+  const int gx = (int)((quads + kTrainThreads * 2 - 1) / (kTrainThreads * 2));
+  u8_train_transform_kernel<<<dim3(gx, 2 * B), kTrainThreads, 0, st>>>(
+      (const uint8_t*)left, (const uint8_t*)right, B, H, W, pix_stride, disp_left, disp_right, params,
+      (const unsigned long long*)workspace, out_left, out_right, out_target, crop_h, crop_w, maxdisp,
+      n_valid);
+  return launch_status("lea_train_transform_u8");
 }
 
 extern "C" size_t lea_disparity_metrics_workspace_bytes(int B, int H, int W) {

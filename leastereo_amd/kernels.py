@@ -1083,6 +1083,52 @@ def standardize_crop_u8(left: torch.Tensor, right: torch.Tensor, crop_height: in
     return out_l, out_r
 
 
+def train_transform_u8(left: torch.Tensor, right: torch.Tensor, disp_left: torch.Tensor, disp_right,
+                       params: torch.Tensor, crop_height: int, crop_width: int, maxdisp: float):
+    """common.py:119-131 (set_rgb_layers) fused with :43-91 (train_transform) on the device.
+
+    ``left``/``right``: uint8 [B, H, W, 3|4]; ``disp_left``/``disp_right``: float32 [B, H, W]
+    (``disp_right`` may be None); ``params``: int32 [B, 5] rows of
+    ``{src_y0, src_x0_left, src_x0_right, target_sub, flags}`` (``data.sample_train_params``),
+    all on the ROCm device.  Returns (left, right float32 [B, 3, ch, cw], target float32
+    [B, 1, ch, cw], n_valid int32 [B]).  Nothing is copied to the host and nothing
+    synchronises: the launches read ``params`` from device memory, so the call can be
+    captured in a graph and replayed after ``params`` is overwritten."""
+    for t in (left, right):
+        if not t.is_cuda or t.dtype != torch.uint8:
+            raise _lib.HipKernelError(f"train_transform_u8 needs uint8 device images, got "
+                                      f"{t.dtype} on {t.device}")
+    _require_cuda(disp_left, disp_right)
+    if not params.is_cuda or params.dtype != torch.int32:
+        raise _lib.HipKernelError(f"train_transform_u8 needs int32 device params, got "
+                                  f"{params.dtype} on {params.device}")
+    if left.shape != right.shape or left.dim() != 4 or left.shape[-1] not in (3, 4):
+        raise ValueError(f"left/right must both be [B, H, W, 3|4] uint8, got {tuple(left.shape)} "
+                         f"and {tuple(right.shape)}")
+    b, h, w, ps = left.shape
+    for d in (disp_left, disp_right):
+        if d is not None and tuple(d.shape) != (b, h, w):
+            raise ValueError(f"disparities must be [B, H, W] = {(b, h, w)}, got {tuple(d.shape)}")
+    if tuple(params.shape) != (b, 5):
+        raise ValueError(f"params must be [B, 5] = {(b, 5)}, got {tuple(params.shape)}")
+    left, right, disp_left, params = left.contiguous(), right.contiguous(), disp_left.contiguous(), params.contiguous()
+    if disp_right is not None:
+        disp_right = disp_right.contiguous()
+    lib = _lib.load()
+    dev = left.device
+    ws = torch.empty(lib.lea_train_transform_workspace_bytes(b), device=dev, dtype=torch.uint8)
+    out_l = torch.empty((b, 3, crop_height, crop_width), device=dev, dtype=torch.float32)
+    out_r = torch.empty_like(out_l)
+    out_t = torch.empty((b, 1, crop_height, crop_width), device=dev, dtype=torch.float32)
+    n_valid = torch.empty((b,), device=dev, dtype=torch.int32)
+    check(lib.lea_train_transform_u8(left.data_ptr(), right.data_ptr(), b, h, w, ps, disp_left.data_ptr(),
+                                     disp_right.data_ptr() if disp_right is not None else None,
+                                     params.data_ptr(), out_l.data_ptr(), out_r.data_ptr(), out_t.data_ptr(),
+                                     crop_height, crop_width, float(maxdisp), n_valid.data_ptr(),
+                                     ws.data_ptr(), _stream()), "lea_train_transform_u8")
+    return out_l, out_r, out_t, n_valid
+
+
 METRIC_FIELDS = ("n_epe", "sum_abs", "n_valid", "n_correct3", "n_le_thr1", "n_le_thr2", "n_le_thr3")
 
 

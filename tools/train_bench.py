@@ -7,6 +7,8 @@ forward + backward alone at the hot layer shapes.  One JSON line per measurement
 
     python tools/train_bench.py [--height 288 --width 576 --maxdisp 96] [--steps 5]
     python tools/train_bench.py --edge_loss_w 0.2 ...   the reference's combined_loss (train.py:107-113)
+    python tools/train_bench.py --whole 1 --device_transform 1 [--src_height 540 --src_width 960]
+                                                        the loader's transform inside the timed step
 """
 from __future__ import annotations
 
@@ -118,6 +120,12 @@ def main():
     ap.add_argument("--edge_loss_w", type=float, default=0.0,
                     help="> 0: the step's loss is the reference's combined_loss with this weight "
                          "(leastereo_amd.losses on the hip impl, torch ops on the torch impl); 0: off")
+    ap.add_argument("--device_transform", type=int, default=0,
+                    help="1 (with --whole 1): the step starts from decoded uint8 pairs of --src_height x "
+                         "--src_width and their disparity, standardised, random-cropped to --height x --width "
+                         "and cut to the target on the device (leastereo_amd.data.DeviceTrainTransform)")
+    ap.add_argument("--src_height", type=int, default=540)
+    ap.add_argument("--src_width", type=int, default=960)
     ap.add_argument("--torch-modes", default="default,benchmark",
                     help="MIOpen modes for the torch leg: default (immediate mode) and/or benchmark "
                          "(torch.backends.cudnn.benchmark=True: MIOpen's find per shape, more warm-up)")
@@ -169,8 +177,24 @@ def whole_model(args, dev):
     right = torch.randn(1, 3, args.height, args.width, device=dev, generator=gen).requires_grad_(True)
     target = torch.rand(1, args.height, args.width, device=dev, generator=gen) * (args.maxdisp - 1)
 
+    tf = None
+    if args.device_transform:
+        # the loader's per-sample transform inside the timed step: decoded uint8 pairs and
+        # disparities (synthetic, already on the device) through leastereo_amd.data
+        from leastereo_amd.data import DeviceTrainTransform
+        src = (1, args.src_height, args.src_width)
+        left_u8 = torch.randint(0, 256, src + (3,), device=dev, dtype=torch.uint8, generator=gen)
+        right_u8 = torch.randint(0, 256, src + (3,), device=dev, dtype=torch.uint8, generator=gen)
+        disp_u8 = torch.rand(src, device=dev, generator=gen) * (args.maxdisp - 1)
+        tf = DeviceTrainTransform(args.height, args.width, args.maxdisp, device=dev)
+
     def step(edge_loss_w=args.edge_loss_w):
+        nonlocal left, right, target
         opt.zero_grad()
+        if tf is not None:
+            batch = tf(left_u8, right_u8, disp_u8)
+            left, right = batch.left.requires_grad_(True), batch.right.requires_grad_(True)
+            target = batch.target.squeeze(1)
         disp = model(left, right)
         if edge_loss_w:
             losses.combined_loss(disp, target, args.maxdisp, edge_loss_w).backward()
@@ -198,9 +222,12 @@ def whole_model(args, dev):
                   flush=True)
         return
     ms = timed(step, args.steps, args.warmup)
-    print(json.dumps({"what": "whole_model_train_step", "impl": "hip", "height": args.height, "width": args.width,
-                      "maxdisp": args.maxdisp, "edge_loss_w": args.edge_loss_w, "ms": round(ms, 2),
-                      "peak_gb": round(torch.cuda.max_memory_allocated() / 2 ** 30, 1)}), flush=True)
+    line = {"what": "whole_model_train_step", "impl": "hip", "height": args.height, "width": args.width,
+            "maxdisp": args.maxdisp, "edge_loss_w": args.edge_loss_w, "ms": round(ms, 2),
+            "peak_gb": round(torch.cuda.max_memory_allocated() / 2 ** 30, 1)}
+    if tf is not None:  # the default line keeps its keys
+        line.update({"device_transform": 1, "src_height": args.src_height, "src_width": args.src_width})
+    print(json.dumps(line), flush=True)
 
 
 if __name__ == "__main__":
