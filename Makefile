@@ -76,12 +76,22 @@ build/asan/transform_asan_main.o: tests/asan/transform_asan.cpp include/leastere
 build/asan/transform_asan: build/asan/transform_asan_main.o $(ASANOBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -fno-gpu-sanitize -fsanitize=address -o $@ $^
 
-asan: build/asan/capi_asan build/asan/disp_stats_asan build/asan/lr_asan build/asan/loss_asan build/asan/transform_asan
+# photometric consistency's three entries (lea_photometric_workspace_bytes, lea_photometric_f32,
+# lea_photometric_grad_f32)
+build/asan/photo_asan_main.o: tests/asan/photo_asan.cpp include/leastereo_hip.h
+	@mkdir -p build/asan
+	$(HIPCC) $(ASANFLAGS) -c $< -o $@
+
+build/asan/photo_asan: build/asan/photo_asan_main.o $(ASANOBJ)
+	$(HIPCC) --offload-arch=$(ARCH) -fno-gpu-sanitize -fsanitize=address -o $@ $^
+
+asan: build/asan/capi_asan build/asan/disp_stats_asan build/asan/lr_asan build/asan/loss_asan build/asan/transform_asan build/asan/photo_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/capi_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/disp_stats_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/lr_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/loss_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/transform_asan
+	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/photo_asan
 
 clean:
 	rm -rf build $(LIB)

@@ -321,6 +321,74 @@ int lea_edge_loss_grad_f32(const float* pred, int64_t pred_bstride, const float*
                            int64_t dpred_bstride, int B, int H, int W, float maxdisp,
                            void* stream);
 
+/* Photometric consistency (additive: the ABI number stays 14).  The right image is warped
+ * to the left view with a disparity map and compared with the left image by an SSIM + L1
+ * error: a label-free quality measure and the self-supervised training signal.  Three
+ * entries: the workspace query, the forward sums (with two optional maps) and the gradient
+ * with respect to the disparity.  None synchronises the host, allocates or reads anything
+ * back; batch strides are in elements.
+ *
+ * Inputs.  left, right: [B, C, H, W] f32, 1 <= C <= 4, H, W >= 3, the (C, H, W) block
+ * contiguous, any batch stride >= C*H*W.  disp: [B, H, W] f32, batch stride >= H*W.
+ * exclude: NULL or [B, H, W] bytes, batch stride >= H*W; non-zero = the pixel takes no part
+ * (the state of lea_disparity_lr_check can be passed as it is).  0 <= alpha <= 1, c1, c2 > 0.
+ *
+ * Warp, per pixel (y, x) and channel c, R = right[b, c]:
+ *   xs      = float(x) - disp[b, y, x]            one f32 subtraction
+ *   in_view = isfinite(disp) && xs >= 0 && xs <= W - 1
+ *   x0      = min(floor(xs), W - 2),  t = xs - x0  (exact; 0 <= t <= 1)
+ *   w_c     = R[y, x0] + t (R[y, x0 + 1] - R[y, x0]),  correctly rounded to f32
+ *   dw_c / ddisp = -(R[y, x0 + 1] - R[y, x0])      at an integer xs: the cell to its right
+ *   out of view: w_c = 0 and the derivative is 0.
+ * Masks: v(p) = in_view(p) && !exclude(p); vs(p) = p is an interior position
+ * (1 <= y <= H - 2, 1 <= x <= W - 2) and v holds on all nine pixels of its 3x3 window.
+ * Terms, in f32:
+ *   l1(p)    = mean_c |L_c - w_c|
+ *   dssim(p) = mean_c clamp((1 - SSIM_c(p)) / 2, 0, 1)
+ *   SSIM     = (2 mu_x mu_y + c1)(2 s_xy + c2) / ((mu_x^2 + mu_y^2 + c1)(s_x^2 + s_y^2 + c2))
+ *              over the 3x3 window, x = left, y = warped; mu = box sum / 9,
+ *              s_x^2 = E[x^2] - mu_x^2, s_xy = E[xy] - mu_x mu_y (evaluated in the centred
+ *              form sum (x - mu)^2 / 9, the same function with less cancellation).
+ * Sums, float64, in a fixed order (per-workgroup partials in the workspace, reduced by one
+ * workgroup in the same call; the same inputs give the same bits):
+ *   sums[0] = #v   sums[1] = sum_v l1   sums[2] = #vs   sums[3] = sum_vs dssim
+ * The loss is (1 - alpha) sums[1] / sums[0] + alpha sums[3] / sums[2], a term whose count is
+ * 0 being 0.
+ * Optional outputs (NULL = not written): warped [B, C, H, W] contiguous; err [B, H, W]
+ * contiguous = (1 - alpha) l1 + alpha dssim where vs holds, l1 where only v holds, -1
+ * elsewhere.  alpha is used for err only.
+ * sums: 4 doubles on the device; workspace: lea_photometric_workspace_bytes(B, H, W) bytes
+ * on the device; both 8-byte aligned.
+ * LEA_E_INVALID, before any launch: a null left, right, disp, sums or workspace; B < 1;
+ * C outside 1..4; H or W < 3; a batch stride below the map size; alpha outside [0, 1]; c1 or
+ * c2 not positive; sums, workspace, warped or err overlapping an input or one another;
+ * sums or workspace misaligned. */
+size_t lea_photometric_workspace_bytes(int B, int H, int W);
+int lea_photometric_f32(const float* left, int64_t left_bstride, const float* right,
+                        int64_t right_bstride, const float* disp, int64_t disp_bstride,
+                        const uint8_t* exclude, int64_t exclude_bstride, int B, int C, int H,
+                        int W, float alpha, float c1, float c2, double* sums, void* workspace,
+                        float* warped, float* err, void* stream);
+
+/* ddisp [B, H, W] = the gradient with respect to disp of
+ * g_l sums[1] / sums[0] + g_s sums[3] / sums[2]; scales = {g_l, g_s} (2 floats) and the
+ * counts sums[0], sums[2] (as lea_photometric_f32 left them) are read on the device; a term
+ * whose count is 0 has gradient 0.  The L1 part uses sign(w_c - L_c) with sign(0) = 0; the
+ * SSIM part uses the unclamped derivative (the clamp only bites where rounding pushed SSIM
+ * past +-1, and the true derivative there is 0), in the gather form: with n1, n2, d1, d2 the
+ * four SSIM factors of window p and S = n1 n2 / (d1 d2),
+ *   dS_p / dw_q = (a_p + b_p w_q + c_p L_q) / 9
+ *   a = 2 mu_x (n2 - n1) / (d1 d2) - 2 S mu_y (1/d1 - 1/d2),  b = -2 S / d2,  c = 2 n1 / (d1 d2)
+ * summed over the <= 9 windows with vs that hold q.  Every pixel is written (0 where v
+ * fails), one launch, no atomics.  ddisp: batch stride >= H*W; it may overlap none of the
+ * inputs, sums or scales.  Argument checks as for lea_photometric_f32. */
+int lea_photometric_grad_f32(const float* left, int64_t left_bstride, const float* right,
+                             int64_t right_bstride, const float* disp, int64_t disp_bstride,
+                             const uint8_t* exclude, int64_t exclude_bstride, int B, int C,
+                             int H, int W, float c1, float c2, const double* sums,
+                             const float* scales, float* ddisp, int64_t ddisp_bstride,
+                             void* stream);
+
 /* ---- bf16 path (BASELINE configs 3 and 4) ----
  * Activations are bf16 in the "c8" layout: NCDHW with channels blocked by 8
  * innermost, x[b][c/8][d][h][w][c%8] (one voxel's 8 channels = one 16-byte word;

@@ -65,6 +65,12 @@ SIGNATURES = {
     "lea_edge_loss_f32": (_i, [_p, _i64, _p, _i64, _p, _i64, _i, _i, _i, ctypes.c_float, _p, _p, _p]),
     "lea_edge_loss_grad_f32": (_i, [_p, _i64, _p, _i64, _p, _i64, _p, _p, _p, _i64, _i, _i, _i,
                                     ctypes.c_float, _p]),
+    # photometric consistency (csrc/photometric.hip)
+    "lea_photometric_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "lea_photometric_f32": (_i, [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _i, _i, _i, _i, ctypes.c_float,
+                                 ctypes.c_float, ctypes.c_float, _p, _p, _p, _p, _p]),
+    "lea_photometric_grad_f32": (_i, [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _i, _i, _i, _i, ctypes.c_float,
+                                      ctypes.c_float, _p, _p, _p, _i64, _p]),
     # bf16 path (c8 layout)
     "lea_conv3d_packed_elems_bf16": (ctypes.c_size_t, [_i, _i, _i]),
     "lea_conv3d_pack_weights_bf16": (_i, [_p, _p, _i, _i, _i, _p]),

@@ -81,5 +81,10 @@ def obtain_predict_args(argv=None):
                         help="left-right check with this threshold in pixels (0 = off): also write the "
                              "right-view disparity, the occlusion mask and the filled disparity "
                              "(not in the reference)")
+    parser.add_argument("--photo_check", action="store_true",
+                        help="photometric consistency of the prediction with its image pair: also write "
+                             "the right image warped to the left view and the per-pixel SSIM + L1 error, "
+                             "and print its mean; with --lr_check the flagged pixels take no part "
+                             "(not in the reference)")
     add_leastereo_args(parser)
     return parser.parse_args(argv)

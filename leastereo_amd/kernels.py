@@ -692,6 +692,88 @@ def edge_loss_grad(pred: torch.Tensor, target: torch.Tensor, tsmooth: torch.Tens
     return dpred
 
 
+# ---- photometric consistency (csrc/photometric.hip) ----
+
+PHOTOMETRIC_FIELDS = ("n_view", "sum_l1", "n_window", "sum_dssim")
+PHOTO_C1, PHOTO_C2 = 0.01 ** 2, 0.03 ** 2
+
+
+def _image_view(t: torch.Tensor):
+    """[B, C, H, W] float32 whose (C, H, W) block is contiguous per batch (a copy if it is
+    not); returns the tensor and its batch stride in elements."""
+    b, c, h, w = t.shape
+    if t.stride()[1:] != (h * w, w, 1) or (b > 1 and t.stride(0) < c * h * w):
+        t = t.contiguous()
+    return t, (t.stride(0) if b > 1 else c * h * w)
+
+
+def _photo_maps(left, right, disp, exclude):
+    _require_cuda(left, right, disp)
+    if left.dim() != 4 or left.shape != right.shape:
+        raise ValueError("left and right must be [B, C, H, W] of one shape")
+    b, c, h, w = left.shape
+    if not 1 <= c <= 4:
+        raise ValueError(f"photometric: 1 <= C <= 4 channels, got {c}")
+    if h < 3 or w < 3:
+        raise ValueError("photometric: H >= 3 and W >= 3 are needed")
+    if tuple(disp.shape) != (b, h, w):
+        raise ValueError(f"disp must be [B, H, W] = {(b, h, w)}, got {tuple(disp.shape)}")
+    ex = (None, 0)
+    if exclude is not None:
+        if not exclude.is_cuda or tuple(exclude.shape) != (b, h, w) or exclude.dtype not in (torch.uint8, torch.bool):
+            raise ValueError("exclude must be a [B, H, W] uint8 or bool tensor on the device")
+        e = exclude.view(torch.uint8) if exclude.dtype == torch.bool else exclude
+        ex = _plane_view(e, "exclude")
+    return _image_view(left), _image_view(right), _plane_view(disp, "disp"), ex
+
+
+def photometric_sums(left: torch.Tensor, right: torch.Tensor, disp: torch.Tensor, exclude: torch.Tensor = None,
+                     alpha: float = 0.85, c1: float = PHOTO_C1, c2: float = PHOTO_C2, want_warped: bool = False,
+                     want_err: bool = False):
+    """The four sums of ``lea_photometric_f32`` (include/leastereo_hip.h), float64 [4] on the
+    device in the order of ``PHOTOMETRIC_FIELDS``; nothing is read back.  With ``want_warped``
+    or ``want_err`` returns ``(sums, warped, err)``, the map not asked for being None."""
+    (l, lbs), (r, rbs), (d, dbs), (e, ebs) = _photo_maps(left, right, disp, exclude)
+    b, c, h, w = l.shape
+    lib = _lib.load()
+    ws = torch.empty(lib.lea_photometric_workspace_bytes(b, h, w) // 8, device=l.device, dtype=torch.float64)
+    sums = torch.empty(4, device=l.device, dtype=torch.float64)
+    warped = torch.empty((b, c, h, w), device=l.device, dtype=torch.float32) if want_warped else None
+    err = torch.empty((b, h, w), device=l.device, dtype=torch.float32) if want_err else None
+    rec = None if _probe is None else _probe_launch("photometric", 0.0, 4.0 * (l.numel() + r.numel() + d.numel()))
+    check(lib.lea_photometric_f32(l.data_ptr(), lbs, r.data_ptr(), rbs, d.data_ptr(), dbs,
+                                  None if e is None else e.data_ptr(), ebs, b, c, h, w, float(alpha), float(c1),
+                                  float(c2), sums.data_ptr(), ws.data_ptr(),
+                                  None if warped is None else warped.data_ptr(),
+                                  None if err is None else err.data_ptr(), _stream()), "lea_photometric_f32")
+    _probe_end(rec)
+    return (sums, warped, err) if (want_warped or want_err) else sums
+
+
+def photometric_grad(left: torch.Tensor, right: torch.Tensor, disp: torch.Tensor, exclude: torch.Tensor = None,
+                     c1: float = PHOTO_C1, c2: float = PHOTO_C2, *, sums: torch.Tensor,
+                     scales: torch.Tensor) -> torch.Tensor:
+    """``lea_photometric_grad_f32``: the gradient with respect to ``disp`` of
+    ``scales[0] * l1 + scales[1] * dssim`` (the two means); ``sums`` is what
+    ``photometric_sums`` returned for the same inputs, ``scales`` two float32 on the device."""
+    (l, lbs), (r, rbs), (d, dbs), (e, ebs) = _photo_maps(left, right, disp, exclude)
+    _require_cuda(scales)
+    if not sums.is_cuda or sums.dtype != torch.float64 or sums.numel() != 4 or not sums.is_contiguous():
+        raise ValueError("sums: the contiguous float64 [4] device tensor of photometric_sums")
+    if scales.numel() != 2 or not scales.is_contiguous():
+        raise ValueError("scales: two contiguous float32 (g_l1, g_dssim) on the device")
+    b, c, h, w = l.shape
+    ddisp = torch.empty((b, h, w), device=l.device, dtype=torch.float32)
+    rec = None if _probe is None else _probe_launch("photometric_grad", 0.0,
+                                                    4.0 * (l.numel() + r.numel() + 2 * d.numel()))
+    check(_lib.load().lea_photometric_grad_f32(l.data_ptr(), lbs, r.data_ptr(), rbs, d.data_ptr(), dbs,
+                                               None if e is None else e.data_ptr(), ebs, b, c, h, w, float(c1),
+                                               float(c2), sums.data_ptr(), scales.data_ptr(), ddisp.data_ptr(),
+                                               h * w, _stream()), "lea_photometric_grad_f32")
+    _probe_end(rec)
+    return ddisp
+
+
 # ------------------------------------------------------------------ bf16 path (c8)
 # Activations: torch.bfloat16 [B, C/8, D, H, W, 8] ("c8": 8 channels per voxel word).
 

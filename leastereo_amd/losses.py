@@ -11,6 +11,10 @@ reference, where it passes through numpy.
 
 With no valid pixel the direct term and its gradient are 0 (torch's mean over an empty
 selection gives NaN; the reference's loop skips such a batch, ``train.py:152``).
+
+``photometric_loss`` is the label-free companion: the right image warped to the left view by
+the predicted disparity against the left image (SSIM + L1), a gradient at every in-view
+pixel of every batch whatever the target holds.
 """
 from __future__ import annotations
 
@@ -91,3 +95,47 @@ def masked_smooth_l1(disp: torch.Tensor, target: torch.Tensor, maxdisp: float) -
     edge term is not wanted, so the target stands in for its smoothed form (no median)."""
     disp, target = _maps(disp, target)
     return _EdgeAwareLoss.apply(disp, target, target, maxdisp, 0.0)[1]
+
+
+class _PhotometricLoss(torch.autograd.Function):
+    """(disp, left, right, exclude, alpha) -> (loss, l1, dssim, n_view, n_window), float32
+    0-d but the two counts (float64)."""
+
+    @staticmethod
+    def forward(ctx, disp, left, right, exclude, alpha):
+        disp = disp.detach()
+        sums = kernels.photometric_sums(left, right, disp, exclude, alpha)
+        n_v, n_w = sums[0], sums[2]
+        l1 = sums[1] / n_v.clamp(min=1.0)        # a sum over no pixel is 0: 0 / 1
+        dssim = sums[3] / n_w.clamp(min=1.0)
+        loss = (1.0 - alpha) * l1 + alpha * dssim
+        ctx.save_for_backward(disp, left, right, sums, *(() if exclude is None else (exclude,)))
+        ctx.alpha = float(alpha)
+        n_v, n_w = n_v.clone(), n_w.clone()
+        ctx.mark_non_differentiable(n_v, n_w)
+        return loss.float(), l1.float(), dssim.float(), n_v, n_w
+
+    @staticmethod
+    def backward(ctx, g_loss, g_l1, g_dssim, _g_nv, _g_nw):
+        disp, left, right, sums, *rest = ctx.saved_tensors
+        scales = torch.stack([g_loss * (1.0 - ctx.alpha) + g_l1, g_loss * ctx.alpha + g_dssim]).float()
+        ddisp = kernels.photometric_grad(left, right, disp, rest[0] if rest else None, sums=sums, scales=scales)
+        return ddisp, None, None, None, None
+
+
+def photometric_loss(left: torch.Tensor, right: torch.Tensor, disp: torch.Tensor, exclude: torch.Tensor = None,
+                     alpha: float = 0.85, return_parts: bool = False):
+    """Photometric consistency of a disparity map with its image pair, the self-supervised
+    signal that needs no target: the right image warped to the left view by ``disp``
+    against the left image, ``(1 - alpha) * L1 + alpha * (1 - SSIM) / 2`` over the pixels in
+    view (``lea_photometric_f32`` in include/leastereo_hip.h has the definition).  Two
+    launches forward, one backward, no host synchronisation; differentiable in ``disp``
+    only.  ``left``, ``right``: [B, C, H, W] with C <= 4; ``disp``: [B, H, W] or
+    [B, 1, H, W]; ``exclude``: optional [B, H, W] uint8 or bool, non-zero pixels take no part
+    (``DisparityLR.state`` as it is).  With ``return_parts`` also ``(l1, dssim, n_view,
+    n_window)``, device scalars.  With no pixel in view the loss and its gradient are 0."""
+    if disp.dim() == 4 and disp.shape[1] == 1:
+        disp = disp.squeeze(1)
+    kernels._require_cuda(left, right, disp)
+    loss, l1, dssim, n_v, n_w = _PhotometricLoss.apply(disp, left.detach(), right.detach(), exclude, float(alpha))
+    return (loss, (l1, dssim, n_v, n_w)) if return_parts else loss

@@ -18,6 +18,11 @@ Restates the host-side steps around ``LEAStereo.forward`` (predict.py:144-243):
   * ``predict_pair_lr`` / ``save_lr``  not in the reference: --lr_check THR adds the
                        left-right check of ``LEAStereo.forward_lr`` ({index}_right.npy,
                        {index}_occ.png, {index}_filled.npy / .png; {name}_occ.png)
+  * ``photometric_check`` / ``save_photo``  not in the reference: --photo_check warps the right
+                       image to the left view with the prediction and scores it against
+                       the left image ({index}_warped.png, {index}_photo.npy / .png, the
+                       pair's mean error printed); with --lr_check the flagged pixels are
+                       excluded
 Arithmetic runs on the HIP kernels; what stays on the host is file I/O (PIL, PFM, PNG).
 
     python predict.py --sceneflow=1 --maxdisp=192 --crop_height=576 --crop_width=960 \
@@ -141,6 +146,45 @@ def save_lr(prefix, right, state, filled, max_disp=192):
     save_float_png(prefix + "_occ.png", occlusion_u8(state))
     np.save(prefix + "_filled.npy", filled.astype(np.float32))
     plot_disparity(prefix + "_filled.png", filled, max_disp)
+
+
+def photometric_check(model, leftname, rightname, crop_height, crop_width, lr_threshold=0.0, device="cuda"):
+    """The label-free quality measure of ``kernels.photometric_sums`` on one pair: (warped
+    [h', w', 3], err [h', w'], loss, l1, dssim), the maps cropped like the disparity.  The
+    images are the standardised network inputs, so the error is in units of their standard
+    deviation.  ``err`` is -1 where a pixel takes no part: warped from outside the right
+    image, in the padding of a pair smaller than the crop, or -- with ``lr_threshold`` > 0
+    -- flagged by the left-right check (``DisparityLR.state`` passed as it is)."""
+    from . import kernels
+    left, right, h, w = load_transform(*load_images(leftname, rightname), crop_height, crop_width,
+                                       device)
+    with torch.no_grad():
+        if lr_threshold > 0:
+            lr = model.forward_lr(left, right, lr_threshold)
+            disp, exclude = lr.disp, lr.state
+        else:
+            disp, exclude = model(left, right), None
+    if h < crop_height or w < crop_width:  # the zero padding is no image
+        pad = torch.ones(disp.shape, device=disp.device, dtype=torch.uint8)
+        pad[:, max(crop_height - h, 0):, max(crop_width - w, 0):] = 0
+        exclude = pad if exclude is None else torch.maximum(exclude, pad)
+    alpha = 0.85
+    sums, warped, err = kernels.photometric_sums(left, right, disp, exclude, alpha, want_warped=True, want_err=True)
+    s = sums.cpu().tolist()
+    l1 = s[1] / s[0] if s[0] else 0.0
+    dssim = s[3] / s[2] if s[2] else 0.0
+    warped = crop_output(warped[0].permute(1, 2, 0).unsqueeze(0).cpu().numpy(), h, w, crop_height, crop_width)
+    err = crop_output(err.cpu().numpy(), h, w, crop_height, crop_width)
+    return warped, err, (1 - alpha) * l1 + alpha * dssim, l1, dssim
+
+
+def save_photo(prefix, warped, err):
+    """<prefix>_warped.png (the warped right image, min-max 8-bit like the satellite branch's
+    float images), <prefix>_photo.npy (float32, -1 where a pixel takes no part) and
+    <prefix>_photo.png (the error clipped to [0, 1])."""
+    save_float_png(prefix + "_warped.png", warped)
+    np.save(prefix + "_photo.npy", err.astype(np.float32))
+    save_float_png(prefix + "_photo.png", np.clip(err, 0.0, 1.0))
 
 
 def plot_disparity(savename, data, max_disp=192):
@@ -286,6 +330,12 @@ def main(argv=None):
         if opt.confidence != "none":
             disp, conf, local = disp
             save_confidence(os.path.join(opt.save_path, f"{index}"), conf, local)
+        if opt.photo_check:
+            warped, err, loss, l1, dssim = photometric_check(model, leftname, rightname, opt.crop_height,
+                                                             opt.crop_width, opt.lr_check)
+            save_photo(os.path.join(opt.save_path, f"{index}"), warped, err)
+            print(f"{index}: mean photometric error {loss:.4f} (L1 {l1:.4f}, (1 - SSIM) / 2 {dssim:.4f}) over "
+                  f"{100.0 * float((err >= 0).mean()):.2f} % of the pixels")
         plot_disparity(opt.save_path + f"{index:d}.png", disp, 192)  # predict.py:240
         np.save(os.path.join(opt.save_path, f"{index}.npy"), disp.astype(np.float32))
         if gt is not None:

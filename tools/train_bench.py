@@ -7,6 +7,8 @@ forward + backward alone at the hot layer shapes.  One JSON line per measurement
 
     python tools/train_bench.py [--height 288 --width 576 --maxdisp 96] [--steps 5]
     python tools/train_bench.py --edge_loss_w 0.2 ...   the reference's combined_loss (train.py:107-113)
+    python tools/train_bench.py --whole 1 --photo_loss_w 0.1   adds W x losses.photometric_loss to the whole-model step
+                                                        (--whole 2: with and without it in one process)
     python tools/train_bench.py --whole 1 --device_transform 1 [--src_height 540 --src_width 960]
                                                         the loader's transform inside the timed step
 """
@@ -120,6 +122,9 @@ def main():
     ap.add_argument("--edge_loss_w", type=float, default=0.0,
                     help="> 0: the step's loss is the reference's combined_loss with this weight "
                          "(leastereo_amd.losses on the hip impl, torch ops on the torch impl); 0: off")
+    ap.add_argument("--photo_loss_w", type=float, default=0.0,
+                    help="> 0 (with --whole 1 or 2): adds this weight times losses.photometric_loss(left, right, disp) "
+                         "to the step's loss, next to --edge_loss_w; 0: off")
     ap.add_argument("--device_transform", type=int, default=0,
                     help="1 (with --whole 1): the step starts from decoded uint8 pairs of --src_height x "
                          "--src_width and their disparity, standardised, random-cropped to --height x --width "
@@ -188,7 +193,7 @@ def whole_model(args, dev):
         disp_u8 = torch.rand(src, device=dev, generator=gen) * (args.maxdisp - 1)
         tf = DeviceTrainTransform(args.height, args.width, args.maxdisp, device=dev)
 
-    def step(edge_loss_w=args.edge_loss_w):
+    def step(edge_loss_w=args.edge_loss_w, photo_loss_w=args.photo_loss_w):
         nonlocal left, right, target
         opt.zero_grad()
         if tf is not None:
@@ -197,26 +202,33 @@ def whole_model(args, dev):
             target = batch.target.squeeze(1)
         disp = model(left, right)
         if edge_loss_w:
-            losses.combined_loss(disp, target, args.maxdisp, edge_loss_w).backward()
+            loss = losses.combined_loss(disp, target, args.maxdisp, edge_loss_w)
         else:
             mask = (target < args.maxdisp) & (target > 0.001)
-            F.smooth_l1_loss(disp[mask], target[mask], reduction="mean").backward()
+            loss = F.smooth_l1_loss(disp[mask], target[mask], reduction="mean")
+        if photo_loss_w:
+            loss = loss + photo_loss_w * losses.photometric_loss(left, right, disp)
+        loss.backward()
         opt.step()
     torch.cuda.reset_peak_memory_stats()
     if args.whole == 2:
         # processes differ by more than the loss costs: both steps in this one, in alternating
         # windows of --steps steps, the order reversed every other round; medians of the windows
-        ws = (0.0, args.edge_loss_w or 0.2)
+        # (with --photo_loss_w: the step with and without the photometric term instead)
+        photo = bool(args.photo_loss_w)
+        ws = (0.0, args.photo_loss_w) if photo else (0.0, args.edge_loss_w or 0.2)
+        run = (lambda w: step(args.edge_loss_w, w)) if photo else (lambda w: step(w, 0.0))
         t = {w: [] for w in ws}
         for w in ws:
-            timed(lambda: step(w), 1, args.warmup)
+            timed(lambda: run(w), 1, args.warmup)
         for r in range(7):
             for w in (ws if r % 2 == 0 else ws[::-1]):
-                t[w].append(timed(lambda: step(w), args.steps, 0))
+                t[w].append(timed(lambda: run(w), args.steps, 0))
         for w in ws:
             v = sorted(t[w])
             print(json.dumps({"what": "whole_model_train_step_ab", "impl": "hip", "height": args.height,
-                              "width": args.width, "maxdisp": args.maxdisp, "edge_loss_w": w,
+                              "width": args.width, "maxdisp": args.maxdisp,
+                              "edge_loss_w": args.edge_loss_w if photo else w, **({"photo_loss_w": w} if photo else {}),
                               "ms_median": round(v[len(v) // 2], 2), "ms_min": round(v[0], 2),
                               "ms_max": round(v[-1], 2), "windows": len(v), "steps_per_window": args.steps}),
                   flush=True)
@@ -225,7 +237,9 @@ def whole_model(args, dev):
     line = {"what": "whole_model_train_step", "impl": "hip", "height": args.height, "width": args.width,
             "maxdisp": args.maxdisp, "edge_loss_w": args.edge_loss_w, "ms": round(ms, 2),
             "peak_gb": round(torch.cuda.max_memory_allocated() / 2 ** 30, 1)}
-    if tf is not None:  # the default line keeps its keys
+    if args.photo_loss_w:  # the default line keeps its keys
+        line["photo_loss_w"] = args.photo_loss_w
+    if tf is not None:
         line.update({"device_transform": 1, "src_height": args.src_height, "src_width": args.src_width})
     print(json.dumps(line), flush=True)
 
