@@ -85,13 +85,24 @@ build/asan/photo_asan_main.o: tests/asan/photo_asan.cpp include/leastereo_hip.h
 build/asan/photo_asan: build/asan/photo_asan_main.o $(ASANOBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -fno-gpu-sanitize -fsanitize=address -o $@ $^
 
-asan: build/asan/capi_asan build/asan/disp_stats_asan build/asan/lr_asan build/asan/loss_asan build/asan/transform_asan build/asan/photo_asan
+# whole-scene inference's three entries (lea_standardize_tiles_workspace_bytes, lea_standardize_tiles_u8,
+# lea_tile_blend_f32)
+build/asan/scene_asan_main.o: tests/asan/scene_asan.cpp include/leastereo_hip.h
+	@mkdir -p build/asan
+	$(HIPCC) $(ASANFLAGS) -c $< -o $@
+
+build/asan/scene_asan: build/asan/scene_asan_main.o $(ASANOBJ)
+	$(HIPCC) --offload-arch=$(ARCH) -fno-gpu-sanitize -fsanitize=address -o $@ $^
+
+asan: build/asan/capi_asan build/asan/disp_stats_asan build/asan/lr_asan build/asan/loss_asan build/asan/transform_asan build/asan/photo_asan \
+      build/asan/scene_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/capi_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/disp_stats_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/lr_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/loss_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/transform_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/photo_asan
+	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/scene_asan
 
 clean:
 	rm -rf build $(LIB)

@@ -568,6 +568,49 @@ int lea_train_transform_u8(const void* left, const void* right, int B, int H, in
                            float* out_left, float* out_right, float* out_target, int crop_h,
                            int crop_w, float maxdisp, int* n_valid, void* workspace, void* stream);
 
+/* ---- whole-scene inference: overlapping tiles gathered and blended (not in the reference) ---- */
+
+/* The gather: one pair of decoded scenes cut into N tiles, each standardised as
+ * lea_standardize_crop_u8 standardises (the same exact sums, the same float64 -> float32
+ * store) with the statistics of the WHOLE scene, as the reference standardises before it
+ * crops.
+ *   left/right: uint8 HWC scenes [H, W, pix_stride] (3 or 4)
+ *   origins: device int32 [N][2] = {y, x}; tile k's pixel (y, x) reads scene pixel
+ *     (y + origins[k][0], x + origins[k][1]) and is 0 where that lies outside the scene.
+ *     The rows are not validated: coordinates are formed in 64 bits and bounds-tested
+ *     before every read, so any N pairs of ints are memory-safe (a tile wholly outside the
+ *     scene is all 0).
+ *   out_left/out_right: [N, 3, tile_h, tile_w] float32 (16-byte aligned when tile_w % 4 == 0)
+ *   workspace: lea_standardize_tiles_workspace_bytes() bytes, cleared by the call.
+ * A clearing launch, the statistics launch and the tile launch (kernels only: a captured
+ * call holds no memset node); all on `stream`, no host sync.  N in 1..65535.            */
+size_t lea_standardize_tiles_workspace_bytes(void);
+int lea_standardize_tiles_u8(const void* left, const void* right, int H, int W, int pix_stride,
+                             const int* origins, int N, float* out_left, float* out_right, int tile_h,
+                             int tile_w, void* workspace, void* stream);
+
+/* The blend: the ny * nx per-tile maps of a separable plan (tile k = ky * nx + kx at origin
+ * (ys[ky], xs[kx]), both in device memory, ny, nx <= 64) gathered into out [H, W].
+ * Per axis (scene length S, tile length L, origin o, low / high guard g0 / g1) tile
+ * coordinate i weighs
+ *   lo = o > 0, hi = o + L < S, a = lo ? g0 : 0, b = hi ? g1 : 0
+ *   w = 0 for i < a or i >= L - b, else min(lo ? i - a + 1 : ramp, hi ? (L - b) - i : ramp, ramp)
+ * and a pixel's weight in a tile is the integer product wy * wx.  Over the tiles of positive
+ * weight in ascending k: one tile -> its value copied; several -> (sum w * v) / (sum w) in
+ * float32, each product, add and the divide rounded once; none -> 0.  A tile is never read
+ * where its weight is 0.  The origins are not validated (any ints are memory-safe).
+ *   tiles: [ny * nx, tile_h, tile_w] float32, tile_bstride elements from tile to tile
+ *   guard_*: >= 0 (left-view maps: x guards (maxdisp + context, context); the right view's
+ *     disparity: (context, maxdisp + context)); ramp: 1..256
+ *   out: [H, W] float32 (16-byte aligned when W % 4 == 0), not aliasing tiles
+ *   n_uncovered: optional device int32, cleared by the call (a launch): the number of
+ *     pixels no tile covers.
+ * One launch (two with n_uncovered) on `stream`, no host sync, no float atomics:
+ * bit-reproducible.                                                                    */
+int lea_tile_blend_f32(const float* tiles, int64_t tile_bstride, const int* ys, int ny, const int* xs,
+                       int nx, int tile_h, int tile_w, int guard_y0, int guard_y1, int guard_x0,
+                       int guard_x1, int ramp, float* out, int H, int W, int* n_uncovered, void* stream);
+
 /* Disparity metrics of one batch, per pair b (device out[b][8], float64):
  *   [0] n    of evaluation.py:287 mask (gt >= 0.001 & gt <= maxdisp)
  *   [1] sum |pred - gt| over that mask          (EPE = [1] / [0], evaluation.py:288)

@@ -141,6 +141,10 @@ SIGNATURES = {
     "lea_train_transform_workspace_bytes": (ctypes.c_size_t, [_i]),
     "lea_train_transform_u8": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _i, _i,
                                     ctypes.c_float, _p, _p, _p]),
+    # whole-scene inference: the tile gather (csrc/evalio.hip) and blend (csrc/tile_blend.hip)
+    "lea_standardize_tiles_workspace_bytes": (ctypes.c_size_t, []),
+    "lea_standardize_tiles_u8": (_i, [_p, _p, _i, _i, _i, _p, _i, _p, _p, _i, _i, _p, _p]),
+    "lea_tile_blend_f32": (_i, [_p, _i64, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _i, _i, _p, _p]),
     "lea_disparity_metrics_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
     "lea_disparity_metrics": (_i, [_p, _i64, _p, _i64, _i, _i, _i, ctypes.c_float, _i, _i,
                                    _i, _i, _i, _p, _p, _p, _p]),

@@ -86,5 +86,14 @@ def obtain_predict_args(argv=None):
                              "the right image warped to the left view and the per-pixel SSIM + L1 error, "
                              "and print its mean; with --lr_check the flagged pixels take no part "
                              "(not in the reference)")
+    parser.add_argument("--scene", type=int, default=0,
+                        help="1: whole-scene inference -- --crop_height/--crop_width name the tile, an image "
+                             "larger than it is cut into overlapping tiles, gathered and blended on the "
+                             "device, and every output has the image's size (not in the reference)")
+    parser.add_argument("--scene_batch", type=int, default=1, help="tiles per forward under --scene")
+    parser.add_argument("--scene_context", type=int, default=16,
+                        help="pixels of context dropped on every cut side of a tile under --scene")
+    parser.add_argument("--scene_ramp", type=int, default=32,
+                        help="width of the blend ramp between tiles under --scene (1..256)")
     add_leastereo_args(parser)
     return parser.parse_args(argv)

@@ -19,6 +19,9 @@
 //    launch, then one crop launch whose window, shift and swap come from a per-sample
 //    params row in device memory, and which also cuts the disparity target and counts its
 //    valid pixels (integer atomics: order-free).
+//  * lea_standardize_tiles_u8: whole-scene inference's gather (not in the reference): the same
+//    statistics launch over one pair of scenes, then one launch that cuts N overlapping tiles
+//    at origins read from device memory, each standardised with the scene's statistics.
 // The first two are HBM-bound streaming passes; the third's statistics launch is latency-bound at
 // training sizes (bytes and measurements in DESIGN.md §4).
 #include <cmath>
@@ -265,6 +268,59 @@ __global__ __launch_bounds__(kTrainThreads) void u8_train_transform_kernel(
   }
 }
 
+// ---------------------------------------------------------------- scene tiles
+// Whole-scene inference's gather: grid (G, N, 2), blockIdx.y = tile,
+// blockIdx.z = view (0 left, 1 right).  Tile k's pixel (y, x) is the standardised scene pixel
+// (y + origins[k][0], x + origins[k][1]) -- the whole scene's statistics, not the tile's --
+// and 0 outside the scene.  origins is read from device memory and trusted for nothing: the
+// coordinates are formed in 64 bits and tested against [0,H) x [0,W) before every read.
+__global__ __launch_bounds__(256) void u8_standardize_tiles_kernel(
+    const uint8_t* __restrict__ left, const uint8_t* __restrict__ right, int H, int W, int pix_stride,
+    const unsigned long long* __restrict__ sums, const int* __restrict__ origins,
+    float* __restrict__ out_l, float* __restrict__ out_r, int th, int tw) {
+  const int img = blockIdx.z;
+  const int k = blockIdx.y;
+  __shared__ float lut[3][256];
+  for (int e = threadIdx.x; e < 3 * 256; e += blockDim.x) {
+    const int c = e / 256;
+    lut[c][e % 256] = standardized(sums[((long long)img * 3 + c) * 2],
+                                   sums[((long long)img * 3 + c) * 2 + 1], (long long)H * W, e % 256);
+  }
+  __syncthreads();
+  const long long oy = origins[2 * k], ox = origins[2 * k + 1];
+  const uint8_t* src = img ? right : left;
+  const long long plane = (long long)th * tw;
+  float* dst = (img ? out_r : out_l) + (long long)k * 3 * plane;
+  const int qw = (tw + 3) / 4;  // float4 columns per tile row
+  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < th * qw; t += gridDim.x * blockDim.x) {
+    const int y = t / qw, x0 = (t - y * qw) * 4;
+    const long long sy = y + oy;
+    const bool row_in = sy >= 0 && sy < H;
+    float v[3][4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const long long sx = x0 + j + ox;
+      const bool in = row_in && sx >= 0 && sx < W;
+      const long long pix = in ? sy * W + sx : 0;  // < H * W < 2^31
+      const uint8_t* q = src + pix * pix_stride;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) v[c][j] = in ? lut[c][q[c]] : 0.f;
+    }
+    const long long o = (long long)y * tw + x0;
+    if ((tw & 3) == 0) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        *reinterpret_cast<float4*>(dst + c * plane + o) = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (x0 + j < tw)
+#pragma unroll
+          for (int c = 0; c < 3; ++c) dst[c * plane + o + j] = v[c][j];
+    }
+  }
+}
+
 // ---------------------------------------------------------------- metrics
 constexpr int kMetThreads = 256;
 constexpr int kMetFields = 8;
@@ -479,6 +535,52 @@ extern "C" int lea_train_transform_u8(const void* left, const void* right, int B
       (const unsigned long long*)workspace, out_left, out_right, out_target, crop_h, crop_w, maxdisp,
       n_valid);
   return launch_status("lea_train_transform_u8");
+}
+
+extern "C" size_t lea_standardize_tiles_workspace_bytes() {
+  return lea_standardize_workspace_bytes(1);  // one pair of scenes: the same exact integer sums
+}
+
+extern "C" int lea_standardize_tiles_u8(const void* left, const void* right, int H, int W, int pix_stride,
+                                        const int* origins, int N, float* out_left, float* out_right,
+                                        int tile_h, int tile_w, void* workspace, void* stream) {
+  using namespace lea;
+  clear_error();
+  LEA_CHECK_ARG(left && right && origins && out_left && out_right && workspace,
+                "lea_standardize_tiles_u8: null pointer");
+  LEA_CHECK_ARG(H > 0 && W > 0 && tile_h > 0 && tile_w > 0,
+                "lea_standardize_tiles_u8: bad shape H=%d W=%d tile %dx%d", H, W, tile_h, tile_w);
+  LEA_CHECK_ARG(N > 0 && N <= 65535, "lea_standardize_tiles_u8: %d tiles (1..65535)", N);
+  LEA_CHECK_ARG(pix_stride >= 3 && pix_stride <= 4,
+                "lea_standardize_tiles_u8: pixel stride %d (RGB = 3, RGBA = 4)", pix_stride);
+  LEA_CHECK_ARG((long long)H * W < (1LL << 31) && (long long)tile_h * tile_w < (1LL << 31),
+                "lea_standardize_tiles_u8: image too large");
+  // the tile kernel stores float4 when tile_w % 4 == 0
+  LEA_CHECK_ARG((tile_w & 3) != 0 || ((((uintptr_t)out_left) | ((uintptr_t)out_right)) & 15) == 0,
+                "lea_standardize_tiles_u8: outputs must be 16-byte aligned when tile_w %% 4 == 0");
+  LEA_CHECK_ARG((((uintptr_t)origins) & 3) == 0 && (((uintptr_t)workspace) & 7) == 0,
+                "lea_standardize_tiles_u8: misaligned origins or workspace");
+  hipStream_t st = as_stream(stream);
+  const long long npix = (long long)H * W;
+  const int nsums = 2 * 3 * 2;
+  train_clear_kernel<<<1, 256, 0, st>>>((unsigned long long*)workspace, nsums, nullptr, 0);
+  int rc = launch_status("lea_standardize_tiles_u8 (clear)");
+  if (rc) return rc;
+  // the statistics launch of lea_standardize_crop_u8, as it is, over the whole scene
+  long long g = (npix + kStatThreads * 16 - 1) / (kStatThreads * 16);
+  g = g > 1024 ? 1024 : g;
+  const long long gmin = (npix + ((long long)kStatThreads << 23) - 1) / ((long long)kStatThreads << 23);
+  g = g < gmin ? gmin : g;
+  u8_stats_kernel<<<dim3((unsigned)g, 2), kStatThreads, 0, st>>>(
+      (const uint8_t*)left, (const uint8_t*)right, 1, npix, pix_stride, (unsigned long long*)workspace);
+  rc = launch_status("lea_standardize_tiles_u8 (stats)");
+  if (rc) return rc;
+  const long long quads = (long long)tile_h * ((tile_w + 3) / 4);
+  const int gx = (int)((quads + 256 * 2 - 1) / (256 * 2));
+  u8_standardize_tiles_kernel<<<dim3(gx, N, 2), 256, 0, st>>>(
+      (const uint8_t*)left, (const uint8_t*)right, H, W, pix_stride, (const unsigned long long*)workspace,
+      origins, out_left, out_right, tile_h, tile_w);
+  return launch_status("lea_standardize_tiles_u8");
 }
 
 extern "C" size_t lea_disparity_metrics_workspace_bytes(int B, int H, int W) {

@@ -1211,6 +1211,77 @@ def train_transform_u8(left: torch.Tensor, right: torch.Tensor, disp_left: torch
     return out_l, out_r, out_t, n_valid
 
 
+# ---- whole-scene inference: tile gather and blend (csrc/evalio.hip, csrc/tile_blend.hip) ----
+
+def standardize_tiles_u8(left: torch.Tensor, right: torch.Tensor, origins: torch.Tensor, tile_height: int,
+                         tile_width: int):
+    """``lea_standardize_tiles_u8`` (include/leastereo_hip.h): one pair of uint8 scenes
+    [H, W, 3|4] (or [1, H, W, 3|4]) cut into the N tiles whose (y, x) origins the int32 device
+    tensor ``origins`` [N, 2] holds, standardised with the whole scene's statistics, 0 outside
+    the scene.  Returns (left, right) float32 [N, 3, tile_height, tile_width].  Nothing is
+    copied to the host and nothing synchronises; any origins are memory-safe."""
+    for t in (left, right):
+        if not t.is_cuda or t.dtype != torch.uint8:
+            raise _lib.HipKernelError(f"standardize_tiles_u8 needs uint8 device images, got "
+                                      f"{t.dtype} on {t.device}")
+    if not origins.is_cuda or origins.dtype != torch.int32:
+        raise _lib.HipKernelError(f"standardize_tiles_u8 needs int32 device origins, got "
+                                  f"{origins.dtype} on {origins.device}")
+    if left.dim() == 4 and left.shape[0] == 1:
+        left, right = left[0], right[0]
+    if left.shape != right.shape or left.dim() != 3 or left.shape[-1] not in (3, 4):
+        raise ValueError(f"left/right must both be [H, W, 3|4] uint8, got {tuple(left.shape)} "
+                         f"and {tuple(right.shape)}")
+    if origins.dim() != 2 or origins.shape[1] != 2 or origins.shape[0] < 1:
+        raise ValueError(f"origins must be [N, 2] with N >= 1, got {tuple(origins.shape)}")
+    left, right, origins = left.contiguous(), right.contiguous(), origins.contiguous()
+    h, w, ps = left.shape
+    n = origins.shape[0]
+    lib = _lib.load()
+    ws = torch.empty(lib.lea_standardize_tiles_workspace_bytes(), device=left.device, dtype=torch.uint8)
+    out_l = torch.empty((n, 3, tile_height, tile_width), device=left.device, dtype=torch.float32)
+    out_r = torch.empty_like(out_l)
+    check(lib.lea_standardize_tiles_u8(left.data_ptr(), right.data_ptr(), h, w, ps, origins.data_ptr(), n,
+                                       out_l.data_ptr(), out_r.data_ptr(), tile_height, tile_width,
+                                       ws.data_ptr(), _stream()), "lea_standardize_tiles_u8")
+    return out_l, out_r
+
+
+def blend_tiles(tiles: torch.Tensor, plan, view: str = "left", check: bool = False,
+                count: torch.Tensor = None) -> torch.Tensor:
+    """``lea_tile_blend_f32`` (include/leastereo_hip.h): the per-tile maps ``tiles``
+    [N, tile_h, tile_w] float32 of ``plan`` (a ``scene.TilePlan``; N = ny * nx, any batch
+    stride) blended into one [H, W] map with the plan's weights.  ``view`` "left" for the
+    left view's maps (disparity, entropy, peak, local disparity), "right" for the right view's
+    disparity, whose truncated columns are on the tile's right.  ``count``: an int32 device
+    tensor of one element that receives the number of pixels no tile covers.  ``check=True``
+    reads that count back (a synchronisation) and raises if it is not 0; the default neither
+    counts nor synchronises."""
+    _require_cuda(tiles)
+    n, th, tw = plan.ny * plan.nx, plan.tile_h, plan.tile_w
+    if tiles.dim() != 3 or tuple(tiles.shape) != (n, th, tw):
+        raise ValueError(f"tiles must be [N, tile_h, tile_w] = {(n, th, tw)}, got {tuple(tiles.shape)}")
+    if tiles.stride()[1:] != (tw, 1) or (n > 1 and tiles.stride(0) < th * tw):
+        tiles = tiles.contiguous()
+    (gy0, gy1), (gx0, gx1) = plan.guards(view)
+    ys, xs = plan.device_axes(tiles.device)
+    if check and count is None:
+        count = torch.empty(1, device=tiles.device, dtype=torch.int32)
+    if count is not None and (not count.is_cuda or count.dtype != torch.int32 or count.numel() != 1):
+        raise ValueError("count must be one int32 element on the device")
+    out = torch.empty((plan.height, plan.width), device=tiles.device, dtype=torch.float32)
+    _lib.check(_lib.load().lea_tile_blend_f32(
+        tiles.data_ptr(), tiles.stride(0) if n > 1 else th * tw, ys.data_ptr(), plan.ny, xs.data_ptr(), plan.nx,
+        th, tw, gy0, gy1, gx0, gx1, plan.ramp, out.data_ptr(), plan.height, plan.width,
+        None if count is None else count.data_ptr(), _stream()), "lea_tile_blend_f32")
+    if check:
+        holes = int(count.item())
+        if holes:
+            raise _lib.HipKernelError(f"blend_tiles: {holes} of {plan.height * plan.width} pixels have no "
+                                      f"covering tile (view {view!r})")
+    return out
+
+
 METRIC_FIELDS = ("n_epe", "sum_abs", "n_valid", "n_correct3", "n_le_thr1", "n_le_thr2", "n_le_thr3")
 
 

@@ -305,6 +305,19 @@ class LEAStereo(nn.Module):
         disp = self.disp(cost, fast_exp=fast)
         return kernels.lr_check(disp, self.disp.right(cost, fast_exp=fast), threshold)
 
+    def forward_scene(self, left_u8, right_u8, tile, **kw):
+        """A uint8 scene pair [H, W, 3|4] of any size through overlapping ``tile`` = (h, w)
+        forwards, gathered and blended on the device: ``scene.SceneResult`` at the scene's
+        size.  ``kw`` as ``scene.SceneRunner`` (tile_batch, context, ramp, confidence, radius,
+        lr_threshold, graph); the runners (their captured graphs and tile plans) are kept per
+        setting.  Inference only."""
+        from .scene import SceneRunner
+        key = (int(tile[0]), int(tile[1]), tuple(sorted(kw.items())))
+        runners = self.__dict__.setdefault("_scene_runners", {})
+        if key not in runners:
+            runners[key] = SceneRunner(self, key[0], key[1], **kw)
+        return runners[key](left_u8, right_u8)
+
     def set_precision(self, precision: str):
         """Switch the arithmetic ("f32" / "bf16" / "f32_direct"); weights are re-packed
         on the next forward."""

@@ -23,6 +23,10 @@ Restates the host-side steps around ``LEAStereo.forward`` (predict.py:144-243):
                        the left image ({index}_warped.png, {index}_photo.npy / .png, the
                        pair's mean error printed); with --lr_check the flagged pixels are
                        excluded
+  * ``predict_scene``  not in the reference: --scene 1 makes --crop_height/--crop_width the
+                       tile of ``scene.SceneRunner``; an image larger than it is cut into
+                       overlapping tiles, gathered and blended on the device, and every output
+                       above has the image's size under its usual name
 Arithmetic runs on the HIP kernels; what stays on the host is file I/O (PIL, PFM, PNG).
 
     python predict.py --sceneflow=1 --maxdisp=192 --crop_height=576 --crop_width=960 \
@@ -131,6 +135,26 @@ def predict_pair_lr(model, leftname, rightname, crop_height, crop_width, thresho
     with torch.no_grad():
         lr = model.forward_lr(left, right, threshold)
     return tuple(crop_output(t.cpu().numpy(), h, w, crop_height, crop_width) for t in lr)
+
+
+def predict_scene(runner, leftname, rightname, confidence="none"):
+    """One pair through ``scene.SceneRunner`` (--scene): (disp, lr) at the image's size, shaped
+    as ``predict_pair`` and ``predict_pair_lr`` shape them -- disp the disparity, or (disparity,
+    conf, local) under ``confidence``; lr (disparity, right-view disparity, state, filled) when
+    the runner has an ``lr_threshold``, else None."""
+    import math
+    res = runner(*load_images(leftname, rightname))
+    disp = res.disp.cpu().numpy()
+    lr = None
+    if res.disp_right is not None:
+        lr = (disp,) + tuple(t.cpu().numpy() for t in (res.disp_right, res.state, res.disp_filled))
+    if confidence in (None, "none"):
+        return disp, lr
+    if confidence not in ("entropy", "peak"):
+        raise ValueError(f"confidence {confidence!r}: one of none, entropy, peak")
+    if confidence == "entropy":  # DisparityStats.confidence on the blended entropy
+        return (disp, (1.0 - res.entropy / math.log(runner.model.maxdisp)).cpu().numpy(), None), lr
+    return (disp, res.peak.cpu().numpy(), res.disp_local.cpu().numpy()), lr
 
 
 def occlusion_u8(state):
@@ -244,11 +268,22 @@ def satellite_names(data_path, save_path, line):
 
 
 def test_satellite(model, leftname, rightname, savename, in_savename, crop_height, crop_width,
-                   confidence="none", radius=4, lr_threshold=0.0):
+                   confidence="none", radius=4, lr_threshold=0.0, runner=None):
     """predict.py:187-211: the disparity as a PNG (min-max 8-bit, as skimage writes a
     float image) and the left input cropped / padded to the crop.  With ``confidence``
-    also <name>_conf.png beside <name>.png, with ``lr_threshold`` > 0 <name>_occ.png."""
+    also <name>_conf.png beside <name>.png, with ``lr_threshold`` > 0 <name>_occ.png.
+    With ``runner`` (--scene) the same files at the image's own size."""
     from PIL import Image
+    if runner is not None:
+        disp, lr = predict_scene(runner, leftname, rightname, confidence)
+        if lr is not None:
+            save_float_png(os.path.splitext(savename)[0] + "_occ.png", occlusion_u8(lr[2]))
+        if confidence not in (None, "none"):
+            disp, conf, _ = disp
+            save_float_png(os.path.splitext(savename)[0] + "_conf.png", np.clip(conf, 0.0, 1.0))
+        save_float_png(savename, disp)
+        save_float_png(in_savename, crop_image(Image.open(leftname), *disp.shape))
+        return disp
     if lr_threshold > 0:
         state = predict_pair_lr(model, leftname, rightname, crop_height, crop_width, lr_threshold)[2]
         save_float_png(os.path.splitext(savename)[0] + "_occ.png", occlusion_u8(state))
@@ -295,6 +330,16 @@ def main(argv=None):
             raise FileNotFoundError(opt.resume)
         load_checkpoint(model, opt.resume)
     model = model.cuda().eval()
+    runner = None
+    if opt.scene:
+        if opt.photo_check:
+            raise NotImplementedError("--photo_check with --scene is not supported: the photometric check "
+                                      "scores one forward's crop; run it without --scene")
+        from .scene import SceneRunner
+        runner = SceneRunner(model, opt.crop_height, opt.crop_width, tile_batch=opt.scene_batch,
+                             context=opt.scene_context, ramp=opt.scene_ramp,
+                             confidence=opt.confidence != "none", radius=opt.conf_radius,
+                             lr_threshold=opt.lr_check if opt.lr_check > 0 else None)
     os.makedirs(opt.save_path, exist_ok=True)
     with open(opt.test_list) as f:
         lines = f.readlines()
@@ -304,7 +349,8 @@ def main(argv=None):
     for index, line in enumerate(lines):
         if opt.satellite:  # predict.py:258-264
             test_satellite(model, *satellite_names(opt.data_path, opt.save_path, line),
-                           opt.crop_height, opt.crop_width, opt.confidence, opt.conf_radius, opt.lr_check)
+                           opt.crop_height, opt.crop_width, opt.confidence, opt.conf_radius, opt.lr_check,
+                           runner)
         if not opt.sceneflow:
             continue
         print(f"Running for sceneflow {index}")
@@ -315,9 +361,11 @@ def main(argv=None):
             plot_disparity(opt.save_path + f"{index:d}_gt.png", gt, 192)
         t0 = time.time()
         lr = None
-        if opt.lr_check > 0:
+        if runner is None and opt.lr_check > 0:
             lr = predict_pair_lr(model, leftname, rightname, opt.crop_height, opt.crop_width, opt.lr_check)
-        if lr is None or opt.confidence != "none":  # with --confidence: its own call on the pair
+        if runner is not None:  # --scene: every map of the pair from one call
+            disp, lr = predict_scene(runner, leftname, rightname, opt.confidence)
+        elif lr is None or opt.confidence != "none":  # with --confidence: its own call on the pair
             disp = predict_pair(model, leftname, rightname, opt.crop_height, opt.crop_width,
                                 confidence=opt.confidence, radius=opt.conf_radius)
         else:
