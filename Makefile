@@ -94,8 +94,16 @@ build/asan/scene_asan_main.o: tests/asan/scene_asan.cpp include/leastereo_hip.h
 build/asan/scene_asan: build/asan/scene_asan_main.o $(ASANOBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -fno-gpu-sanitize -fsanitize=address -o $@ $^
 
+# the disparity refinement's two entries (lea_disparity_refine_workspace_bytes, lea_disparity_refine_f32)
+build/asan/refine_asan_main.o: tests/asan/refine_asan.cpp include/leastereo_hip.h
+	@mkdir -p build/asan
+	$(HIPCC) $(ASANFLAGS) -c $< -o $@
+
+build/asan/refine_asan: build/asan/refine_asan_main.o $(ASANOBJ)
+	$(HIPCC) --offload-arch=$(ARCH) -fno-gpu-sanitize -fsanitize=address -o $@ $^
+
 asan: build/asan/capi_asan build/asan/disp_stats_asan build/asan/lr_asan build/asan/loss_asan build/asan/transform_asan build/asan/photo_asan \
-      build/asan/scene_asan
+      build/asan/scene_asan build/asan/refine_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/capi_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/disp_stats_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/lr_asan
@@ -103,6 +111,7 @@ asan: build/asan/capi_asan build/asan/disp_stats_asan build/asan/lr_asan build/a
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/transform_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/photo_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/scene_asan
+	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/refine_asan
 
 clean:
 	rm -rf build $(LIB)

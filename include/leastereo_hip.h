@@ -389,6 +389,54 @@ int lea_photometric_grad_f32(const float* left, int64_t left_bstride, const floa
                              const float* scales, float* ddisp, int64_t ddisp_bstride,
                              void* stream);
 
+/* Confidence-weighted edge-preserving disparity refinement (additive: the ABI number stays
+ * 14): the weighted-least-squares smoothing of OpenCV's ximgproc disparity WLS filter, solved
+ * with the fast global smoother (Min et al., "Fast global image smoothing based on weighted
+ * least squares", 2014).  Confident pixels keep their disparity; excluded, non-finite and
+ * zero-confidence ones are filled from confident neighbours on the same side of an edge of
+ * the guide image.  Neither entry synchronises the host, allocates or reads anything back.
+ *
+ * Inputs.  guide: [B, C, H, W] f32, 1 <= C <= 4, the (C, H, W) block contiguous, batch
+ * stride guide_bstride >= C*H*W in elements.  disp: [B, H, W] f32.  conf: [B, H, W] f32 or
+ * NULL (= 1 everywhere).  exclude: [B, H, W] bytes or NULL; non-zero = no evidence (the
+ * state of lea_disparity_lr_check can be passed as it is).  Any H, W >= 1.
+ * lambda > 0, sigma > 0, 1 <= iterations (T) <= 8 (the result is unspecified for a lambda
+ * above 1e30, where lambda_t w overflows the reciprocal).
+ *
+ * Evidence.  c0 = conf, but 0 where exclude != 0, disp is not finite, or conf is not finite
+ * or <= 0; f0 = disp where c0 > 0, else 0 (a NaN under a zero weight never enters the
+ * arithmetic).  num = c0 * f0, den = c0.
+ * Edge weights, once per call, with the accurate expf:
+ *   wh[y, x] = exp(-(max_c |G[c, y, x+1] - G[c, y, x]|) / sigma)   for x < W - 1
+ *   wv[y, x] = the same along y                                     for y < H - 1
+ * Schedule.  For t = 1 .. T: lambda_t = 1.5 lambda 4^(T-t) / (4^T - 1), formed in double on
+ * the host and cast to f32; iteration t is a horizontal pass (every row), then a vertical
+ * pass (every column), both with lambda_t.
+ * One pass solves, for every line of n pixels with neighbour weights w_i (between i and
+ * i + 1), the system (I + lambda_t L) u = r:
+ *   a_i = -lambda_t w_(i-1) (0 at i = 0),  c_i = -lambda_t w_i (0 at i = n - 1),
+ *   b_i = 1 - a_i - c_i,    a_i u_(i-1) + b_i u_i + c_i u_(i+1) = r_i
+ * for the two right-hand sides num and den, which share the matrix; the pass overwrites
+ * both.  A line of one pixel is the identity.  The systems are strictly diagonally dominant,
+ * so they are eliminated without pivoting, in f32 (a Thomas sweep per line: the same inputs
+ * give the same bits, call after call).
+ * Outputs.  refined [B, H, W] = num / den where den > 1e-30f; elsewhere disp bit for bit, or
+ * 0 if disp is not finite (den underflows only deep inside a region without evidence at a
+ * small lambda).  support [B, H, W] (NULL = not written) = den: how much confident evidence
+ * reached the pixel.
+ * workspace: lea_disparity_refine_workspace_bytes(B, H, W) bytes on the device (0 for a
+ * non-positive size), 4-byte aligned.  2 + 4 T launches on the stream; capturable.
+ * LEA_E_INVALID, before any launch: a null guide, disp, workspace or refined; B, H or W < 1
+ * (or B above 32767, H or W above 2^21, B*H*W above 2^31 - 1); C outside 1..4; iterations outside 1..8;
+ * lambda or sigma not a finite number > 0; a guide batch stride below C*H*W; a misaligned
+ * workspace; refined or support overlapping an input, the workspace or one another; the
+ * workspace overlapping an input. */
+size_t lea_disparity_refine_workspace_bytes(int B, int H, int W);
+int lea_disparity_refine_f32(const float* guide, int64_t guide_bstride, const float* disp,
+                             const float* conf, const uint8_t* exclude, int B, int C, int H,
+                             int W, float lambda, float sigma, int iterations, void* workspace,
+                             float* refined, float* support, void* stream);
+
 /* ---- bf16 path (BASELINE configs 3 and 4) ----
  * Activations are bf16 in the "c8" layout: NCDHW with channels blocked by 8
  * innermost, x[b][c/8][d][h][w][c%8] (one voxel's 8 channels = one 16-byte word;

@@ -95,5 +95,16 @@ def obtain_predict_args(argv=None):
                         help="pixels of context dropped on every cut side of a tile under --scene")
     parser.add_argument("--scene_ramp", type=int, default=32,
                         help="width of the blend ramp between tiles under --scene (1..256)")
+    parser.add_argument("--refine", type=int, default=0,
+                        help="1: confidence-weighted edge-preserving refinement of the disparity (the fast "
+                             "global smoother; guide the left image, confidence the peak mass, the pixels the "
+                             "left-right check flags excluded): also write {index}_refined.npy/.png and "
+                             "{index}_support.png; implies the confidence and left-right heads it needs "
+                             "(not in the reference)")
+    parser.add_argument("--refine_lambda", type=float, default=8000.0,
+                        help="smoothness weight of --refine (OpenCV's default; untuned)")
+    parser.add_argument("--refine_sigma", type=float, default=0.05,
+                        help="edge sensitivity of --refine in units of the standardised image (untuned)")
+    parser.add_argument("--refine_iters", type=int, default=3, help="iterations of --refine (1..8)")
     add_leastereo_args(parser)
     return parser.parse_args(argv)

@@ -774,6 +774,66 @@ def photometric_grad(left: torch.Tensor, right: torch.Tensor, disp: torch.Tensor
     return ddisp
 
 
+# ---- confidence-weighted edge-preserving refinement (csrc/refine.hip) ----
+
+REFINE_LAMBDA, REFINE_SIGMA, REFINE_ITERATIONS = 8000.0, 0.05, 3
+
+DisparityRefined = collections.namedtuple("DisparityRefined", "disp disp_refined support peak disp_right state")
+DisparityRefined.__doc__ = """What ``LEAStereo.forward_refined`` returns, all [B, H, W]:
+  disp          the left-view disparity of ``forward``, bit for bit
+  disp_refined  ``fgs_refine`` of it: guide the left image, conf ``peak``, exclude ``state``
+  support       how much confident evidence reached each pixel (the smoothed confidence)
+  peak          the peak mass of ``forward_with_confidence``
+  disp_right    the right view's disparity of ``forward_lr``
+  state         uint8, the left-right check's state of ``forward_lr``
+None differentiable."""
+
+
+def fgs_refine(guide: torch.Tensor, disp: torch.Tensor, conf: torch.Tensor = None, exclude: torch.Tensor = None,
+               lam: float = REFINE_LAMBDA, sigma: float = REFINE_SIGMA, iterations: int = REFINE_ITERATIONS,
+               return_support: bool = False):
+    """``lea_disparity_refine_f32`` (include/leastereo_hip.h): the confidence-weighted,
+    image-guided weighted-least-squares smoothing of a disparity map by the fast global
+    smoother.  ``guide`` [B, C, H, W] float32 with 1 <= C <= 4 (a channel slice of a larger
+    tensor goes as a view), ``disp`` [B, H, W] float32, ``conf`` [B, H, W] float32 or None
+    (= 1), ``exclude`` [B, H, W] uint8 or bool or None (non-zero = no evidence;
+    ``DisparityLR.state`` goes as it is).  ``sigma`` is in the guide's units.  Returns the
+    refined disparity [B, H, W], with ``return_support`` (refined, support).  2 + 4 *
+    ``iterations`` launches on the current stream; nothing is read back."""
+    _require_cuda(guide, disp, conf)
+    if guide.dim() != 4 or not 1 <= guide.shape[1] <= 4:
+        raise ValueError(f"fgs_refine: guide must be [B, C, H, W] with 1 <= C <= 4, got {tuple(guide.shape)}")
+    b, c, h, w = guide.shape
+    if tuple(disp.shape) != (b, h, w):
+        raise ValueError(f"disp must be [B, H, W] = {(b, h, w)}, got {tuple(disp.shape)}")
+    if conf is not None and tuple(conf.shape) != (b, h, w):
+        raise ValueError(f"conf must be [B, H, W] = {(b, h, w)}, got {tuple(conf.shape)}")
+    e = None
+    if exclude is not None:
+        if not exclude.is_cuda or tuple(exclude.shape) != (b, h, w) or exclude.dtype not in (torch.uint8, torch.bool):
+            raise ValueError("exclude must be a [B, H, W] uint8 or bool tensor on the device")
+        e = (exclude.view(torch.uint8) if exclude.dtype == torch.bool else exclude).contiguous()
+    if not (lam > 0 and math.isfinite(lam) and sigma > 0 and math.isfinite(sigma)):
+        raise ValueError(f"fgs_refine: lam {lam} and sigma {sigma} must be finite numbers > 0")
+    if not 1 <= int(iterations) <= 8 or int(iterations) != iterations:
+        raise ValueError(f"fgs_refine: iterations {iterations} (1..8)")
+    g, gbs = _image_view(guide)
+    d = disp.contiguous()
+    cf = None if conf is None else conf.contiguous()
+    lib = _lib.load()
+    ws = torch.empty(lib.lea_disparity_refine_workspace_bytes(b, h, w) // 4, device=d.device, dtype=torch.float32)
+    refined = torch.empty((b, h, w), device=d.device, dtype=torch.float32)
+    support = torch.empty_like(refined) if return_support else None
+    rec = None if _probe is None else _probe_launch("disparity_refine", 0.0, 4.0 * d.numel() * (c + 3 + 22 * iterations))
+    check(lib.lea_disparity_refine_f32(g.data_ptr(), gbs, d.data_ptr(), None if cf is None else cf.data_ptr(),
+                                       None if e is None else e.data_ptr(), b, c, h, w, float(lam), float(sigma),
+                                       int(iterations), ws.data_ptr(), refined.data_ptr(),
+                                       None if support is None else support.data_ptr(), _stream()),
+          "lea_disparity_refine_f32")
+    _probe_end(rec)
+    return (refined, support) if return_support else refined
+
+
 # ------------------------------------------------------------------ bf16 path (c8)
 # Activations: torch.bfloat16 [B, C/8, D, H, W, 8] ("c8": 8 channels per voxel word).
 

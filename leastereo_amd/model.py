@@ -305,6 +305,31 @@ class LEAStereo(nn.Module):
         disp = self.disp(cost, fast_exp=fast)
         return kernels.lr_check(disp, self.disp.right(cost, fast_exp=fast), threshold)
 
+    def forward_refined(self, x, y, lam=kernels.REFINE_LAMBDA, sigma=kernels.REFINE_SIGMA,
+                        iterations=kernels.REFINE_ITERATIONS, radius=4, lr_threshold=1.0):
+        """``forward`` with the confidence-weighted edge-preserving refinement, as
+        ``kernels.DisparityRefined``: one feature call, one matching call, the stats head (the
+        disparity of ``forward`` bit for bit, and the peak mass within ``radius``), the right
+        head, the left-right check at ``lr_threshold``, then ``kernels.fgs_refine`` with the
+        left image ``x`` as guide, ``conf`` the peak mass and ``exclude`` the check's state.
+        ``sigma`` is in units of the standardised image that ``forward`` receives; the defaults
+        restate OpenCV's and are untuned.  Inference only: the outputs are not differentiable."""
+        if not x.is_cuda:
+            raise RuntimeError("leastereo_amd.LEAStereo runs the matching net on a ROCm device only")
+        if self.training or (torch.is_grad_enabled() and (x.requires_grad or y.requires_grad)):
+            raise RuntimeError("forward_refined is inference only (its outputs have no backward): "
+                               "call model.eval() and pass inputs that do not require grad")
+        self.check_shape(x.shape[2], x.shape[3])
+        f = self.feature(x, y) if STEM_PAIR else self.feature(torch.cat((x, y), 0))
+        fx, fy = f[: x.shape[0]], f[x.shape[0]:]
+        cost = self.matching.executor().run_features(fx, fy, self.maxdisp)
+        fast = self.precision == "bf16"
+        st = self.disp.stats(cost, radius, fast_exp=fast)  # the call of forward_with_confidence
+        lr = kernels.lr_check(st.disp, self.disp.right(cost, fast_exp=fast), lr_threshold, want_filled=False)
+        refined, support = kernels.fgs_refine(x, st.disp, st.peak, lr.state, lam, sigma, iterations,
+                                              return_support=True)
+        return kernels.DisparityRefined(st.disp, refined, support, st.peak, lr.disp_right, lr.state)
+
     def forward_scene(self, left_u8, right_u8, tile, **kw):
         """A uint8 scene pair [H, W, 3|4] of any size through overlapping ``tile`` = (h, w)
         forwards, gathered and blended on the device: ``scene.SceneResult`` at the scene's
@@ -326,14 +351,16 @@ class LEAStereo(nn.Module):
         self.precision = precision
 
     def graphed(self, batch: int, height: int, width: int, confidence: bool = False, radius: int = 4,
-                lr_threshold=None):
+                lr_threshold=None, refine=None):
         """``forward`` for one input shape captured into a HIP graph (SURVEY.md §7:
         one host call per batch instead of ~140 launches, for serving and for ranks
         that share a node's host CPUs).  The forward issues only library kernels on
         the current stream and never synchronises, so it captures as is.
         ``confidence=True`` captures ``forward_with_confidence(..., radius)`` instead, a number
-        for ``lr_threshold`` captures ``forward_lr(..., lr_threshold)``; not both in one capture."""
-        return GraphedForward(self, batch, height, width, confidence, radius, lr_threshold)
+        for ``lr_threshold`` captures ``forward_lr(..., lr_threshold)``; not both in one capture.
+        ``refine=dict(...)`` (the keywords of ``forward_refined``; an empty dict for its defaults)
+        captures ``forward_refined`` instead, on its own."""
+        return GraphedForward(self, batch, height, width, confidence, radius, lr_threshold, refine)
 
 
 class GraphedForward:
@@ -341,10 +368,14 @@ class GraphedForward:
     with static input/output buffers; ``__call__(x, y)`` copies the inputs in,
     replays, and returns the static output (overwritten by the next call): the disparity,
     with ``confidence`` the ``DisparityStats`` of ``forward_with_confidence``, or with
-    ``lr_threshold`` the ``DisparityLR`` of ``forward_lr``."""
+    ``lr_threshold`` the ``DisparityLR`` of ``forward_lr``, or with ``refine`` the
+    ``DisparityRefined`` of ``forward_refined``."""
 
     def __init__(self, model: LEAStereo, batch: int, height: int, width: int, confidence: bool = False,
-                 radius: int = 4, lr_threshold=None):
+                 radius: int = 4, lr_threshold=None, refine=None):
+        if refine is not None and (confidence or lr_threshold is not None):
+            raise ValueError("graphed(): refine=dict(...) captures forward_refined on its own; give radius and "
+                             "lr_threshold inside the dict")
         if confidence and lr_threshold is not None:
             raise ValueError("graphed(): confidence=True and lr_threshold in one capture is not supported; "
                              "capture two graphs")
@@ -357,7 +388,8 @@ class GraphedForward:
         model.check_shape(height, width)
         dev = next(model.parameters()).device
         self.model = model
-        run = ((lambda a, b: model.forward_with_confidence(a, b, radius)) if confidence else
+        run = ((lambda a, b: model.forward_refined(a, b, **refine)) if refine is not None else
+               (lambda a, b: model.forward_with_confidence(a, b, radius)) if confidence else
                (lambda a, b: model.forward_lr(a, b, lr_threshold)) if lr_threshold is not None else model)
         self.x = torch.zeros(batch, 3, height, width, device=dev)
         self.y = torch.zeros_like(self.x)

@@ -27,6 +27,10 @@ Restates the host-side steps around ``LEAStereo.forward`` (predict.py:144-243):
                        tile of ``scene.SceneRunner``; an image larger than it is cut into
                        overlapping tiles, gathered and blended on the device, and every output
                        above has the image's size under its usual name
+  * ``predict_pair_refined`` / ``predict_scene_refined`` / ``save_refined``  not in the reference:
+                       --refine 1 adds the confidence-weighted edge-preserving refinement of
+                       ``LEAStereo.forward_refined`` ({index}_refined.npy / .png, {index}_support.png);
+                       under --scene it runs once on the blended scene (``scene.refine_scene``)
 Arithmetic runs on the HIP kernels; what stays on the host is file I/O (PIL, PFM, PNG).
 
     python predict.py --sceneflow=1 --maxdisp=192 --crop_height=576 --crop_width=960 \
@@ -142,8 +146,12 @@ def predict_scene(runner, leftname, rightname, confidence="none"):
     as ``predict_pair`` and ``predict_pair_lr`` shape them -- disp the disparity, or (disparity,
     conf, local) under ``confidence``; lr (disparity, right-view disparity, state, filled) when
     the runner has an ``lr_threshold``, else None."""
+    return _scene_maps(runner(*load_images(leftname, rightname)), runner.model.maxdisp, confidence)
+
+
+def _scene_maps(res, maxdisp, confidence):
+    """A ``SceneResult`` as ``predict_scene`` returns it."""
     import math
-    res = runner(*load_images(leftname, rightname))
     disp = res.disp.cpu().numpy()
     lr = None
     if res.disp_right is not None:
@@ -153,8 +161,56 @@ def predict_scene(runner, leftname, rightname, confidence="none"):
     if confidence not in ("entropy", "peak"):
         raise ValueError(f"confidence {confidence!r}: one of none, entropy, peak")
     if confidence == "entropy":  # DisparityStats.confidence on the blended entropy
-        return (disp, (1.0 - res.entropy / math.log(runner.model.maxdisp)).cpu().numpy(), None), lr
+        return (disp, (1.0 - res.entropy / math.log(maxdisp)).cpu().numpy(), None), lr
     return (disp, res.peak.cpu().numpy(), res.disp_local.cpu().numpy()), lr
+
+
+def predict_pair_refined(model, leftname, rightname, crop_height, crop_width, lam, sigma, iterations, radius=4,
+                         lr_threshold=1.0, device="cuda"):
+    """``predict_pair`` through ``model.forward_refined``: (disparity, refined disparity,
+    support), each cropped like the disparity.  The disparity is ``predict_pair``'s bit for bit."""
+    left, right, h, w = load_transform(*load_images(leftname, rightname), crop_height, crop_width,
+                                       device)
+    with torch.no_grad():
+        out = model.forward_refined(left, right, lam=lam, sigma=sigma, iterations=iterations, radius=radius,
+                                    lr_threshold=lr_threshold)
+    return tuple(crop_output(t.cpu().numpy(), h, w, crop_height, crop_width)
+                 for t in (out.disp, out.disp_refined, out.support))
+
+
+def predict_scene_refined(runner, leftname, rightname, lam, sigma, iterations, confidence="none"):
+    """``predict_scene`` plus the refinement of the blended scene (``scene.refine_scene``: once,
+    at the image's size, never per tile): (disp, lr, (refined, support)), the first two as
+    ``predict_scene`` returns them.  The runner should blend the peak mass and run the
+    left-right check (``confidence=True``, an ``lr_threshold``): they are the refinement's
+    confidence and exclusion."""
+    from .scene import refine_scene
+    left, right = load_images(leftname, rightname)
+    res = runner(left, right)
+    refined, support = refine_scene(res, left, lam, sigma, iterations, return_support=True)
+    disp, lr = _scene_maps(res, runner.model.maxdisp, confidence)
+    return disp, lr, (refined.cpu().numpy(), support.cpu().numpy())
+
+
+def refine_pair(model, runner, leftname, rightname, opt):
+    """--refine on one pair: through the scene runner when there is one (--scene), else one
+    ``forward_refined`` on the crop.  Returns (disp, lr, (refined, support)); disp and lr are
+    None without a runner (the pair's other outputs then come from their own calls)."""
+    if runner is not None:
+        return predict_scene_refined(runner, leftname, rightname, opt.refine_lambda, opt.refine_sigma,
+                                     opt.refine_iters, opt.confidence)
+    out = predict_pair_refined(model, leftname, rightname, opt.crop_height, opt.crop_width, opt.refine_lambda,
+                               opt.refine_sigma, opt.refine_iters, opt.conf_radius,
+                               opt.lr_check if opt.lr_check > 0 else 1.0)
+    return None, None, out[1:]
+
+
+def save_refined(prefix, refined, support, max_disp=192):
+    """<prefix>_refined.npy (float32), <prefix>_refined.png (coloured like the disparity) and
+    <prefix>_support.png (8-bit: the smoothed confidence, in [0, 1], scaled by 255)."""
+    np.save(prefix + "_refined.npy", refined.astype(np.float32))
+    plot_disparity(prefix + "_refined.png", refined, max_disp)
+    save_float_png(prefix + "_support.png", np.clip(support, 0.0, 1.0))
 
 
 def occlusion_u8(state):
@@ -322,6 +378,11 @@ def main(argv=None):
     opt = default_arch_args(obtain_predict_args(argv))
     if not opt.lr_check >= 0:
         raise ValueError(f"--lr_check {opt.lr_check}: a threshold in pixels > 0, or 0 for off")
+    if opt.refine and not (opt.refine_lambda > 0 and opt.refine_sigma > 0 and 1 <= opt.refine_iters <= 8):
+        raise ValueError(f"--refine_lambda {opt.refine_lambda} and --refine_sigma {opt.refine_sigma} must be > 0, "
+                         f"--refine_iters {opt.refine_iters} in 1..8")
+    if opt.refine and opt.satellite:
+        raise NotImplementedError("--refine writes its maps beside the --sceneflow outputs only")
     if not torch.cuda.is_available():
         raise RuntimeError("leastereo_amd runs on a ROCm device only")
     model = LEAStereo(opt, "cuda")
@@ -338,8 +399,8 @@ def main(argv=None):
         from .scene import SceneRunner
         runner = SceneRunner(model, opt.crop_height, opt.crop_width, tile_batch=opt.scene_batch,
                              context=opt.scene_context, ramp=opt.scene_ramp,
-                             confidence=opt.confidence != "none", radius=opt.conf_radius,
-                             lr_threshold=opt.lr_check if opt.lr_check > 0 else None)
+                             confidence=opt.confidence != "none" or bool(opt.refine), radius=opt.conf_radius,
+                             lr_threshold=opt.lr_check if opt.lr_check > 0 else (1.0 if opt.refine else None))
     os.makedirs(opt.save_path, exist_ok=True)
     with open(opt.test_list) as f:
         lines = f.readlines()
@@ -360,16 +421,22 @@ def main(argv=None):
             gt, _, _ = read_pfm(gtname)
             plot_disparity(opt.save_path + f"{index:d}_gt.png", gt, 192)
         t0 = time.time()
-        lr = None
+        lr, refined = None, None
         if runner is None and opt.lr_check > 0:
             lr = predict_pair_lr(model, leftname, rightname, opt.crop_height, opt.crop_width, opt.lr_check)
-        if runner is not None:  # --scene: every map of the pair from one call
+        if runner is not None and opt.refine:  # --scene --refine: the refinement of the blended maps with them
+            disp, lr, refined = refine_pair(model, runner, leftname, rightname, opt)
+            if not opt.lr_check > 0:
+                lr = None  # the check that --refine implies writes no files of its own
+        elif runner is not None:  # --scene: every map of the pair from one call
             disp, lr = predict_scene(runner, leftname, rightname, opt.confidence)
         elif lr is None or opt.confidence != "none":  # with --confidence: its own call on the pair
             disp = predict_pair(model, leftname, rightname, opt.crop_height, opt.crop_width,
                                 confidence=opt.confidence, radius=opt.conf_radius)
         else:
             disp = lr[0]
+        if runner is None and opt.refine:  # its own call on the pair
+            refined = refine_pair(model, None, leftname, rightname, opt)[2]
         print(f"Processing time: {time.time() - t0:.4f}")
         if lr is not None:
             save_lr(os.path.join(opt.save_path, f"{index}"), *lr[1:])
@@ -378,6 +445,11 @@ def main(argv=None):
         if opt.confidence != "none":
             disp, conf, local = disp
             save_confidence(os.path.join(opt.save_path, f"{index}"), conf, local)
+        if refined is not None:
+            save_refined(os.path.join(opt.save_path, f"{index}"), *refined)
+            print(f"{index}: refined at lambda {opt.refine_lambda:g}, sigma {opt.refine_sigma:g}, "
+                  f"{opt.refine_iters} iterations; {100.0 * float((refined[1] <= 1e-30).mean()):.2f} % of the pixels "
+                  f"without support")
         if opt.photo_check:
             warped, err, loss, l1, dssim = photometric_check(model, leftname, rightname, opt.crop_height,
                                                              opt.crop_width, opt.lr_check)

@@ -295,3 +295,36 @@ class SceneRunner:
             lr = kernels.lr_check(out["disp"][None], out["disp_right"][None], self.lr_threshold)
             out["state"], out["disp_filled"] = lr.state[0], lr.disp_filled[0]
         return SceneResult(**out)
+
+
+@torch.no_grad()
+def refine_scene(result: SceneResult, left_u8, lam: float = None, sigma: float = None, iterations: int = None,
+                 return_support: bool = False):
+    """``kernels.fgs_refine`` of a ``SceneResult``, once, at scene size, after the blend (never
+    per tile: a tile's solve stops at its cut).  The guide is the uint8 scene ``left_u8``
+    [H, W, 3|4] standardised with the whole scene's statistics (what the tiles were cut from),
+    ``conf`` is ``result.peak`` if the runner blended it, ``exclude`` is ``result.state`` if it
+    ran the left-right check.  Returns the refined disparity [H, W], with ``return_support``
+    (refined, support).  ``None`` for a parameter takes the default of ``kernels.fgs_refine``."""
+    from . import kernels
+    disp = result.disp
+    left = left_u8
+    if isinstance(left, np.ndarray):
+        left = torch.from_numpy(np.ascontiguousarray(left))
+    if left.dtype != torch.uint8:
+        raise ValueError(f"refine_scene takes the decoded uint8 scene, got {left.dtype}")
+    if left.dim() == 4 and left.shape[0] == 1:
+        left = left[0]
+    if left.dim() != 3 or tuple(left.shape[:2]) != tuple(disp.shape):
+        raise ValueError(f"left_u8 must be [H, W, 3|4] of the result's size {tuple(disp.shape)}, got "
+                         f"{tuple(left.shape)}")
+    left = left.to(disp.device, non_blocking=True)
+    h, w = disp.shape
+    origin = torch.zeros((1, 2), dtype=torch.int32, device=disp.device)
+    guide = kernels.standardize_tiles_u8(left, left, origin, h, w)[0]  # one tile: the whole scene
+    out = kernels.fgs_refine(guide, disp[None], None if result.peak is None else result.peak[None],
+                             None if result.state is None else result.state[None],
+                             kernels.REFINE_LAMBDA if lam is None else lam,
+                             kernels.REFINE_SIGMA if sigma is None else sigma,
+                             kernels.REFINE_ITERATIONS if iterations is None else iterations, return_support=True)
+    return (out[0][0], out[1][0]) if return_support else out[0][0]
