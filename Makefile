@@ -102,8 +102,16 @@ build/asan/refine_asan_main.o: tests/asan/refine_asan.cpp include/leastereo_hip.
 build/asan/refine_asan: build/asan/refine_asan_main.o $(ASANOBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -fno-gpu-sanitize -fsanitize=address -o $@ $^
 
+# the speckle filter's two entries (lea_disparity_speckle_workspace_bytes, lea_disparity_speckle_f32)
+build/asan/speckle_asan_main.o: tests/asan/speckle_asan.cpp include/leastereo_hip.h
+	@mkdir -p build/asan
+	$(HIPCC) $(ASANFLAGS) -c $< -o $@
+
+build/asan/speckle_asan: build/asan/speckle_asan_main.o $(ASANOBJ)
+	$(HIPCC) --offload-arch=$(ARCH) -fno-gpu-sanitize -fsanitize=address -o $@ $^
+
 asan: build/asan/capi_asan build/asan/disp_stats_asan build/asan/lr_asan build/asan/loss_asan build/asan/transform_asan build/asan/photo_asan \
-      build/asan/scene_asan build/asan/refine_asan
+      build/asan/scene_asan build/asan/refine_asan build/asan/speckle_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/capi_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/disp_stats_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/lr_asan
@@ -112,6 +120,7 @@ asan: build/asan/capi_asan build/asan/disp_stats_asan build/asan/lr_asan build/a
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/photo_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/scene_asan
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/refine_asan
+	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/speckle_asan
 
 clean:
 	rm -rf build $(LIB)

@@ -437,6 +437,46 @@ int lea_disparity_refine_f32(const float* guide, int64_t guide_bstride, const fl
                              int W, float lambda, float sigma, int iterations, void* workspace,
                              float* refined, float* support, void* stream);
 
+/* Speckle filter (additive: the ABI number stays 14): the connected components of a
+ * disparity map and the removal of the small ones, OpenCV's filterSpeckles (the
+ * speckleWindowSize / speckleRange of StereoBM / StereoSGBM), on the device.  It belongs
+ * between the left-right check and the refinement: the refinement spreads a confident
+ * speckle, and fills an excluded one from its neighbours.  Neither entry synchronises the
+ * host, allocates or reads anything back.
+ *
+ * Inputs.  disp: [B, H, W] f32.  exclude: [B, H, W] bytes or NULL (the state of
+ * lea_disparity_lr_check can be passed as it is).  max_diff: finite, >= 0.  max_size: >= 0.
+ * fill: any float, NaN allowed.
+ * Connectivity.  A pixel is a wall if its disp is not finite or its exclude is non-zero; a
+ * wall belongs to no component.  Two 4-neighbours of the same image are connected if neither
+ * is a wall and fabsf(a - b) <= max_diff in f32 (the subtraction is exactly rounded; -0.0 and
+ * 0.0 are connected at max_diff = 0).  The components are the connected components of that
+ * graph: the edges are pairwise, so the values may drift along a component.  Images of a
+ * batch never connect.
+ * Outputs, each [B, H, W], each optional through NULL (never written), at least one required:
+ *   labels   (int32) the smallest linear index y*W + x of the pixel's component; -1 for a wall
+ *   size     (int32) the number of pixels of the pixel's component; 0 for a wall
+ *   state    (uint8) exclude where that is non-zero; elsewhere 3 (LEA_LR_SPECKLE, beside the
+ *            0 / 1 / 2 of lea_disparity_lr_check) where 0 < size <= max_size and 0 otherwise;
+ *            a pixel whose disp is not finite and whose exclude is 0 gets 3 too: it carries
+ *            no evidence.  max_size = 0 removes no component.
+ *   filtered (f32) fill where state != 0, disp bit for bit elsewhere
+ * The labels are canonical and the sizes integer sums, so all four are the same bits call
+ * after call, whatever the scheduling.
+ * workspace: lea_disparity_speckle_workspace_bytes(B, H, W) bytes on the device (0 for a
+ * non-positive size), 4-byte aligned; its contents need not be initialised.  Four launches on
+ * the stream (three when the image is one tile); capturable.
+ * LEA_E_INVALID, before any launch: a null disp or workspace; every output null; B, H or
+ * W < 1 (or B above 65535, H above 1048560, H*W not below 2^31); max_diff negative or not finite;
+ * max_size negative; a misaligned workspace; an output overlapping an input, the workspace or
+ * another output; the workspace overlapping an input. */
+#define LEA_LR_SPECKLE 3
+size_t lea_disparity_speckle_workspace_bytes(int B, int H, int W);
+int lea_disparity_speckle_f32(const float* disp, const uint8_t* exclude, int B, int H, int W,
+                              float max_diff, int max_size, float fill, void* workspace,
+                              int32_t* labels, int32_t* size, uint8_t* state, float* filtered,
+                              void* stream);
+
 /* ---- bf16 path (BASELINE configs 3 and 4) ----
  * Activations are bf16 in the "c8" layout: NCDHW with channels blocked by 8
  * innermost, x[b][c/8][d][h][w][c%8] (one voxel's 8 channels = one 16-byte word;

@@ -106,5 +106,14 @@ def obtain_predict_args(argv=None):
     parser.add_argument("--refine_sigma", type=float, default=0.05,
                         help="edge sensitivity of --refine in units of the standardised image (untuned)")
     parser.add_argument("--refine_iters", type=int, default=3, help="iterations of --refine (1..8)")
+    parser.add_argument("--speckle", type=int, default=0, metavar="SIZE",
+                        help="speckle filter (0 = off): remove the connected components of the disparity of at "
+                             "most SIZE pixels (OpenCV's filterSpeckles; 50-200 is its recommended window, "
+                             "untuned here): also write {index}_speckle.png and {index}_despeckled.npy; with "
+                             "--lr_check the flagged pixels are walls, with --refine 1 the refinement fills the "
+                             "removed pixels (not in the reference)")
+    parser.add_argument("--speckle_diff", type=float, default=1.0, metavar="D",
+                        help="largest disparity step in pixels between connected neighbours under --speckle "
+                             "(OpenCV's speckleRange, 1-2 recommended; untuned)")
     add_leastereo_args(parser)
     return parser.parse_args(argv)

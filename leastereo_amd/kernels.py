@@ -558,6 +558,7 @@ def disparity_regression_stats(cost: torch.Tensor, maxdisp: int, radius: int = 4
 
 
 LR_CONSISTENT, LR_INCONSISTENT, LR_OUT_OF_VIEW = 0, 1, 2
+LR_SPECKLE = 3  # written by ``speckle_filter`` into the same state map
 
 DisparityLR = collections.namedtuple("DisparityLR", "disp disp_right state disp_filled")
 DisparityLR.__doc__ = """What ``LEAStereo.forward_lr`` / ``lr_check`` return (``None`` where not asked for):
@@ -832,6 +833,75 @@ def fgs_refine(guide: torch.Tensor, disp: torch.Tensor, conf: torch.Tensor = Non
           "lea_disparity_refine_f32")
     _probe_end(rec)
     return (refined, support) if return_support else refined
+
+
+# ---- speckle filter: connected components of the disparity (csrc/speckle.hip) ----
+
+SPECKLE_MAX_SIZE, SPECKLE_MAX_DIFF = 200, 1.0
+
+DisparitySpeckle = collections.namedtuple("DisparitySpeckle", "disp state size labels filtered")
+DisparitySpeckle.__doc__ = """What ``speckle_filter`` returns, all [B, H, W] (``None`` where not asked for):
+  disp      the input, as it was given
+  state     uint8: ``exclude`` where that is non-zero, elsewhere ``LR_SPECKLE`` (3) on the removed pixels, else 0
+  size      int32: the pixel count of the pixel's component, 0 for a wall
+  labels    int32: the smallest linear index y * W + x of the pixel's component, -1 for a wall
+  filtered  float32: ``fill`` where state != 0, ``disp`` bit for bit elsewhere
+None differentiable."""
+
+
+def speckle_filter(disp: torch.Tensor, exclude: torch.Tensor = None, max_size: int = SPECKLE_MAX_SIZE,
+                   max_diff: float = SPECKLE_MAX_DIFF, fill: float = 0.0, want_labels: bool = False,
+                   want_size: bool = True, want_filtered: bool = True) -> DisparitySpeckle:
+    """``lea_disparity_speckle_f32`` (include/leastereo_hip.h): the 4-connected components of a
+    disparity map (two neighbours connected when |a - b| <= ``max_diff`` px; a non-finite or
+    excluded pixel is a wall) and the removal of those of at most ``max_size`` pixels, OpenCV's
+    ``filterSpeckles``.  ``disp`` [B, H, W] or [H, W] float32 on the device, ``exclude`` of the
+    same shape, uint8 or bool, or None (``DisparityLR.state`` goes as it is, and its values come
+    back in ``state``).  Returns ``DisparitySpeckle``; ``state`` is always computed.  The
+    defaults (200 px, 1.0 px) are the middle of OpenCV's recommended 50-200 window and 1-2
+    range and are **untuned**: there is no trained checkpoint and no real pair here to tune
+    them on.  Four launches on the current stream; nothing is read back."""
+    if not isinstance(disp, torch.Tensor) or disp.dim() not in (2, 3):
+        raise ValueError(f"speckle_filter: disp must be [B, H, W] or [H, W], got "
+                         f"{tuple(disp.shape) if isinstance(disp, torch.Tensor) else type(disp)}")
+    _require_cuda(disp)
+    shape = tuple(disp.shape)
+    if exclude is not None:
+        if (not isinstance(exclude, torch.Tensor) or not exclude.is_cuda or tuple(exclude.shape) != shape
+                or exclude.dtype not in (torch.uint8, torch.bool)):
+            raise ValueError(f"speckle_filter: exclude must be a {shape} uint8 or bool tensor on the device")
+    if isinstance(max_diff, bool) or not isinstance(max_diff, (int, float)) or not (
+            max_diff >= 0 and math.isfinite(max_diff)):
+        raise ValueError(f"speckle_filter: max_diff {max_diff} must be a finite number >= 0")
+    if isinstance(max_size, bool) or not isinstance(max_size, int) or not 0 <= max_size <= 2 ** 31 - 1:
+        raise ValueError(f"speckle_filter: max_size {max_size} must be an integer in 0 .. 2^31 - 1")
+    if not isinstance(fill, (int, float)):
+        raise ValueError(f"speckle_filter: fill {fill} must be a number")
+    if 0 in shape:
+        raise ValueError(f"speckle_filter: empty map {shape}")
+    if shape[-2] * shape[-1] >= 2 ** 31:
+        raise ValueError(f"speckle_filter: H * W = {shape[-2] * shape[-1]} is not below 2^31")
+    d = disp.contiguous()
+    e = None
+    if exclude is not None:
+        e = (exclude.view(torch.uint8) if exclude.dtype == torch.bool else exclude).contiguous()
+    b = shape[0] if len(shape) == 3 else 1
+    h, w = shape[-2:]
+    lib = _lib.load()
+    ws = torch.empty(lib.lea_disparity_speckle_workspace_bytes(b, h, w) // 4, device=d.device, dtype=torch.int32)
+    state = torch.empty(shape, device=d.device, dtype=torch.uint8)
+    size = torch.empty(shape, device=d.device, dtype=torch.int32) if want_size else None
+    labels = torch.empty(shape, device=d.device, dtype=torch.int32) if want_labels else None
+    filtered = torch.empty(shape, device=d.device, dtype=torch.float32) if want_filtered else None
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    rec = None if _probe is None else _probe_launch(
+        "disparity_speckle", 0.0, d.numel() * (30.0 + (4.0 if want_size else 0.0) + (4.0 if want_labels else 0.0) +
+                                               (8.0 if want_filtered else 0.0)))
+    check(lib.lea_disparity_speckle_f32(d.data_ptr(), ptr(e), b, h, w, float(max_diff), int(max_size), float(fill),
+                                        ws.data_ptr(), ptr(labels), ptr(size), state.data_ptr(), ptr(filtered),
+                                        _stream()), "lea_disparity_speckle_f32")
+    _probe_end(rec)
+    return DisparitySpeckle(disp, state, size, labels, filtered)
 
 
 # ------------------------------------------------------------------ bf16 path (c8)

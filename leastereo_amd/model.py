@@ -306,19 +306,26 @@ class LEAStereo(nn.Module):
         return kernels.lr_check(disp, self.disp.right(cost, fast_exp=fast), threshold)
 
     def forward_refined(self, x, y, lam=kernels.REFINE_LAMBDA, sigma=kernels.REFINE_SIGMA,
-                        iterations=kernels.REFINE_ITERATIONS, radius=4, lr_threshold=1.0):
+                        iterations=kernels.REFINE_ITERATIONS, radius=4, lr_threshold=1.0, speckle=None):
         """``forward`` with the confidence-weighted edge-preserving refinement, as
         ``kernels.DisparityRefined``: one feature call, one matching call, the stats head (the
         disparity of ``forward`` bit for bit, and the peak mass within ``radius``), the right
         head, the left-right check at ``lr_threshold``, then ``kernels.fgs_refine`` with the
         left image ``x`` as guide, ``conf`` the peak mass and ``exclude`` the check's state.
         ``sigma`` is in units of the standardised image that ``forward`` receives; the defaults
-        restate OpenCV's and are untuned.  Inference only: the outputs are not differentiable."""
+        restate OpenCV's and are untuned.  ``speckle=dict(max_size=..., max_diff=...)`` (an empty
+        dict for the untuned defaults of ``kernels.speckle_filter``) runs the speckle filter
+        between the check and the refinement, as OpenCV does: on the disparity, with the check's
+        flags as walls; the refinement then excludes, and so fills, the removed components too,
+        and ``state`` marks them ``kernels.LR_SPECKLE``.  ``None``: no such call.
+        Inference only: the outputs are not differentiable."""
         if not x.is_cuda:
             raise RuntimeError("leastereo_amd.LEAStereo runs the matching net on a ROCm device only")
         if self.training or (torch.is_grad_enabled() and (x.requires_grad or y.requires_grad)):
             raise RuntimeError("forward_refined is inference only (its outputs have no backward): "
                                "call model.eval() and pass inputs that do not require grad")
+        if speckle is not None and (not isinstance(speckle, dict) or set(speckle) - {"max_size", "max_diff"}):
+            raise ValueError(f"forward_refined: speckle must be None or a dict of max_size / max_diff, got {speckle!r}")
         self.check_shape(x.shape[2], x.shape[3])
         f = self.feature(x, y) if STEM_PAIR else self.feature(torch.cat((x, y), 0))
         fx, fy = f[: x.shape[0]], f[x.shape[0]:]
@@ -326,9 +333,12 @@ class LEAStereo(nn.Module):
         fast = self.precision == "bf16"
         st = self.disp.stats(cost, radius, fast_exp=fast)  # the call of forward_with_confidence
         lr = kernels.lr_check(st.disp, self.disp.right(cost, fast_exp=fast), lr_threshold, want_filled=False)
-        refined, support = kernels.fgs_refine(x, st.disp, st.peak, lr.state, lam, sigma, iterations,
+        state = lr.state
+        if speckle is not None:
+            state = kernels.speckle_filter(st.disp, state, want_size=False, want_filtered=False, **speckle).state
+        refined, support = kernels.fgs_refine(x, st.disp, st.peak, state, lam, sigma, iterations,
                                               return_support=True)
-        return kernels.DisparityRefined(st.disp, refined, support, st.peak, lr.disp_right, lr.state)
+        return kernels.DisparityRefined(st.disp, refined, support, st.peak, lr.disp_right, state)
 
     def forward_scene(self, left_u8, right_u8, tile, **kw):
         """A uint8 scene pair [H, W, 3|4] of any size through overlapping ``tile`` = (h, w)
@@ -358,8 +368,8 @@ class LEAStereo(nn.Module):
         the current stream and never synchronises, so it captures as is.
         ``confidence=True`` captures ``forward_with_confidence(..., radius)`` instead, a number
         for ``lr_threshold`` captures ``forward_lr(..., lr_threshold)``; not both in one capture.
-        ``refine=dict(...)`` (the keywords of ``forward_refined``; an empty dict for its defaults)
-        captures ``forward_refined`` instead, on its own."""
+        ``refine=dict(...)`` (the keywords of ``forward_refined``, ``speckle=dict(...)`` among them;
+        an empty dict for its defaults) captures ``forward_refined`` instead, on its own."""
         return GraphedForward(self, batch, height, width, confidence, radius, lr_threshold, refine)
 
 

@@ -31,6 +31,10 @@ Restates the host-side steps around ``LEAStereo.forward`` (predict.py:144-243):
                        --refine 1 adds the confidence-weighted edge-preserving refinement of
                        ``LEAStereo.forward_refined`` ({index}_refined.npy / .png, {index}_support.png);
                        under --scene it runs once on the blended scene (``scene.refine_scene``)
+  * ``despeckle`` / ``save_speckle``  not in the reference: --speckle SIZE [--speckle_diff D]
+                       adds the speckle filter of ``kernels.speckle_filter`` on the written
+                       disparity ({index}_speckle.png, {index}_despeckled.npy; the flags of
+                       --lr_check are its walls), and feeds --refine 1 the removed pixels
 Arithmetic runs on the HIP kernels; what stays on the host is file I/O (PIL, PFM, PNG).
 
     python predict.py --sceneflow=1 --maxdisp=192 --crop_height=576 --crop_width=960 \
@@ -166,28 +170,32 @@ def _scene_maps(res, maxdisp, confidence):
 
 
 def predict_pair_refined(model, leftname, rightname, crop_height, crop_width, lam, sigma, iterations, radius=4,
-                         lr_threshold=1.0, device="cuda"):
+                         lr_threshold=1.0, device="cuda", speckle=None):
     """``predict_pair`` through ``model.forward_refined``: (disparity, refined disparity,
-    support), each cropped like the disparity.  The disparity is ``predict_pair``'s bit for bit."""
+    support), each cropped like the disparity.  The disparity is ``predict_pair``'s bit for bit.
+    ``speckle``: the dict of ``forward_refined`` (None: the call as it is without it)."""
     left, right, h, w = load_transform(*load_images(leftname, rightname), crop_height, crop_width,
                                        device)
+    kw = {} if speckle is None else {"speckle": speckle}
     with torch.no_grad():
         out = model.forward_refined(left, right, lam=lam, sigma=sigma, iterations=iterations, radius=radius,
-                                    lr_threshold=lr_threshold)
+                                    lr_threshold=lr_threshold, **kw)
     return tuple(crop_output(t.cpu().numpy(), h, w, crop_height, crop_width)
                  for t in (out.disp, out.disp_refined, out.support))
 
 
-def predict_scene_refined(runner, leftname, rightname, lam, sigma, iterations, confidence="none"):
+def predict_scene_refined(runner, leftname, rightname, lam, sigma, iterations, confidence="none", speckle=None):
     """``predict_scene`` plus the refinement of the blended scene (``scene.refine_scene``: once,
     at the image's size, never per tile): (disp, lr, (refined, support)), the first two as
     ``predict_scene`` returns them.  The runner should blend the peak mass and run the
     left-right check (``confidence=True``, an ``lr_threshold``): they are the refinement's
-    confidence and exclusion."""
+    confidence and exclusion.  ``speckle``: the dict of ``refine_scene`` (None: the call as it
+    is without it)."""
     from .scene import refine_scene
     left, right = load_images(leftname, rightname)
     res = runner(left, right)
-    refined, support = refine_scene(res, left, lam, sigma, iterations, return_support=True)
+    kw = {} if speckle is None else {"speckle": speckle}
+    refined, support = refine_scene(res, left, lam, sigma, iterations, return_support=True, **kw)
     disp, lr = _scene_maps(res, runner.model.maxdisp, confidence)
     return disp, lr, (refined.cpu().numpy(), support.cpu().numpy())
 
@@ -196,13 +204,48 @@ def refine_pair(model, runner, leftname, rightname, opt):
     """--refine on one pair: through the scene runner when there is one (--scene), else one
     ``forward_refined`` on the crop.  Returns (disp, lr, (refined, support)); disp and lr are
     None without a runner (the pair's other outputs then come from their own calls)."""
+    kw = {} if speckle_options(opt) is None else {"speckle": speckle_options(opt)}
     if runner is not None:
         return predict_scene_refined(runner, leftname, rightname, opt.refine_lambda, opt.refine_sigma,
-                                     opt.refine_iters, opt.confidence)
+                                     opt.refine_iters, opt.confidence, **kw)
     out = predict_pair_refined(model, leftname, rightname, opt.crop_height, opt.crop_width, opt.refine_lambda,
                                opt.refine_sigma, opt.refine_iters, opt.conf_radius,
-                               opt.lr_check if opt.lr_check > 0 else 1.0)
+                               opt.lr_check if opt.lr_check > 0 else 1.0, **kw)
     return None, None, out[1:]
+
+
+def speckle_options(opt):
+    """--speckle SIZE [--speckle_diff D] as the ``speckle`` dict of ``forward_refined`` /
+    ``refine_scene``; None when the filter is off (SIZE 0).  Refuses a negative SIZE and a D that
+    is negative or not finite."""
+    size, diff = getattr(opt, "speckle", 0), getattr(opt, "speckle_diff", 1.0)
+    if size < 0 or size > 2 ** 31 - 1:
+        raise ValueError(f"--speckle {size}: a component size in pixels > 0, or 0 for off")
+    if not 0 <= diff < float("inf"):
+        raise ValueError(f"--speckle_diff {diff}: a finite disparity step in pixels >= 0")
+    if not size:
+        return None
+    if getattr(opt, "satellite", 0):
+        raise NotImplementedError("--speckle writes its maps beside the --sceneflow outputs only")
+    return dict(max_size=int(size), max_diff=float(diff))
+
+
+def despeckle(disp, state, max_size, max_diff, device="cuda"):
+    """``kernels.speckle_filter`` of a written disparity map [H, W] (numpy; under --scene the
+    blended scene, never a tile: a component cut by a tile's edge looks small), with the
+    left-right check's ``state`` as walls when there is one: (removed, despeckled), the pixels
+    the filter removed (bool) and the disparity with 0 on every flagged pixel."""
+    from . import kernels
+    d = torch.from_numpy(np.ascontiguousarray(disp, dtype=np.float32)).to(device)
+    e = None if state is None else torch.from_numpy(np.ascontiguousarray(state, dtype=np.uint8)).to(device)
+    out = kernels.speckle_filter(d, e, max_size, max_diff, want_size=False)
+    return (out.state == kernels.LR_SPECKLE).cpu().numpy(), out.filtered.cpu().numpy()
+
+
+def save_speckle(prefix, removed, despeckled):
+    """<prefix>_speckle.png (8-bit: 255 on the removed pixels) and <prefix>_despeckled.npy (float32)."""
+    save_float_png(prefix + "_speckle.png", np.where(removed, 255, 0).astype(np.uint8))
+    np.save(prefix + "_despeckled.npy", despeckled.astype(np.float32))
 
 
 def save_refined(prefix, refined, support, max_disp=192):
@@ -383,6 +426,7 @@ def main(argv=None):
                          f"--refine_iters {opt.refine_iters} in 1..8")
     if opt.refine and opt.satellite:
         raise NotImplementedError("--refine writes its maps beside the --sceneflow outputs only")
+    speckle = speckle_options(opt)
     if not torch.cuda.is_available():
         raise RuntimeError("leastereo_amd runs on a ROCm device only")
     model = LEAStereo(opt, "cuda")
@@ -450,6 +494,11 @@ def main(argv=None):
             print(f"{index}: refined at lambda {opt.refine_lambda:g}, sigma {opt.refine_sigma:g}, "
                   f"{opt.refine_iters} iterations; {100.0 * float((refined[1] <= 1e-30).mean()):.2f} % of the pixels "
                   f"without support")
+        if speckle is not None:  # on the map that is written, at its size
+            removed, despeckled = despeckle(disp, None if lr is None else lr[2], **speckle)
+            save_speckle(os.path.join(opt.save_path, f"{index}"), removed, despeckled)
+            print(f"{index}: speckle filter at {speckle['max_size']} px, {speckle['max_diff']:g} px steps removes "
+                  f"{100.0 * float(removed.mean()):.2f} % of the pixels")
         if opt.photo_check:
             warped, err, loss, l1, dssim = photometric_check(model, leftname, rightname, opt.crop_height,
                                                              opt.crop_width, opt.lr_check)

@@ -299,14 +299,21 @@ class SceneRunner:
 
 @torch.no_grad()
 def refine_scene(result: SceneResult, left_u8, lam: float = None, sigma: float = None, iterations: int = None,
-                 return_support: bool = False):
+                 return_support: bool = False, speckle: dict = None):
     """``kernels.fgs_refine`` of a ``SceneResult``, once, at scene size, after the blend (never
     per tile: a tile's solve stops at its cut).  The guide is the uint8 scene ``left_u8``
     [H, W, 3|4] standardised with the whole scene's statistics (what the tiles were cut from),
     ``conf`` is ``result.peak`` if the runner blended it, ``exclude`` is ``result.state`` if it
     ran the left-right check.  Returns the refined disparity [H, W], with ``return_support``
-    (refined, support).  ``None`` for a parameter takes the default of ``kernels.fgs_refine``."""
+    (refined, support).  ``None`` for a parameter takes the default of ``kernels.fgs_refine``.
+    ``speckle=dict(max_size=..., max_diff=...)`` (an empty dict for the defaults) runs
+    ``speckle_scene`` first, and the refinement excludes what it removed; ``None``: no such
+    call."""
     from . import kernels
+    if speckle is not None:
+        if not isinstance(speckle, dict) or set(speckle) - {"max_size", "max_diff"}:
+            raise ValueError(f"refine_scene: speckle must be None or a dict of max_size / max_diff, got {speckle!r}")
+        result = result._replace(state=speckle_scene(result, **speckle).state)
     disp = result.disp
     left = left_u8
     if isinstance(left, np.ndarray):
@@ -328,3 +335,17 @@ def refine_scene(result: SceneResult, left_u8, lam: float = None, sigma: float =
                              kernels.REFINE_SIGMA if sigma is None else sigma,
                              kernels.REFINE_ITERATIONS if iterations is None else iterations, return_support=True)
     return (out[0][0], out[1][0]) if return_support else out[0][0]
+
+
+@torch.no_grad()
+def speckle_scene(result: SceneResult, max_size: int = None, max_diff: float = None, fill: float = 0.0):
+    """``kernels.speckle_filter`` of a ``SceneResult``, once, at scene size, after the blend:
+    the blended disparity, with ``result.state`` as walls if the runner ran the left-right
+    check.  Never run the filter per tile: a component cut by a tile's edge looks small there
+    and would be removed, while at scene size it is judged at its whole size.  Returns
+    ``kernels.DisparitySpeckle`` with [H, W] maps (state, size, filtered).  ``None`` for a
+    parameter takes the (untuned) default of ``kernels.speckle_filter``."""
+    from . import kernels
+    return kernels.speckle_filter(result.disp, result.state,
+                                  kernels.SPECKLE_MAX_SIZE if max_size is None else max_size,
+                                  kernels.SPECKLE_MAX_DIFF if max_diff is None else max_diff, fill)
