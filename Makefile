@@ -37,90 +37,28 @@ build/asan/%.o: leastereo_amd/csrc/%.hip $(wildcard leastereo_amd/csrc/*.h) incl
 	@mkdir -p build/asan
 	$(HIPCC) $(ASANFLAGS) -c $< -o $@
 
-build/asan/capi_asan_main.o: tests/asan/capi_asan.cpp include/leastereo_hip.h include/leastereo_hip_tuning.h
+# one stand-alone driver per group of entry points (tests/asan/NAME.cpp -> build/asan/NAME), each
+# linked with every unit: capi the ABI at large, disp_stats lea_disparity_regression_stats, lr the
+# left-right check, loss the median and edge loss, transform the training transform, photo
+# photometric consistency, scene whole-scene inference, refine the refinement, speckle the filter
+ASANDRIVERS := capi_asan disp_stats_asan lr_asan loss_asan transform_asan photo_asan scene_asan refine_asan \
+               speckle_asan
+
+$(ASANDRIVERS:%=build/asan/%_main.o): build/asan/%_main.o: tests/asan/%.cpp include/leastereo_hip.h include/leastereo_hip_tuning.h
 	@mkdir -p build/asan
 	$(HIPCC) $(ASANFLAGS) -c $< -o $@
 
-build/asan/capi_asan: build/asan/capi_asan_main.o $(ASANOBJ)
+$(ASANDRIVERS:%=build/asan/%): build/asan/%: build/asan/%_main.o $(ASANOBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -fno-gpu-sanitize -fsanitize=address -o $@ $^
 
-# the confidence head's entry (lea_disparity_regression_stats) has a driver of its own
-build/asan/disp_stats_asan_main.o: tests/asan/disp_stats_asan.cpp include/leastereo_hip.h
-	@mkdir -p build/asan
-	$(HIPCC) $(ASANFLAGS) -c $< -o $@
+# one recipe line per driver, in the list's order
+define ASANRUN
+	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/$(1)
 
-build/asan/disp_stats_asan: build/asan/disp_stats_asan_main.o $(ASANOBJ)
-	$(HIPCC) --offload-arch=$(ARCH) -fno-gpu-sanitize -fsanitize=address -o $@ $^
+endef
 
-# the left-right check's two entries (lea_disparity_regression_right, lea_disparity_lr_check)
-build/asan/lr_asan_main.o: tests/asan/lr_asan.cpp include/leastereo_hip.h
-	@mkdir -p build/asan
-	$(HIPCC) $(ASANFLAGS) -c $< -o $@
-
-build/asan/lr_asan: build/asan/lr_asan_main.o $(ASANOBJ)
-	$(HIPCC) --offload-arch=$(ARCH) -fno-gpu-sanitize -fsanitize=address -o $@ $^
-
-# the edge-aware loss's three entries (lea_median5x5_f32, lea_edge_loss_f32, lea_edge_loss_grad_f32)
-build/asan/loss_asan_main.o: tests/asan/loss_asan.cpp include/leastereo_hip.h
-	@mkdir -p build/asan
-	$(HIPCC) $(ASANFLAGS) -c $< -o $@
-
-build/asan/loss_asan: build/asan/loss_asan_main.o $(ASANOBJ)
-	$(HIPCC) --offload-arch=$(ARCH) -fno-gpu-sanitize -fsanitize=address -o $@ $^
-
-# the training transform's two entries (lea_train_transform_workspace_bytes, lea_train_transform_u8)
-build/asan/transform_asan_main.o: tests/asan/transform_asan.cpp include/leastereo_hip.h
-	@mkdir -p build/asan
-	$(HIPCC) $(ASANFLAGS) -c $< -o $@
-
-build/asan/transform_asan: build/asan/transform_asan_main.o $(ASANOBJ)
-	$(HIPCC) --offload-arch=$(ARCH) -fno-gpu-sanitize -fsanitize=address -o $@ $^
-
-# photometric consistency's three entries (lea_photometric_workspace_bytes, lea_photometric_f32,
-# lea_photometric_grad_f32)
-build/asan/photo_asan_main.o: tests/asan/photo_asan.cpp include/leastereo_hip.h
-	@mkdir -p build/asan
-	$(HIPCC) $(ASANFLAGS) -c $< -o $@
-
-build/asan/photo_asan: build/asan/photo_asan_main.o $(ASANOBJ)
-	$(HIPCC) --offload-arch=$(ARCH) -fno-gpu-sanitize -fsanitize=address -o $@ $^
-
-# whole-scene inference's three entries (lea_standardize_tiles_workspace_bytes, lea_standardize_tiles_u8,
-# lea_tile_blend_f32)
-build/asan/scene_asan_main.o: tests/asan/scene_asan.cpp include/leastereo_hip.h
-	@mkdir -p build/asan
-	$(HIPCC) $(ASANFLAGS) -c $< -o $@
-
-build/asan/scene_asan: build/asan/scene_asan_main.o $(ASANOBJ)
-	$(HIPCC) --offload-arch=$(ARCH) -fno-gpu-sanitize -fsanitize=address -o $@ $^
-
-# the disparity refinement's two entries (lea_disparity_refine_workspace_bytes, lea_disparity_refine_f32)
-build/asan/refine_asan_main.o: tests/asan/refine_asan.cpp include/leastereo_hip.h
-	@mkdir -p build/asan
-	$(HIPCC) $(ASANFLAGS) -c $< -o $@
-
-build/asan/refine_asan: build/asan/refine_asan_main.o $(ASANOBJ)
-	$(HIPCC) --offload-arch=$(ARCH) -fno-gpu-sanitize -fsanitize=address -o $@ $^
-
-# the speckle filter's two entries (lea_disparity_speckle_workspace_bytes, lea_disparity_speckle_f32)
-build/asan/speckle_asan_main.o: tests/asan/speckle_asan.cpp include/leastereo_hip.h
-	@mkdir -p build/asan
-	$(HIPCC) $(ASANFLAGS) -c $< -o $@
-
-build/asan/speckle_asan: build/asan/speckle_asan_main.o $(ASANOBJ)
-	$(HIPCC) --offload-arch=$(ARCH) -fno-gpu-sanitize -fsanitize=address -o $@ $^
-
-asan: build/asan/capi_asan build/asan/disp_stats_asan build/asan/lr_asan build/asan/loss_asan build/asan/transform_asan build/asan/photo_asan \
-      build/asan/scene_asan build/asan/refine_asan build/asan/speckle_asan
-	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/capi_asan
-	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/disp_stats_asan
-	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/lr_asan
-	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/loss_asan
-	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/transform_asan
-	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/photo_asan
-	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/scene_asan
-	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/refine_asan
-	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/speckle_asan
+asan: $(addprefix build/asan/,$(ASANDRIVERS))
+	$(foreach d,$(ASANDRIVERS),$(call ASANRUN,$(d)))
 
 clean:
 	rm -rf build $(LIB)

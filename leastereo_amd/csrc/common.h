@@ -66,6 +66,12 @@ inline int launch_status(const char* what) {
 
 constexpr int kWave = 64;
 
+// do the byte spans [a, a + an) and [b, b + bn) share a byte?  (the entries' aliasing checks)
+inline bool spans_overlap(const void* a, size_t an, const void* b, size_t bn) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + bn && y < x + an;
+}
+
 // ---- trilinear interpolation with aten's source-index rule (UpSample.h:
 // area_pixel_compute_scale / area_pixel_compute_source_index); shared by the
 // resample kernel and the conv's resampling stager so both round identically.

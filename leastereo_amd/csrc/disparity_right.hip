@@ -22,7 +22,7 @@
 // the same column is kRCols - 1 further, so the four taps of a candidate are two
 // two-address reads off one base.  Plane D3 repeats plane D3 - 1 (the depth clamp) and
 // columns are clamped into [0, W3) when staged (the width clamp): k1 = k0 + 1 and
-// i1 = i0 + 1 always.  The depth and width axes' aten weights come from src_axis once per
+// i1 = i0 + 1 always.  The depth and width axes' aten weights come from axis_index once per
 // workgroup, as two small LDS tables (per od; per left column of the tile).
 //
 // The round-6 factorisation does not carry over: along the diagonal the three samples of a
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(kDispThreads) void disparity_right_rows_f32(const f
   const int oh = blockIdx.y;
   const int b = blockIdx.z;
   const int c0 = xr0 / 3;
-  const AxisW ah = src_axis(rh, oh, H3, Ho);
+  const Axis ah = axis_index(rh, oh, H3, Ho, 0);
   const long long HW = (long long)H3 * W3;
   const float* base = cost + (long long)b * D3 * HW;
   const float* r0 = base + (long long)ah.i0 * W3;
@@ -131,11 +131,11 @@ __global__ __launch_bounds__(kDispThreads) void disparity_right_rows_f32(const f
     hl[e] = ah.l0 * r0[o] + ah.l1 * r1[o];
   }
   for (int od = threadIdx.x; od < MD; od += kDispThreads) {
-    const AxisW ad = src_axis(rd, od, D3, MD);
+    const Axis ad = axis_index(rd, od, D3, MD, 0);
     dt[od] = RDepth{ad.i0 * (kRCols - 1), ad.l0, ad.l1};
   }
   for (int e = threadIdx.x; e < kX; e += kDispThreads) {
-    const AxisW aw = src_axis(rw, min(xr0 + e, Wo - 1), W3, Wo);
+    const Axis aw = axis_index(rw, min(xr0 + e, Wo - 1), W3, Wo, 0);
     ct[e] = RCol{aw.i0 - c0 + 2, aw.l1};
   }
   __syncthreads();
@@ -168,15 +168,15 @@ __global__ __launch_bounds__(kDispThreads) void disparity_right_any_f32(const fl
   if (xr >= Wo) return;
   const int oh = blockIdx.y;
   const int b = blockIdx.z;
-  const AxisW ah = src_axis(rh, oh, H3, Ho);
+  const Axis ah = axis_index(rh, oh, H3, Ho, 0);
   const long long HW = (long long)H3 * W3;
   const float* base = cost + (long long)b * D3 * HW;
   const float* r0 = base + (long long)ah.i0 * W3;
   const float* r1 = base + (long long)ah.i1 * W3;
   const int n = min(MD, Wo - xr);
   auto u = [&](int od) {
-    const AxisW ad = src_axis(rd, od, D3, MD);
-    const AxisW aw = src_axis(rw, xr + od, W3, Wo);  // xr + od <= Wo - 1: i0, i1 in [0, W3)
+    const Axis ad = axis_index(rd, od, D3, MD, 0);
+    const Axis aw = axis_index(rw, xr + od, W3, Wo, 0);  // xr + od <= Wo - 1: i0, i1 in [0, W3)
     auto plane = [&](int k) {
       const long long o = (long long)k * HW;
       return aw.l0 * (ah.l0 * r0[o + aw.i0] + ah.l1 * r1[o + aw.i0]) +
@@ -193,40 +193,23 @@ extern "C" int lea_disparity_regression_right(const void* cost, float* disp_righ
                                               int maxdisp, int dtype, void* stream) {
   using namespace lea;
   clear_error();
-  LEA_CHECK_ARG(cost && disp_right, "lea_disparity_regression_right: null pointer");
-  LEA_CHECK_ARG(B > 0 && D3 > 0 && H3 > 0 && W3 > 0 && maxdisp > 0,
-                "lea_disparity_regression_right: bad shape B=%d D3=%d H3=%d W3=%d maxdisp=%d", B, D3, H3, W3,
-                maxdisp);
-  LEA_CHECK_ARG(3LL * H3 <= 65535 && B <= 65535 && 3LL * W3 <= 0x7fffffffLL - kDispThreads &&
-                    3LL * D3 <= 0x7fffffffLL,
-                "lea_disparity_regression_right: grid too large");
-  if (dtype != LEA_F32 && dtype != LEA_BF16) {
-    set_error("lea_disparity_regression_right: dtype %d unsupported", dtype);
-    return LEA_E_UNSUPPORTED;
-  }
-  if (maxdisp % 3 != 0 || maxdisp / 3 != D3) {
-    set_error("lea_disparity_regression_right: maxdisp %d is not 3 * D3 (D3=%d)", maxdisp, D3);
-    return LEA_E_UNSUPPORTED;
-  }
-  {  // the kernels read cost while they write
-    const size_t n_out = (size_t)B * 9u * (size_t)H3 * (size_t)W3 * sizeof(float);
-    const size_t n_cost = (size_t)B * (size_t)D3 * (size_t)H3 * (size_t)W3 * sizeof(float);
-    const uintptr_t c = (uintptr_t)cost, o = (uintptr_t)disp_right;
-    LEA_CHECK_ARG(c + n_cost <= o || o + n_out <= c, "lea_disparity_regression_right: disp_right overlaps cost");
-  }
-  const int Wo = 3 * W3;
-  const float rd = (float)D3 / (float)maxdisp, rh = (float)H3 / (float)(3 * H3), rw = (float)W3 / (float)(3 * W3);
-  const bool fast = dtype == LEA_BF16;
-  const dim3 grid((Wo + kDispThreads - 1) / kDispThreads, 3 * H3, B);
+  const char* who = "lea_disparity_regression_right";
+  DispHead h;
+  if (int rc = disp_head_check(who, true, "lea_disparity_regression_right: disp_right overlaps cost", cost,
+                               &disp_right, 1, B, D3, H3, W3, maxdisp, dtype, &h))
+    return rc;
+  const float rd = (float)D3 / (float)maxdisp, rh = h.rh, rw = h.rw;
+  const bool fast = h.fast;
+  const dim3 grid = h.grid;
 #define LEA_RIGHT_ROWS(D3_)                                                                                \
   if (D3 == D3_) {                                                                                        \
     auto k_ = fast ? disparity_right_rows_f32<D3_, true> : disparity_right_rows_f32<D3_, false>;            \
     k_<<<grid, kDispThreads, 0, as_stream(stream)>>>((const float*)cost, disp_right, H3, W3, rd, rh, rw);   \
-    return launch_status("lea_disparity_regression_right");                                               \
+    return launch_status(who);                                                                            \
   }
   LEA_RIGHT_ROWS(4) LEA_RIGHT_ROWS(8) LEA_RIGHT_ROWS(16) LEA_RIGHT_ROWS(32) LEA_RIGHT_ROWS(64) LEA_RIGHT_ROWS(88)
 #undef LEA_RIGHT_ROWS
   auto k_ = fast ? disparity_right_any_f32<true> : disparity_right_any_f32<false>;
   k_<<<grid, kDispThreads, 0, as_stream(stream)>>>((const float*)cost, disp_right, D3, H3, W3, rd, rh, rw);
-  return launch_status("lea_disparity_regression_right");
+  return launch_status(who);
 }

@@ -9,7 +9,7 @@
 //   Sy q   = (q00 - q20) + 2 (q01 - q21) + (q02 - q22)       (H-2) x (W-2) valid positions
 // Each response is a sum of pair differences, so a constant window gives exactly 0.
 //
-// Forward (edge_loss_partial_kernel, then edge_loss_final_kernel in the same call):
+// Forward (edge_loss_partial_kernel, then reduce4.h's final kernel in the same call):
 //   sums[0] = #m   sums[1] = sum_m smooth_l1(d), beta 1   sums[2] = sum_m |d|
 //   sums[3] = sum over positions and batch of |Sx p| exp(-|Sx t~|) + |Sy p| exp(-|Sy t~|)
 // per-pixel terms in f32 (expf), summed in float64: per thread, per wave by shuffles, per
@@ -26,7 +26,7 @@
 // A workgroup stages pred and tsmooth for its 64 x 16 tile plus a halo of 2, writes the two
 // weighted sign fields of the tile plus 1 into LDS and gathers from them; again the sums
 // are pair differences, so the edge part is exactly 0 where pred is constant all around.
-#include "common.h"
+#include "reduce4.h"
 
 namespace lea {
 
@@ -96,37 +96,7 @@ __global__ __launch_bounds__(kElThreads) void edge_loss_partial_kernel(const Edg
       acc[3] += (double)e;
     }
   }
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    for (int o = kWave / 2; o > 0; o >>= 1) acc[k] += __shfl_down(acc[k], o);
-  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
-  if (lane == 0)
-    for (int k = 0; k < 4; ++k) red[wave][k] = acc[k];
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    double s = 0.0;
-    for (int w = 0; w < kElThreads / kWave; ++w) s += red[w][threadIdx.x];
-    const long long blk = ((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    partial[blk * 4 + threadIdx.x] = s;
-  }
-}
-
-// one workgroup: thread t sums partials t, t + 256, ... in order, then a fixed tree
-__global__ __launch_bounds__(kElThreads) void edge_loss_final_kernel(const double* __restrict__ partial,
-                                                                     const long long nblk,
-                                                                     double* __restrict__ sums) {
-  __shared__ double red[kElThreads][4];
-  double acc[4] = {0.0, 0.0, 0.0, 0.0};
-  for (long long i = threadIdx.x; i < nblk; i += kElThreads)
-    for (int k = 0; k < 4; ++k) acc[k] += partial[i * 4 + k];
-  for (int k = 0; k < 4; ++k) red[threadIdx.x][k] = acc[k];
-  __syncthreads();
-  for (int o = kElThreads / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o)
-      for (int k = 0; k < 4; ++k) red[threadIdx.x][k] += red[threadIdx.x + o][k];
-    __syncthreads();
-  }
-  if (threadIdx.x < 4) sums[threadIdx.x] = red[0][threadIdx.x];
+  reduce4_block<kElThreads>(acc, red, partial);
 }
 
 __global__ __launch_bounds__(kElThreads) void edge_loss_grad_kernel(const EdgeMaps a, const double* __restrict__ sums,
@@ -198,11 +168,6 @@ static int edge_check(const char* who, const float* pred, int64_t pbs, const flo
   return LEA_OK;
 }
 
-static bool overlaps(const void* a, size_t an, const void* b, size_t bn) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return !(x + an <= y || y + bn <= x);
-}
-
 }  // namespace lea
 
 extern "C" size_t lea_edge_loss_workspace_bytes(int B, int H, int W) {
@@ -222,14 +187,14 @@ extern "C" int lea_edge_loss_f32(const float* pred, int64_t pred_bstride, const 
   LEA_CHECK_ARG(((uintptr_t)sums & 7) == 0 && ((uintptr_t)workspace & 7) == 0,
                 "%s: sums and workspace must be 8-byte aligned", who);
   const long long nblk = edge_blocks(B, H, W);
-  LEA_CHECK_ARG(!overlaps(sums, 4 * sizeof(double), workspace, (size_t)nblk * 4 * sizeof(double)),
+  LEA_CHECK_ARG(!spans_overlap(sums, 4 * sizeof(double), workspace, (size_t)nblk * 4 * sizeof(double)),
                 "%s: sums overlaps the workspace", who);
   const EdgeMaps a{pred, target, tsmooth, pred_bstride, target_bstride, tsmooth_bstride, H, W, maxdisp};
   const dim3 grid((unsigned)((W + kElW - 1) / kElW), (unsigned)((H + kElH - 1) / kElH), (unsigned)B);
   double* partial = static_cast<double*>(workspace);
   edge_loss_partial_kernel<<<grid, kElThreads, 0, as_stream(stream)>>>(a, partial);
   if (int rc = launch_status(who)) return rc;
-  edge_loss_final_kernel<<<1, kElThreads, 0, as_stream(stream)>>>(partial, nblk, sums);
+  reduce4_final_kernel<kElThreads><<<1, kElThreads, 0, as_stream(stream)>>>(partial, nblk, sums);
   return launch_status("lea_edge_loss_f32 (final)");
 }
 
@@ -251,9 +216,10 @@ extern "C" int lea_edge_loss_grad_f32(const float* pred, int64_t pred_bstride, c
     const void* in[3] = {pred, target, tsmooth};
     const int64_t bs[3] = {pred_bstride, target_bstride, tsmooth_bstride};
     for (int i = 0; i < 3; ++i)
-      LEA_CHECK_ARG(!overlaps(dpred, dn, in[i], 4 * ((size_t)(B - 1) * (size_t)bs[i] + (size_t)hw)),
+      LEA_CHECK_ARG(!spans_overlap(dpred, dn, in[i], 4 * ((size_t)(B - 1) * (size_t)bs[i] + (size_t)hw)),
                     "%s: dpred overlaps input %d (0 = pred, 1 = target, 2 = tsmooth)", who, i);
-    LEA_CHECK_ARG(!overlaps(dpred, dn, sums, 4 * sizeof(double)) && !overlaps(dpred, dn, scales, 2 * sizeof(float)),
+    LEA_CHECK_ARG(!spans_overlap(dpred, dn, sums, 4 * sizeof(double)) &&
+                      !spans_overlap(dpred, dn, scales, 2 * sizeof(float)),
                   "%s: dpred overlaps sums or scales", who);
   }
   const EdgeMaps a{pred, target, tsmooth, pred_bstride, target_bstride, tsmooth_bstride, H, W, maxdisp};

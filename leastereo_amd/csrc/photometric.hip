@@ -33,7 +33,7 @@
 // LDS: 3 workgroups per CU.  The coefficients are worked out in float64 from the f32 maps and
 // rounded once (1/d1 and 1/d2 reach the hundreds where a window's means or variances are
 // small, and a, b, c are then differences of large terms); the box sums and the rest are f32.
-#include "common.h"
+#include "reduce4.h"
 
 namespace lea {
 
@@ -195,37 +195,7 @@ __global__ __launch_bounds__(kPhThreads) void photometric_kernel(const PhotoMaps
     }
     if (err) err[(long long)b * hw + (long long)gy * a.W + gx] = e;
   }
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    for (int o = kWave / 2; o > 0; o >>= 1) acc[k] += __shfl_down(acc[k], o);
-  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
-  if (lane == 0)
-    for (int k = 0; k < 4; ++k) red[wave][k] = acc[k];
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    double s = 0.0;
-    for (int w = 0; w < kPhThreads / kWave; ++w) s += red[w][threadIdx.x];
-    const long long blk = ((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    partial[blk * 4 + threadIdx.x] = s;
-  }
-}
-
-// one workgroup: thread t sums partials t, t + 256, ... in order, then a fixed tree
-__global__ __launch_bounds__(kPhThreads) void photometric_final_kernel(const double* __restrict__ partial,
-                                                                       const long long nblk,
-                                                                       double* __restrict__ sums) {
-  __shared__ double red[kPhThreads][4];
-  double acc[4] = {0.0, 0.0, 0.0, 0.0};
-  for (long long i = threadIdx.x; i < nblk; i += kPhThreads)
-    for (int k = 0; k < 4; ++k) acc[k] += partial[i * 4 + k];
-  for (int k = 0; k < 4; ++k) red[threadIdx.x][k] = acc[k];
-  __syncthreads();
-  for (int o = kPhThreads / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o)
-      for (int k = 0; k < 4; ++k) red[threadIdx.x][k] += red[threadIdx.x + o][k];
-    __syncthreads();
-  }
-  if (threadIdx.x < 4) sums[threadIdx.x] = red[0][threadIdx.x];
+  reduce4_block<kPhThreads>(acc, red, partial);
 }
 
 __global__ __launch_bounds__(kPhThreads) void photometric_grad_kernel(const PhotoMaps a,
@@ -344,11 +314,6 @@ static long long photo_blocks(int B, int H, int W) {
   return (long long)B * ((H + kPhH - 1) / kPhH) * ((W + kPhW - 1) / kPhW);
 }
 
-static bool overlaps(const void* a, size_t an, const void* b, size_t bn) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return !(x + an <= y || y + bn <= x);
-}
-
 struct PhotoSpans {  // bytes each input spans
   size_t left, right, disp, exclude;
 };
@@ -381,10 +346,10 @@ static int photo_check(const char* who, const float* left, int64_t lbs, const fl
 // 0 = the output (named what) overlaps none of the inputs
 static int photo_no_overlap(const char* who, const char* what, const void* out, size_t n, const float* left,
                             const float* right, const float* disp, const uint8_t* exclude, const PhotoSpans& sp) {
-  LEA_CHECK_ARG(!overlaps(out, n, left, sp.left), "%s: %s overlaps left", who, what);
-  LEA_CHECK_ARG(!overlaps(out, n, right, sp.right), "%s: %s overlaps right", who, what);
-  LEA_CHECK_ARG(!overlaps(out, n, disp, sp.disp), "%s: %s overlaps disp", who, what);
-  LEA_CHECK_ARG(!exclude || !overlaps(out, n, exclude, sp.exclude), "%s: %s overlaps exclude", who, what);
+  LEA_CHECK_ARG(!spans_overlap(out, n, left, sp.left), "%s: %s overlaps left", who, what);
+  LEA_CHECK_ARG(!spans_overlap(out, n, right, sp.right), "%s: %s overlaps right", who, what);
+  LEA_CHECK_ARG(!spans_overlap(out, n, disp, sp.disp), "%s: %s overlaps disp", who, what);
+  LEA_CHECK_ARG(!exclude || !spans_overlap(out, n, exclude, sp.exclude), "%s: %s overlaps exclude", who, what);
   return LEA_OK;
 }
 
@@ -421,7 +386,7 @@ extern "C" int lea_photometric_f32(const float* left, int64_t left_bstride, cons
     if (!outs[i]) continue;
     if (int rc = photo_no_overlap(who, names[i], outs[i], outn[i], left, right, disp, exclude, sp)) return rc;
     for (int j = 0; j < i; ++j)
-      LEA_CHECK_ARG(!outs[j] || !overlaps(outs[i], outn[i], outs[j], outn[j]), "%s: %s overlaps %s", who, names[i],
+      LEA_CHECK_ARG(!outs[j] || !spans_overlap(outs[i], outn[i], outs[j], outn[j]), "%s: %s overlaps %s", who, names[i],
                     names[j]);
   }
   const PhotoMaps a{left, right, disp, exclude, left_bstride, right_bstride, disp_bstride, exclude_bstride,
@@ -430,7 +395,7 @@ extern "C" int lea_photometric_f32(const float* left, int64_t left_bstride, cons
   double* partial = static_cast<double*>(workspace);
   photometric_kernel<<<grid, kPhThreads, 0, as_stream(stream)>>>(a, alpha, partial, warped, err);
   if (int rc = launch_status(who)) return rc;
-  photometric_final_kernel<<<1, kPhThreads, 0, as_stream(stream)>>>(partial, nblk, sums);
+  reduce4_final_kernel<kPhThreads><<<1, kPhThreads, 0, as_stream(stream)>>>(partial, nblk, sums);
   return launch_status("lea_photometric_f32 (final)");
 }
 
@@ -454,8 +419,8 @@ extern "C" int lea_photometric_grad_f32(const float* left, int64_t left_bstride,
   LEA_CHECK_ARG(ddisp_bstride >= hw, "%s: ddisp batch stride below H*W", who);
   const size_t dn = 4 * ((size_t)(B - 1) * (size_t)ddisp_bstride + (size_t)hw);
   if (int rc = photo_no_overlap(who, "ddisp", ddisp, dn, left, right, disp, exclude, sp)) return rc;
-  LEA_CHECK_ARG(!overlaps(ddisp, dn, sums, 4 * sizeof(double)), "%s: ddisp overlaps sums", who);
-  LEA_CHECK_ARG(!overlaps(ddisp, dn, scales, 2 * sizeof(float)), "%s: ddisp overlaps scales", who);
+  LEA_CHECK_ARG(!spans_overlap(ddisp, dn, sums, 4 * sizeof(double)), "%s: ddisp overlaps sums", who);
+  LEA_CHECK_ARG(!spans_overlap(ddisp, dn, scales, 2 * sizeof(float)), "%s: ddisp overlaps scales", who);
   const PhotoMaps a{left, right, disp, exclude, left_bstride, right_bstride, disp_bstride, exclude_bstride,
                     C, H, W, c1, c2};
   const dim3 grid((unsigned)((W + kPhW - 1) / kPhW), (unsigned)((H + kPhH - 1) / kPhH), (unsigned)B);

@@ -221,11 +221,6 @@ __global__ __launch_bounds__(kFgsTile * 8) void fgs_transpose(const float* __res
   }
 }
 
-static bool fgs_overlaps(const void* a, size_t an, const void* b, size_t bn) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + bn && y < x + an;
-}
-
 }  // namespace lea
 
 extern "C" size_t lea_disparity_refine_workspace_bytes(int B, int H, int W) {
@@ -268,12 +263,12 @@ extern "C" int lea_disparity_refine_f32(const float* guide, int64_t guide_bstrid
     for (int o = 0; o < 2; ++o) {
       if (!outs[o]) continue;
       for (int i = 0; i < 5; ++i)
-        LEA_CHECK_ARG(!ins[i] || !fgs_overlaps(outs[o], pn, ins[i], inn[i]), "%s: %s overlaps %s", who, outname[o],
+        LEA_CHECK_ARG(!ins[i] || !spans_overlap(outs[o], pn, ins[i], inn[i]), "%s: %s overlaps %s", who, outname[o],
                       inname[i]);
     }
-    LEA_CHECK_ARG(!support || !fgs_overlaps(refined, pn, support, pn), "%s: refined overlaps support", who);
+    LEA_CHECK_ARG(!support || !spans_overlap(refined, pn, support, pn), "%s: refined overlaps support", who);
     for (int i = 0; i < 4; ++i)
-      LEA_CHECK_ARG(!ins[i] || !fgs_overlaps(workspace, kFgsPlanes * pn, ins[i], inn[i]),
+      LEA_CHECK_ARG(!ins[i] || !spans_overlap(workspace, kFgsPlanes * pn, ins[i], inn[i]),
                     "%s: the workspace overlaps %s", who, inname[i]);
   }
   float* ws = static_cast<float*>(workspace);

@@ -300,11 +300,6 @@ __global__ __launch_bounds__(kSpThreads) void speckle_apply(const float* __restr
   }
 }
 
-static bool sp_overlaps(const void* a, size_t an, const void* b, size_t bn) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + bn && y < x + an;
-}
-
 }  // namespace lea
 
 extern "C" size_t lea_disparity_speckle_workspace_bytes(int B, int H, int W) {
@@ -340,14 +335,14 @@ extern "C" int lea_disparity_speckle_f32(const float* disp, const uint8_t* exclu
     for (int o = 0; o < 4; ++o) {
       if (!outs[o]) continue;
       for (int i = 0; i < 3; ++i)
-        LEA_CHECK_ARG(!ins[i] || !sp_overlaps(outs[o], outn[o], ins[i], inn[i]), "%s: %s overlaps %s", who,
+        LEA_CHECK_ARG(!ins[i] || !spans_overlap(outs[o], outn[o], ins[i], inn[i]), "%s: %s overlaps %s", who,
                       outname[o], inname[i]);
       for (int q = 0; q < o; ++q)
-        LEA_CHECK_ARG(!outs[q] || !sp_overlaps(outs[o], outn[o], outs[q], outn[q]), "%s: %s overlaps %s", who,
+        LEA_CHECK_ARG(!outs[q] || !spans_overlap(outs[o], outn[o], outs[q], outn[q]), "%s: %s overlaps %s", who,
                       outname[o], outname[q]);
     }
     for (int i = 0; i < 2; ++i)
-      LEA_CHECK_ARG(!ins[i] || !sp_overlaps(workspace, 8 * n, ins[i], inn[i]), "%s: the workspace overlaps %s", who,
+      LEA_CHECK_ARG(!ins[i] || !spans_overlap(workspace, 8 * n, ins[i], inn[i]), "%s: the workspace overlaps %s", who,
                     inname[i]);
   }
   int* parent = static_cast<int*>(workspace);

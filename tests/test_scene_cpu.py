@@ -4,6 +4,7 @@ the symmetry of the two views' weights, the refusals and the predict flag.  The 
 AddressSanitizer driver of the two new entries (tests/asan/scene_asan.cpp) runs with its
 siblings in tests/test_asan_cpu.py (`make asan`)."""
 import os
+import subprocess
 
 import numpy as np
 import pytest
@@ -139,7 +140,11 @@ def test_predict_flag_parses_and_defaults_off():
 
 
 def test_asan_driver_is_wired_into_make_asan():
-    with open(os.path.join(REPO, "Makefile")) as f:
-        mk = f.read()
+    """`make asan` links the driver with every unit and runs it: asked of make itself (a dry run
+    of everything), since the drivers are one list and a pattern rule pair in the Makefile."""
     assert os.path.isfile(os.path.join(REPO, "tests", "asan", "scene_asan.cpp"))
-    assert "build/asan/scene_asan:" in mk and "./build/asan/scene_asan" in mk
+    plan = subprocess.run(["make", "-n", "-B", "asan"], cwd=REPO, capture_output=True, text=True, timeout=120)
+    assert plan.returncode == 0, plan.stderr[-2000:]
+    link = [l for l in plan.stdout.splitlines() if " -o build/asan/scene_asan " in l]
+    assert len(link) == 1 and "build/asan/scene_asan_main.o" in link[0] and "build/asan/tile_blend.o" in link[0]
+    assert "ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/scene_asan" in plan.stdout.splitlines()

@@ -6,6 +6,7 @@ unless they are asked to."""
 import ctypes
 import math
 import os
+import subprocess
 
 import numpy as np
 import pytest
@@ -399,7 +400,11 @@ def test_save_speckle_writes_the_two_files(tmp_path):
 
 
 def test_asan_driver_is_wired_into_make_asan():
-    with open(os.path.join(REPO, "Makefile")) as f:
-        mk = f.read()
-    assert "build/asan/speckle_asan:" in mk and "./build/asan/speckle_asan" in mk
+    """`make asan` links the driver with every unit and runs it: asked of make itself (a dry run
+    of everything), since the drivers are one list and a pattern rule pair in the Makefile."""
     assert os.path.isfile(os.path.join(REPO, "tests", "asan", "speckle_asan.cpp"))
+    plan = subprocess.run(["make", "-n", "-B", "asan"], cwd=REPO, capture_output=True, text=True, timeout=120)
+    assert plan.returncode == 0, plan.stderr[-2000:]
+    link = [l for l in plan.stdout.splitlines() if " -o build/asan/speckle_asan " in l]
+    assert len(link) == 1 and "build/asan/speckle_asan_main.o" in link[0] and "build/asan/speckle.o" in link[0]
+    assert "ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 ./build/asan/speckle_asan" in plan.stdout.splitlines()

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """The disparity regression at the bench shapes, every form (lea_disparity_set_register_form
-3 / 2 / 1 / 0), f32 and fast exp: HIP-event microseconds and the largest difference from form 1.
+1 / 2 / 3 / 4 / 0, in that order), f32 and fast exp: HIP-event microseconds and the largest
+difference from form 1.
 
   python tools/disp_probe.py [--iters 20]
   python tools/disp_probe.py --stats [--iters 20] [--rounds 9]   the confidence head beside the plain one
