@@ -577,6 +577,23 @@ int lea_conv3d_bnrelu_costvolume_wino(const void* left, const void* right, int64
  * unknown, planned as a deep layer).  The engines' tuning hooks are in
  * leastereo_hip_tuning.h. */
 const char* lea_conv3d_wino_kernel_name(int B, int cin, int cout, int D, int H, int W, int costvolume);
+/* lea_conv3d_bnrelu_wino whose epilogue down-samples: instead of the layer's output it writes
+ *   y [B, cout, D/2, H/2, W/2] = lea_resample3d_trilinear(ConvBR(x), align_corners = 1), bit
+ * for bit (for in == 2 out every output voxel reads one aligned 2 x 2 x 2 block, which the
+ * F(4,3) x F(4,3) tile's epilogue holds in registers: csrc/conv3d_wino44.hip), so a layer whose
+ * only consumer reads it one level down (the matching net's stem1) never writes its
+ * full-resolution output.  One source, no residual: LEA_RESIDUAL / LEA_PAIR_SUM are
+ * LEA_E_UNSUPPORTED.  D and H even, W % 4 == 0 (else LEA_E_INVALID); y 16-byte aligned.  The
+ * entry runs only where the planner puts the shape on the F(4,3) x F(4,3) tile in its default
+ * instantiation (lea_conv3d_wino_down2_supported: 1; aligned operands assumed), otherwise
+ * LEA_E_UNSUPPORTED and nothing is launched.  lea_conv3d_wino_down2_kernel_name: the
+ * instantiation it launches ("conv3d_wino44_down2_kernel"), or NULL where unsupported. */
+int lea_conv3d_wino_down2_supported(int B, int cin, int cout, int D, int H, int W);
+const char* lea_conv3d_wino_down2_kernel_name(int B, int cin, int cout, int D, int H, int W);
+int lea_conv3d_bnrelu_wino_down2(const void* x, int64_t x_bstride, const float* w_packed,
+                                 const float* scale, const float* shift, void* y, int64_t y_bstride,
+                                 int B, int cin, int cout, int D, int H, int W, unsigned flags, int dtype,
+                                 void* stream);
 
 /* ---- Matching-net stem0 over the cost volume, factored (csrc/cv_stem.hip) ----
  * Replaces retrain/LEAStereo.py:34-48 + skip_model_3d.py:141 like
@@ -601,6 +618,21 @@ int lea_cv_stem_split_weights(const float* w, float* wl, float* wr, int cout, in
 int lea_cv_stem_combine(const void* lmaps, int64_t l_bstride, const void* rmaps, int64_t r_bstride,
                         const float* scale, const float* shift, void* y, int64_t y_bstride, int B,
                         int cout, int D3, int H, int W, unsigned flags, int dtype, void* stream);
+/* lea_cv_stem_combine (LEA_F32) with a down-sampled side output: besides y it writes
+ *   y2 [B, cout, D3/2, H/2, W/2] = lea_resample3d_trilinear(y, align_corners = 1), bit for bit
+ * (for in == 2 out every output voxel reads one aligned 2 x 2 x 2 block of y, which the
+ * workgroup of a row pair holds in registers), so the matching net's first cell reads stem0
+ * at its own level without a second pass over y.  y is bit-identical to lea_cv_stem_combine's.
+ * lea_cv_stem_down2_supported: 1 where the entry takes the shape -- LEA_F32, D3 and H even,
+ * W % 4 == 0 and every plane of a row pair in one workgroup's LDS (D3 <= 224); anything
+ * else is LEA_E_UNSUPPORTED (the caller runs lea_cv_stem_combine and resamples).  y needs
+ * 16-byte and y2 8-byte alignment (batch strides included) and they must not overlap
+ * (LEA_E_INVALID).  flags: LEA_RELU only. */
+int lea_cv_stem_down2_supported(int cout, int D3, int H, int W, int dtype);
+int lea_cv_stem_combine_down2(const void* lmaps, int64_t l_bstride, const void* rmaps, int64_t r_bstride,
+                              const float* scale, const float* shift, void* y, int64_t y_bstride,
+                              void* y2, int64_t y2_bstride, int B, int cout, int D3, int H, int W,
+                              unsigned flags, int dtype, void* stream);
 
 /* ---- host steps either side of forward ---- */
 

@@ -115,6 +115,9 @@ SIGNATURES = {
     "lea_conv3d_bnrelu_costvolume_wino": (_i, [_p, _p, _i64, _p, _p, _p, _p, _i64, _i, _i, _i,
                                                _i, _i, _i, _u, _i, _p]),
     "lea_conv3d_wino_kernel_name": (ctypes.c_char_p, [_i, _i, _i, _i, _i, _i, _i]),
+    "lea_conv3d_wino_down2_supported": (_i, [_i, _i, _i, _i, _i, _i]),
+    "lea_conv3d_wino_down2_kernel_name": (ctypes.c_char_p, [_i, _i, _i, _i, _i, _i]),
+    "lea_conv3d_bnrelu_wino_down2": (_i, [_p, _i64, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _i, _i, _u, _i, _p]),
     "lea_conv3d_wino_set_tile_override": (_i, [_i, _i, _i]),
     "lea_conv3d_wino_set_variant": (_i, [_i]),
     "lea_conv3d_wino2_set_walk": (_i, [_i]),
@@ -142,6 +145,9 @@ SIGNATURES = {
     "lea_cv_stem_split_weights": (_i, [_p, _p, _p, _i, _i, _p]),
     "lea_cv_stem_combine": (_i, [_p, _i64, _p, _i64, _p, _p, _p, _i64, _i, _i, _i, _i, _i, _u, _i,
                                  _p]),
+    "lea_cv_stem_down2_supported": (_i, [_i, _i, _i, _i, _i]),
+    "lea_cv_stem_combine_down2": (_i, [_p, _i64, _p, _i64, _p, _p, _p, _i64, _p, _i64, _i, _i, _i, _i, _i,
+                                       _u, _i, _p]),
     # host steps either side of forward: predict.py load_data/test_transform, metrics
     "lea_standardize_workspace_bytes": (ctypes.c_size_t, [_i]),
     "lea_standardize_crop_u8": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _i, _i, _p, _p]),

@@ -1138,3 +1138,92 @@ extern "C" int lea_conv3d_bnrelu_costvolume_wino(const void* left, const void* r
                 "lea_conv3d_bnrelu_costvolume_wino: null or aliased pointer");
   return wino::common(a, B, true, dtype, stream);
 }
+
+// ---- the F(4,3) x F(4,3) tile with the down-sampling epilogue (conv3d_wino44.hip, DOWN) ----
+namespace lea {
+namespace wino {
+
+// does the planner put this layer on the F(4,3) x F(4,3) tile in its default instantiation
+// (conv3d_wino44_kernel<false, 0>)?  `a` = the entry's arguments (alignment checked), or NULL
+// for the shape alone (aligned operands assumed, as lea_conv3d_wino_kernel_name)
+static bool down2_plan(int B, int cin, int cout, int D, int H, int W, ConvArgs* a, Plan2* out) {
+  if (B <= 0 || cin <= 0 || cout <= 0 || D < 2 || H < 2 || W < 4 || D % 2 || H % 2 || W % 4 || cin % CIN_B)
+    return false;
+  if ((long long)D * H * W * 4 >= (1LL << 32) || (long long)(cout + 47) * D * H * W >= (1LL << 31)) return false;
+  Plan p = make_plan(B, cout, D, H, W);
+  if (g_w22 && (p.mt == 1 || (g_w22 == 2 && cout <= 32)) && g_variant == 0 && g_override[0] == 0) return false;
+  plan_halo16(p, false, W, a, cin);
+  if (!p.d2 || !g_w44 || g_w44u || g_w44s != 0 || !has_l44(cout)) return false;
+  const Plan2& q = p.p2;
+  if (!(q.q == 8 && q.wc == 2 && q.mte == 1 && q.nw == 4 && q.occ == 2 && q.pv == 3)) return false;
+  if (out) *out = q;
+  return true;
+}
+
+}  // namespace wino
+}  // namespace lea
+
+extern "C" int lea_conv3d_wino_down2_supported(int B, int cin, int cout, int D, int H, int W) {
+  return wino::down2_plan(B, cin, cout, D, H, W, nullptr, nullptr) ? 1 : 0;
+}
+
+extern "C" const char* lea_conv3d_wino_down2_kernel_name(int B, int cin, int cout, int D, int H, int W) {
+  return wino::down2_plan(B, cin, cout, D, H, W, nullptr, nullptr) ? "conv3d_wino44_down2_kernel" : nullptr;
+}
+
+extern "C" int lea_conv3d_bnrelu_wino_down2(const void* x, int64_t x_bstride, const float* w_packed,
+                                            const float* scale, const float* shift, void* y,
+                                            int64_t y_bstride, int B, int cin, int cout, int D, int H, int W,
+                                            unsigned flags, int dtype, void* stream) {
+  clear_error();
+  ConvArgs a{};
+  a.x = (const float*)x;
+  a.xbs = x_bstride;
+  a.cin1 = cin;
+  a.wp = w_packed;
+  a.scale = scale;
+  a.shift = shift;
+  a.y = (float*)y;
+  a.ybs = y_bstride;
+  a.cin = cin;
+  a.cout = cout;
+  a.D = D;
+  a.H = H;
+  a.W = W;
+  LEA_CHECK_ARG(a.x && a.wp && a.y, "lea_conv3d_bnrelu_wino_down2: null pointer");
+  LEA_CHECK_ARG((scale == nullptr) == (shift == nullptr),
+                "lea_conv3d_bnrelu_wino_down2: scale/shift must both be set or both NULL");
+  LEA_CHECK_ARG(B > 0 && cin > 0 && cout > 0 && D > 0 && H > 0 && W > 0,
+                "lea_conv3d_bnrelu_wino_down2: bad shape B=%d cin=%d cout=%d D=%d H=%d W=%d", B, cin, cout, D, H, W);
+  if (flags & (LEA_RESIDUAL | LEA_PAIR_SUM)) {
+    set_error("lea_conv3d_bnrelu_wino_down2: LEA_RESIDUAL / LEA_PAIR_SUM are not supported with the "
+              "down-sampling epilogue");
+    return LEA_E_UNSUPPORTED;
+  }
+  LEA_CHECK_FLAGS(flags, LEA_RELU, "lea_conv3d_bnrelu_wino_down2");
+  a.flags = flags;
+  LEA_CHECK_ARG(D % 2 == 0 && H % 2 == 0 && W % 4 == 0,
+                "lea_conv3d_bnrelu_wino_down2: D and H must be even and W %% 4 == 0 (D=%d H=%d W=%d)", D, H, W);
+  LEA_CHECK_ARG(cin % wino::CIN_B == 0, "lea_conv3d_bnrelu_wino_down2: cin %d must be a multiple of %d", cin,
+                wino::CIN_B);
+  LEA_CHECK_ARG(a.x != a.y, "lea_conv3d_bnrelu_wino_down2: input aliases output");
+  if (dtype != LEA_F32) {
+    set_error("lea_conv3d_bnrelu_wino_down2: dtype %d unsupported", dtype);
+    return LEA_E_UNSUPPORTED;
+  }
+  // float2 stores through 32-bit byte offsets of a cout block of the L1 tensor
+  LEA_CHECK_ARG(((uintptr_t)y & 15) == 0 && y_bstride % 4 == 0,
+                "lea_conv3d_bnrelu_wino_down2: y needs 16-byte alignment");
+  wino::Plan2 q;
+  if (!wino::down2_plan(B, cin, cout, D, H, W, &a, &q)) {
+    set_error("lea_conv3d_bnrelu_wino_down2: the planner does not put B=%d cin=%d cout=%d D=%d H=%d W=%d on "
+              "the F(4,3) x F(4,3) tile (or its settings / the operands' alignment rule it out)",
+              B, cin, cout, D, H, W);
+    return LEA_E_UNSUPPORTED;
+  }
+  a.rd = axis_ratio(D, D / 2, 1);
+  a.rh = axis_ratio(H, H / 2, 1);
+  a.rw = axis_ratio(W, W / 2, 1);
+  a.uoff = wino::l44_offset(cout, cin);
+  return wino::run44(a, B, q.spw, as_stream(stream), true);
+}

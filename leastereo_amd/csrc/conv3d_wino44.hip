@@ -54,6 +54,7 @@ constexpr int GS = 40, XHS = 20, TRS = 320, TCS = 1284, TS = 4 * TCS;
 constexpr int KGL = 28;                        // per-lane weights per (cout, channel): [kh][kd][x 3] + pad
 constexpr int KGU = 56;                        // UPRE: U = G_D' G_W' g, [kh][x 3][e 6] + pad
 constexpr int NST = 8;                         // buffer stores per epilogue and lane
+constexpr int NSTD = 2;                        // ... of the down-sampling epilogue (DOWN)
 static_assert(CB1 % 64 == 3 && CB2 % 64 == 33 && CB3 % 64 == 35, "V-pass bank map");
 static_assert(BLK16 <= 4 * 64 && 4 * 256 <= CB1 - CB0, "whole pieces per channel region");
 static_assert(TRS % 64 == 0 && TCS % 8 == 4 && GS % 8 == 0 && XHS % 4 == 0 && TRS >= Q * GS && TCS >= RH * TRS,
@@ -160,8 +161,24 @@ __device__ __forceinline__ void at6(const float a0, const float a1, const float 
 // second step's MFMAs; 2 = as 0 without iglp_opt; 3 = the V-pass after all MFMAs.  (Measured
 // and dropped: the V-pass issued first, +4 %; an explicit one-MFMA / three-VALU
 // sched_group_barrier interleave, +10 %.)
-template <bool UPRE, int SCHED>
-__global__ __launch_bounds__(256, 2) void conv3d_wino44_kernel(const ConvArgs a) {
+// DOWN (lea_conv3d_bnrelu_wino_down2): the epilogue writes the trilinear (align_corners)
+// resample of the layer's output to (D/2, H/2, W/2) instead of the output itself -- for in ==
+// 2 out every L1 voxel reads one aligned 2 x 2 x 2 block (both source indices of output o in
+// {2o, 2o + 1}), and a lane holds the W and D pairs of its 4 x 4 outputs, the other row of the
+// tile (TH = 2, h0 even) sits in lane ^ 8.  trilerp's expression tree (common.h: W innermost,
+// then H, then D, contraction off) with axis_index's own (i0, i1, l0, l1): bit-identical to
+// resample3d_* of the plain kernel's output.  Lane row pr stores L1 plane d0 / 2 + pr: one
+// float2 per cout, NSTD stores per epilogue.  a.y is [B][cout][D/2][H/2][W/2] then.
+__device__ __forceinline__ float lerp44(float l0, float v0, float l1, float v1) {
+#pragma clang fp contract(off)
+  return l0 * v0 + l1 * v1;
+}
+__device__ __forceinline__ void buf_store2(__amdgpu_buffer_rsrc_t rs, unsigned off, f32x2 v) {
+  __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_t, v), rs, off, 0, 0);
+}
+
+template <bool UPRE, int SCHED, bool DOWN>
+__device__ __forceinline__ void conv3d_wino44_body(const ConvArgs& a) {
   using namespace w44;
   constexpr int NX = 3, NE = 6;  // this wave's W points x the D points
   __shared__ __attribute__((aligned(16))) float smem[2 * XS + 2 * TS];
@@ -338,7 +355,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_wino44_kernel(const ConvArgs a)
   const int w = w0 + F * pq;
   const int h = h0 + pr;
   const int nco = min(32, a.cout - co0);
-  const __amdgpu_buffer_rsrc_t yrs = block_rsrc(a.y + (long long)b * a.ybs + (long long)co0 * DHW, nco * DHW * 4);
+  const int D2 = a.D / 2, H2 = a.H / 2, W2 = a.W / 2;  // DOWN: the stored volume
+  const long long YV = DOWN ? (long long)D2 * H2 * W2 : DHW;
+  const __amdgpu_buffer_rsrc_t yrs = block_rsrc(a.y + (long long)b * a.ybs + (long long)co0 * YV, nco * YV * 4);
   const __amdgpu_buffer_rsrc_t rrs =
       block_rsrc((resid ? a.res : a.y) + (long long)b * (resid ? a.rbs : a.ybs) + (long long)co0 * DHW, nco * DHW * 4);
   // the epilogue body for x-half XH (a compile-time constant: every register index static)
@@ -388,6 +407,61 @@ __global__ __launch_bounds__(256, 2) void conv3d_wino44_kernel(const ConvArgs a)
         mine[0][3 * (1 - XH) + x][e] = rcv[(x * 6 + e) * 2];
         mine[1][3 * (1 - XH) + x][e] = rcv[(x * 6 + e) * 2 + 1];
       }
+    if constexpr (DOWN) {
+      Axis aw[2];
+#pragma unroll
+      for (int c = 0; c < 2; ++c) aw[c] = axis_index(a.rw, w / 2 + c, a.W, W2, 1);
+      const Axis ah = axis_index(a.rh, h0 / 2, a.H, H2, 1);
+      const int dl = d0 / 2 + pr;  // this lane's L1 plane: full planes d0 + 2 pr + {0, 1}
+      const Axis ad = axis_index(a.rd, dl, a.D, D2, 1);
+      const bool ok = h0 < a.H && w < a.W && dl < D2;
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        float n[NE][F];  // A_W^T per D point
+#pragma unroll
+        for (int e = 0; e < NE; ++e)
+          at6(mine[r][0][e], mine[r][1][e], mine[r][2][e], mine[r][3][e], mine[r][4][e], mine[r][5][e], n[e]);
+        float yd[F][TD];  // A_D^T per W output
+#pragma unroll
+        for (int j = 0; j < F; ++j) at6(n[0][j], n[1][j], n[2][j], n[3][j], n[4][j], n[5][j], yd[j]);
+        float wv[2][TD];  // W-lerped: [L1 column][plane]
+#pragma unroll
+        for (int t = 0; t < TD; ++t) {
+          float y[F];
+#pragma unroll
+          for (int j = 0; j < F; ++j) {
+            float v = yd[j][t] * sc[r] + sh[r];
+            if (relu) v = fmaxf(v, 0.f);
+            y[j] = v;
+          }
+#pragma unroll
+          for (int c = 0; c < 2; ++c)
+            wv[c][t] = lerp44(aw[c].l0, (aw[c].i0 & 1) ? y[2 * c + 1] : y[2 * c], aw[c].l1,
+                              (aw[c].i1 & 1) ? y[2 * c + 1] : y[2 * c]);
+        }
+        f32x2 o2;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+          float hv[2];  // H-lerped at this lane's two planes
+#pragma unroll
+          for (int k = 0; k < 2; ++k) {
+            // the partner row's value at MY plane 2 pr + k: it sends its planes 2 (1 - its pr) + k
+            const float snd = pr ? wv[c][k] : wv[c][2 + k];
+            const float oth = __shfl_xor(snd, 8);
+            const float own = pr ? wv[c][2 + k] : wv[c][k];
+            const float row0 = pr ? oth : own, row1 = pr ? own : oth;  // rows h0, h0 + 1
+            hv[k] = lerp44(ah.l0, (ah.i0 & 1) ? row1 : row0, ah.l1, (ah.i1 & 1) ? row1 : row0);
+          }
+          o2[c] = lerp44(ad.l0, (ad.i0 & 1) ? hv[1] : hv[0], ad.l1, (ad.i1 & 1) ? hv[1] : hv[0]);
+        }
+        const int cr = 16 * wc + 4 * ci + 2 * XH + r;
+        const unsigned offd = (ok && cr < nco)
+                                  ? (unsigned)(cr * YV + ((long long)dl * H2 + h0 / 2) * W2 + w / 2) * 4u
+                                  : kEpiOob;
+        buf_store2(yrs, offd, o2);
+      }
+      return;
+    }
     const bool lv = h < a.H && w < a.W;
     unsigned off[2][TD];
 #pragma unroll
@@ -445,7 +519,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_wino44_kernel(const ConvArgs a)
     int hch = min(2, nitems - 1) % nchunks, hqd = min(2, nitems - 1) / nchunks;
     for (int it = 0; it < nitems; ++it) {
       if (after_epi)
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NST) : "memory");
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DOWN ? NSTD : NST) : "memory");
       else
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
@@ -548,6 +622,14 @@ __global__ __launch_bounds__(256, 2) void conv3d_wino44_kernel(const ConvArgs a)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+template <bool UPRE, int SCHED>
+__global__ __launch_bounds__(256, 2) void conv3d_wino44_kernel(const ConvArgs a) {
+  conv3d_wino44_body<UPRE, SCHED, false>(a);
+}
+__global__ __launch_bounds__(256, 2) void conv3d_wino44_down2_kernel(const ConvArgs a) {
+  conv3d_wino44_body<false, 0, true>(a);
+}
+
 // lea_conv3d_wino44_set (r06 default 1: -9.5 % on its layers, profiles/r06_w44_ab.txt; 2 since v45,
 // after the LDS-conflict fixes: the L0 8 -> 24 group 275.6 -> 259.7 us, profiles/r06_w44_modes_ab.txt)
 int g_w44 = 2;
@@ -555,7 +637,7 @@ int g_w44u = 0;  // lea_conv3d_wino44_set_upre
 int g_w44s = 0;  // lea_conv3d_wino44_set_sched
 int g_w44g = -1;  // lea_conv3d_wino44_set_group (-1: auto)
 
-int run44(ConvArgs a, int B, int spw, hipStream_t st) {
+int run44(ConvArgs a, int B, int spw, hipStream_t st, bool down) {
   a.ncob = (a.cout + 31) / 32;
   a.tiles_w = (a.W + w44::TW - 1) / w44::TW;
   a.ntiles = a.tiles_w * ((a.H + w44::TH - 1) / w44::TH);
@@ -570,6 +652,10 @@ int run44(ConvArgs a, int B, int spw, hipStream_t st) {
   // r06_w44_group_ab.txt)
   a.grp = g_w44g >= 0 ? g_w44g : (n_ >= 2048 ? 16 : 0);
   const dim3 grid((unsigned)n_);
+  if (down) {  // (the host entry checked: the plain form's default instantiation)
+    conv3d_wino44_down2_kernel<<<grid, 256, 0, st>>>(a);
+    return launch_status("lea_conv3d(wino44 down2)");
+  }
   if (g_w44u)
     conv3d_wino44_kernel<true, 0><<<grid, 256, 0, st>>>(a);
   else if (g_w44s == 1)

@@ -43,6 +43,11 @@ struct Args {
   int cout, D, H, W, nseg, ncob;
   int nds, dchunk;  // D split into nds runs of dchunk planes (one workgroup each)
   unsigned flags;
+  // the down-sampling variant: y2 [B][cout][D/2][H/2][W/2] = trilinear (align_corners) resample
+  // of y, the axis ratios from the host's axis_ratio
+  float* y2;
+  long long y2bs;
+  float rd, rh, rw;
 };
 
 // one workgroup walks every plane unless the LDS sums do not fit: splitting D re-stages
@@ -89,7 +94,8 @@ struct Tile {
   long long HW;
 };
 
-__device__ __forceinline__ Tile tile_of(const Args& a) {
+// (rows: the workgroups along H -- a.H, or a.H / 2 row pairs in the down-sampling variant)
+__device__ __forceinline__ Tile tile_of(const Args& a, int rows) {
   Tile t;
   t.D = a.D;
   t.H = a.H;
@@ -101,8 +107,8 @@ __device__ __forceinline__ Tile tile_of(const Args& a) {
   blk /= a.nseg;
   const int ds = blk % a.nds;
   blk /= a.nds;
-  t.h = blk % a.H;
-  blk /= a.H;
+  t.h = blk % rows;
+  blk /= rows;
   t.cob = blk % a.ncob;
   t.b = blk / a.ncob;
   // planes [d0, d1): u = w - d spans [w0 - d0 - dchunk + 1, w0 + WS - 1 - d0]
@@ -118,23 +124,13 @@ __device__ __forceinline__ Tile tile_of(const Args& a) {
 // thread = (cout, 4 columns): one float4 store per plane
 constexpr int OB = 16;
 
-__global__ __launch_bounds__(kThreads) void cv_stem_f32_kernel(const Args a) {
-  extern __shared__ float rs[];  // [OB][NT] sums, then [OB][dchunk] edge corrections
-  const Tile T = tile_of(a);
+// one row's right-half sums rs [OB][NT] and edge corrections corr [OB][dchunk] (rkh: the right
+// maps at that row)
+__device__ __forceinline__ void stage_row_f32(const Args& a, const Tile& T, const float* rkh, float* rs,
+                                              float* corr) {
   const int D = T.D, W = T.W, NU = T.NU, NT = T.NT, d0 = T.d0, d1 = T.d1, w0 = T.w0;
   const long long HW = T.HW;
-  if (a.flags & 0x100u) {  // probe: stores only
-    const int ol = threadIdx.x >> 4, o = T.cob * OB + ol, w = w0 + 4 * (threadIdx.x & 15);
-    if (o >= a.cout || w >= W) return;
-    float* yp = static_cast<float*>(a.y) + T.b * a.ybs + (long long)o * D * HW + (long long)T.h * W + w;
-    for (int d = d0; d < d1; ++d) *reinterpret_cast<float4*>(yp + (long long)d * HW) = make_float4(d, 0.f, 0.f, 1.f);
-    return;
-  }
-  const float* lk = static_cast<const float*>(a.lk) + T.b * a.lbs;
-  const float* rkh = static_cast<const float*>(a.rk) + T.b * a.rbs + (long long)T.h * W;
-  float* corr = rs + OB * NT;
   const int tid = threadIdx.x;
-
   const int NE = OB * NT;
   for (int e0 = 0; e0 < NE; e0 += 4 * kThreads) {
     float q[4][3];
@@ -179,6 +175,25 @@ __global__ __launch_bounds__(kThreads) void cv_stem_f32_kernel(const Args a) {
       corr[ol * a.dchunk + (d - d0)] = s;
     }
   }
+}
+
+__global__ __launch_bounds__(kThreads) void cv_stem_f32_kernel(const Args a) {
+  extern __shared__ float rs[];  // [OB][NT] sums, then [OB][dchunk] edge corrections
+  const Tile T = tile_of(a, a.H);
+  const int D = T.D, W = T.W, NU = T.NU, NT = T.NT, d0 = T.d0, d1 = T.d1, w0 = T.w0;
+  const long long HW = T.HW;
+  if (a.flags & 0x100u) {  // probe: stores only
+    const int ol = threadIdx.x >> 4, o = T.cob * OB + ol, w = w0 + 4 * (threadIdx.x & 15);
+    if (o >= a.cout || w >= W) return;
+    float* yp = static_cast<float*>(a.y) + T.b * a.ybs + (long long)o * D * HW + (long long)T.h * W + w;
+    for (int d = d0; d < d1; ++d) *reinterpret_cast<float4*>(yp + (long long)d * HW) = make_float4(d, 0.f, 0.f, 1.f);
+    return;
+  }
+  const float* lk = static_cast<const float*>(a.lk) + T.b * a.lbs;
+  const float* rkh = static_cast<const float*>(a.rk) + T.b * a.rbs + (long long)T.h * W;
+  float* corr = rs + OB * NT;
+  const int tid = threadIdx.x;
+  stage_row_f32(a, T, rkh, rs, corr);
   __syncthreads();
 
   const int ol = tid >> 4, o = T.cob * OB + ol;
@@ -273,6 +288,141 @@ __global__ __launch_bounds__(kThreads) void cv_stem_f32_kernel(const Args a) {
   }
 }
 
+// ---- f32 with a down-sampled side output: y as above plus y2 = the trilinear (align_corners)
+// resample of y to (D/2, H/2, W/2), bit-identical to resample3d_* on y (trilerp's expression
+// tree: W innermost, then H, then D, contraction off).  For in == 2 out both source indices of
+// output o are in {2o, 2o + 1}, so every y2 voxel reads one aligned 2 x 2 x 2 block of y: a
+// workgroup = (batch, 16 couts, row pair 2 hp and 2 hp + 1, 64 columns) walking every plane in
+// order, thread = (cout, 4 columns) of both rows -- two float4 stores per plane as above, and
+// per plane pair one float2 of y2.  The per-voxel arithmetic of y is cv_stem_f32_kernel's.
+__device__ __forceinline__ float lerp2(float l0, float v0, float l1, float v1) {
+#pragma clang fp contract(off)
+  return l0 * v0 + l1 * v1;
+}
+
+__global__ __launch_bounds__(kThreads) void cv_stem_f32_down2_kernel(const Args a) {
+  extern __shared__ float rs[];  // per row: [OB][NT] sums, then [OB][D] edge corrections
+  const Tile T = tile_of(a, a.H / 2);  // T.h: the row pair; nds == 1, so d0 = 0 and d1 = D
+  const int D = T.D, H = T.H, W = T.W, NU = T.NU, NT = T.NT, w0 = T.w0, hp = T.h;
+  const long long HW = T.HW;
+  const float* lk = static_cast<const float*>(a.lk) + T.b * a.lbs;
+  const float* rk = static_cast<const float*>(a.rk) + T.b * a.rbs;
+  const int rowf = OB * (NT + a.dchunk);  // staged floats per row
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int r = 0; r < 2; ++r)
+    stage_row_f32(a, T, rk + (long long)(2 * hp + r) * W, rs + r * rowf, rs + r * rowf + OB * NT);
+  __syncthreads();
+
+  const int ol = tid >> 4, o = T.cob * OB + ol;
+  const int w = w0 + 4 * (tid & 15);
+  if (o >= a.cout || w >= W) return;  // W % 4 == 0 (host)
+  const bool band = w - (D - 1) <= 1;
+  // per row: the left half of the interior planes (gl, bl as above) and of planes 0 and D - 1
+  float gl[2][4], bl[2][4][4], lf[2][4], ll[2][4];
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    float lkv[3][3][4];
+#pragma unroll
+    for (int kd = 0; kd < 3; ++kd)
+#pragma unroll
+      for (int t = 0; t < 3; ++t) {
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (t == 0 || band)
+          v = *reinterpret_cast<const float4*>(lk + (long long)((3 * kd + t) * a.cout + o) * HW +
+                                               (long long)(2 * hp + r) * W + w);
+        lkv[kd][t][0] = v.x;
+        lkv[kd][t][1] = v.y;
+        lkv[kd][t][2] = v.z;
+        lkv[kd][t][3] = v.w;
+      }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float l3[3][3];
+#pragma unroll
+      for (int kd = 0; kd < 3; ++kd)
+#pragma unroll
+        for (int t = 0; t < 3; ++t) l3[kd][t] = lkv[kd][t][j];
+      gl[r][j] = lkv[0][0][j] + lkv[1][0][j] + lkv[2][0][j];
+#pragma unroll
+      for (int m = 0; m < 4; ++m) bl[r][m][j] = left_sum(l3, 1, m - 2, D);
+      lf[r][j] = left_sum(l3, 0, w + j, D);
+      ll[r][j] = left_sum(l3, D - 1, w + j - (D - 1), D);
+    }
+  }
+  const float sc = a.scale ? a.scale[o] : 1.f, sh = a.scale ? a.shift[o] : 0.f;
+  const float lo = (a.flags & LEA_RELU) ? 0.f : -INFINITY;  // ReLU as a floor
+  const int jedge = W - 1 - w;
+  const bool far = w0 - (D - 2) >= 2;  // every lane has u >= 2 on every interior plane
+  float* yp = static_cast<float*>(a.y) + T.b * a.ybs + (long long)o * D * HW + (long long)(2 * hp) * W + w;
+  const int D2 = D / 2, H2 = H / 2, W2 = W / 2;
+  float* y2p = a.y2 + T.b * a.y2bs + ((long long)o * D2 * H2 + hp) * W2 + w / 2;
+  // the lane's two L1 columns w / 2 + c read columns w + 2 c + {0, 1}; its L1 row hp rows 2 hp + {0, 1}
+  Axis aw[2];
+#pragma unroll
+  for (int c = 0; c < 2; ++c) aw[c] = axis_index(a.rw, w / 2 + c, W, W2, 1);
+  const Axis ah = axis_index(a.rh, hp, H, H2, 1);
+  const bool h0odd = ah.i0 & 1, h1odd = ah.i1 & 1;
+
+  float ev[2] = {0.f, 0.f};  // the even plane's H-lerped values until the odd plane arrives
+  for (int d = 0; d < D; ++d) {
+    float out[2][4];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const float* r0 = rs + r * rowf + ol * NT;
+      const float c = rs[r * rowf + OB * NT + ol * a.dchunk + d];
+      float pre[4];
+      if (d == 0 || d == D - 1) {
+        const int pb = (d == 0 ? NU : NU + WS) + (w - w0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) pre[j] = (d == 0 ? lf[r][j] : ll[r][j]) + r0[pb + j] - (j == jedge ? c : 0.f);
+      } else {
+        const int iu = w - d - T.u0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int u = w + j - d;
+          float l = (far || u >= 2) ? gl[r][j] : 0.f;
+          if (!far) {
+#pragma unroll
+            for (int m = 0; m < 4; ++m) l = u == m - 2 ? bl[r][m][j] : l;
+          }
+          pre[j] = l + r0[iu + j] - (j == jedge ? c : 0.f);
+        }
+      }
+      float4 o4;
+      float* po = reinterpret_cast<float*>(&o4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        po[j] = fmaxf(pre[j] * sc + sh, lo);
+        out[r][j] = po[j];
+      }
+      *reinterpret_cast<float4*>(yp + (long long)d * HW + r * W) = o4;
+    }
+    float hv[2];
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      float wv[2];
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        const float v0 = (aw[c].i0 & 1) ? out[r][2 * c + 1] : out[r][2 * c];
+        const float v1 = (aw[c].i1 & 1) ? out[r][2 * c + 1] : out[r][2 * c];
+        wv[r] = lerp2(aw[c].l0, v0, aw[c].l1, v1);
+      }
+      hv[c] = lerp2(ah.l0, h0odd ? wv[1] : wv[0], ah.l1, h1odd ? wv[1] : wv[0]);
+    }
+    if (!(d & 1)) {
+      ev[0] = hv[0];
+      ev[1] = hv[1];
+    } else {
+      const Axis ad = axis_index(a.rd, d >> 1, D, D2, 1);
+      float2 o2;
+      o2.x = lerp2(ad.l0, (ad.i0 & 1) ? hv[0] : ev[0], ad.l1, (ad.i1 & 1) ? hv[0] : ev[0]);
+      o2.y = lerp2(ad.l0, (ad.i0 & 1) ? hv[1] : ev[1], ad.l1, (ad.i1 & 1) ? hv[1] : ev[1]);
+      *reinterpret_cast<float2*>(y2p + (long long)(d >> 1) * H2 * W2) = o2;
+    }
+  }
+}
+
 // ---- bf16 c8: maps and output in the c8 layout ([B][C/8][D][H][W][8]); workgroup =
 // (batch, 32 couts, row h, 64 columns), thread = (8-cout block, column): one 16-byte
 // word per plane.  LDS sums [4 blocks][2 halves][NT][4] f32 (a wave reads one block's
@@ -282,7 +432,7 @@ constexpr int OB8 = 32;
 
 __global__ __launch_bounds__(kThreads) void cv_stem_c8_kernel(const Args a) {
   extern __shared__ __attribute__((aligned(16))) float rs8[];
-  const Tile T = tile_of(a);
+  const Tile T = tile_of(a, a.H);
   const int D = T.D, W = T.W, NU = T.NU, NT = T.NT, d0 = T.d0, d1 = T.d1, w0 = T.w0;
   const long long HW = T.HW;
   if (a.flags & 0x100u) {  // probe: stores only
@@ -555,4 +705,69 @@ extern "C" int lea_cv_stem_combine(const void* lmaps, int64_t l_bstride, const v
   else
     cvs::cv_stem_c8_kernel<<<dim3((unsigned)nblk), cvs::kThreads, lds, as_stream(stream)>>>(a);
   return launch_status("lea_cv_stem_combine");
+}
+
+// the down-sampling variant's shapes: f32, even D3 / H, W % 4 == 0, the planes of a row pair
+// in one workgroup's LDS (nds == 1 of the plain kernel as well)
+static bool cv_stem_down2_ok(int cout, int D3, int H, int W, int dtype) {
+  if (dtype != LEA_F32 || cout <= 0 || D3 < 2 || H < 2 || W < 4 || D3 % 2 || H % 2 || W % 4) return false;
+  return (size_t)2 * cvs::OB * (2 * D3 + 3 * cvs::WS - 1) * sizeof(float) <= (size_t)cvs::kLdsBytes;
+}
+
+extern "C" int lea_cv_stem_down2_supported(int cout, int D3, int H, int W, int dtype) {
+  return cv_stem_down2_ok(cout, D3, H, W, dtype) ? 1 : 0;
+}
+
+extern "C" int lea_cv_stem_combine_down2(const void* lmaps, int64_t l_bstride, const void* rmaps,
+                                         int64_t r_bstride, const float* scale, const float* shift,
+                                         void* y, int64_t y_bstride, void* y2, int64_t y2_bstride, int B,
+                                         int cout, int D3, int H, int W, unsigned flags, int dtype,
+                                         void* stream) {
+  clear_error();
+  LEA_CHECK_ARG(lmaps && rmaps && y && y2, "lea_cv_stem_combine_down2: null pointer");
+  LEA_CHECK_ARG((scale == nullptr) == (shift == nullptr),
+                "lea_cv_stem_combine_down2: scale/shift must both be set or both NULL");
+  LEA_CHECK_ARG(B > 0 && cout > 0 && D3 >= 2 && H > 0 && W > 0,
+                "lea_cv_stem_combine_down2: bad shape B=%d cout=%d D3=%d H=%d W=%d", B, cout, D3, H, W);
+  LEA_CHECK_FLAGS(flags, LEA_RELU, "lea_cv_stem_combine_down2");
+  if (!cv_stem_down2_ok(cout, D3, H, W, dtype)) {
+    set_error("lea_cv_stem_combine_down2: needs f32, even D3 and H, W %% 4 == 0 and unsplit planes "
+              "(D3=%d H=%d W=%d dtype=%d)", D3, H, W, dtype);
+    return LEA_E_UNSUPPORTED;
+  }
+  LEA_CHECK_ARG((long long)cout * D3 * H * W < (1LL << 40), "lea_cv_stem_combine_down2: volume too large");
+  LEA_CHECK_ARG((uintptr_t)y % 16 == 0 && y_bstride % 4 == 0 && (uintptr_t)y2 % 8 == 0 && y2_bstride % 2 == 0,
+                "lea_cv_stem_combine_down2: y needs 16-byte, y2 8-byte alignment");
+  const size_t ybytes = (size_t)((long long)(B - 1) * y_bstride + (long long)cout * D3 * H * W) * sizeof(float);
+  const size_t y2bytes =
+      (size_t)((long long)(B - 1) * y2_bstride + (long long)cout * (D3 / 2) * (H / 2) * (W / 2)) * sizeof(float);
+  LEA_CHECK_ARG(!spans_overlap(y, ybytes, y2, y2bytes), "lea_cv_stem_combine_down2: y and y2 overlap");
+  cvs::Args a{};
+  a.lk = lmaps;
+  a.lbs = l_bstride;
+  a.rk = rmaps;
+  a.rbs = r_bstride;
+  a.scale = scale;
+  a.shift = shift;
+  a.y = y;
+  a.ybs = y_bstride;
+  a.y2 = static_cast<float*>(y2);
+  a.y2bs = y2_bstride;
+  a.cout = cout;
+  a.D = D3;
+  a.H = H;
+  a.W = W;
+  a.flags = flags & LEA_RELU;
+  a.rd = axis_ratio(D3, D3 / 2, 1);
+  a.rh = axis_ratio(H, H / 2, 1);
+  a.rw = axis_ratio(W, W / 2, 1);
+  a.nseg = (W + cvs::WS - 1) / cvs::WS;
+  a.dchunk = D3;
+  a.nds = 1;
+  a.ncob = (cout + cvs::OB - 1) / cvs::OB;
+  const long long nblk = (long long)B * a.ncob * (H / 2) * a.nseg;
+  LEA_CHECK_ARG(nblk < (1LL << 31), "lea_cv_stem_combine_down2: grid too large");
+  const size_t lds = (size_t)2 * cvs::OB * (2 * D3 + 3 * cvs::WS - 1) * sizeof(float);
+  cvs::cv_stem_f32_down2_kernel<<<dim3((unsigned)nblk), cvs::kThreads, lds, as_stream(stream)>>>(a);
+  return launch_status("lea_cv_stem_combine_down2");
 }

@@ -158,7 +158,7 @@ __global__ void pack_wino44_lane_kernel(const float* __restrict__ w, float* __re
                                         int nchunks, long long total);
 __global__ void pack_wino44_lane_u_kernel(const float* __restrict__ w, float* __restrict__ out, int cout, int cin,
                                           int nchunks, long long total);
-int run44(ConvArgs a, int B, int spw, hipStream_t st);
+int run44(ConvArgs a, int B, int spw, hipStream_t st, bool down = false);  // down: conv3d_wino44_down2_kernel
 const char* name2(const Plan2& p, bool cv);
 
 // F(2,3) x F(2,3) tile for the 16-cout layers (conv3d_wino22.hip): the U section the packer

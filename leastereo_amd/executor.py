@@ -309,15 +309,22 @@ class CellGraphExecutor:
     def _resample(x, size):
         return kernels.resample_trilinear(x, size)
 
-    def cell(self, i, s0, s1):
+    def cell(self, i, s0, s1, down=None):
         """Cell.forward (skip_model_3d.py:41-75 / new_model_2d.py:41-75).  The level
         change of s1 (:44-48) and the size match of s0 (:49-51) are fused into the
-        1x1 preprocess convs (:52-53) that consume them."""
+        1x1 preprocess convs (:52-53) that consume them.  ``down`` = (s0, s1) already at
+        this cell's size (either may be None), written by their producers' down-sampling
+        epilogues: the preprocess convs then run at this level on them."""
         cell = self.m.cells[i]
         c = cell.c_out
+        if down is not None and down[0] is not None:
+            s0 = down[0]
+        s1_down = down is not None and down[1] is not None
+        if s1_down:
+            s1 = down[1]
         prev_input = s1
         size = self._volume(s1)
-        if cell.downup_sample != 0:
+        if cell.downup_sample != 0 and not s1_down:
             sc = 0.5 if cell.downup_sample < 0 else 2
             # the D axis of a 2D map stays 1 (bilinear on H, W only)
             size = tuple(n if (cell.dims == 2 and ax == 0) else scale_dimension(n, sc)
@@ -420,6 +427,12 @@ class MatchingExecutor(CellGraphExecutor):
     # the matching cells' steps as LEA_PAIR_SUM launches (LEASTEREO_PAIR_STEPS=0: the s1 group
     # + accumulating launches); the f32 pair runs on the Winograd F(2,3) x F(2,3) tile
     PAIR_STEPS = WINOGRAD and os.environ.get("LEASTEREO_PAIR_STEPS", "0") != "0"
+    # the stems write cell 0's level themselves (the L0 -> L1 down-sampling as an epilogue): stem0's
+    # factored kernel as a side output (lea_cv_stem_combine_down2), stem1 instead of its
+    # full-resolution output (lea_conv3d_bnrelu_wino_down2), so cell 0's two 1x1 preprocess convs run
+    # at L1 instead of each re-reading a whole L0 volume; LEASTEREO_FUSED_DOWN=0: the separate
+    # resampling launches
+    FUSED_DOWN = os.environ.get("LEASTEREO_FUSED_DOWN", "1") != "0"
 
     def run(self, x):
         """newMatching.forward (skip_model_3d.py:140-174): [B,64,D3,H3,W3] -> [B,1,D3,H3,W3]."""
@@ -433,7 +446,7 @@ class MatchingExecutor(CellGraphExecutor):
             raise ValueError(f"stem0 expects {p.cin} cost-volume channels, got 2*{fl.shape[1]}")
         d3 = int(maxdisp / 3)
         if self.cv is not None and kernels.cv_stem_supported(p.cout, d3, fl.shape[3], False):
-            return self._from_stem0(self._cv_stem(fl.unsqueeze(2), fr.unsqueeze(2), d3))
+            return self._from_stem0(*self._cv_stem(fl.unsqueeze(2), fr.unsqueeze(2), d3))
         if p.wino is not None and kernels.wino_preferred(fl.shape[0], p.cout, p.cin, int(maxdisp / 3),
                                                          *fl.shape[2:4]):
             stem0 = kernels.conv3d_bnrelu_costvolume_wino(fl, fr, maxdisp, p.wino, p.cout, p.scale,
@@ -449,22 +462,44 @@ class MatchingExecutor(CellGraphExecutor):
         p, (wl, wr) = self.p["stem0"], self.cv
         lm = kernels.conv2d_bnrelu(fl5, wl, 9 * p.cout, None, None, relu=False)
         rm = kernels.conv2d_bnrelu(fr5, wr, 6 * p.cout, None, None, relu=False)
-        return kernels.cv_stem_combine(lm, rm, p.cout, d3, p.scale, p.shift, p.relu)
+        if self._cell0_takes_down((d3,) + tuple(lm.shape[3:5])) and kernels.cv_stem_down2_supported(lm, p.cout, d3):
+            # (stem0, stem0 at cell 0's level): the side output of the same launch
+            return kernels.cv_stem_combine_down2(lm, rm, p.cout, d3, p.scale, p.shift, p.relu)
+        return kernels.cv_stem_combine(lm, rm, p.cout, d3, p.scale, p.shift, p.relu), None
+
+    def _cell0_takes_down(self, vol):
+        """Cell 0 reads the stems one level down, at exactly half of ``vol`` (an aligned
+        2 x 2 x 2 reduction): their producers may write that level themselves.  Never with a
+        tap installed (the per-stage checks see today's launches) nor in the c8 layout."""
+        cells = self.m.cells
+        return (self.FUSED_DOWN and self.tap is None and not isinstance(self, _C8Layout) and len(cells) > 0
+                and cells[0].downup_sample < 0 and cells[0].dims == 3
+                and all(n % 2 == 0 and scale_dimension(n, 0.5) == n // 2 for n in vol))
 
     def _cv_stem_pack(self, wl, wr):
         return kernels.pack_conv2d_weight(wl), kernels.pack_conv2d_weight(wr)
 
-    def _from_stem0(self, stem0):
-        out = self._matching_body(stem0)
+    def _from_stem0(self, stem0, stem0_down=None):
+        out = self._matching_body(stem0, stem0_down)
         if self.tap is not None:  # the head's output is f32 NCDHW in every executor
             self.tap("matching", out.detach().clone())
         return out
 
-    def _matching_body(self, stem0):
+    def _matching_body(self, stem0, stem0_down=None):
         d, h, w = self._volume(stem0)
         self._emit("stem0", stem0)
-        stem1 = self.conv("stem1", stem0)
-        self._emit("stem1", stem1)
+        stem1 = stem1_down = None
+        p1 = self.p["stem1"]
+        if ("cells.0.share" in self.p and self._cell0_takes_down((d, h, w)) and p1.wino is not None
+                and kernels.wino_preferred(stem0.shape[0], p1.cout, p1.cin, d, h, w)
+                and kernels.conv3d_wino_down2_supported(stem0, p1.cout)):
+            # stem1's only readers are cell 0's s1 and cell 1's s0 (the share memo), both one
+            # level down: its epilogue writes that level and the full-resolution output never
+            # exists (lea_conv3d_bnrelu_wino_down2)
+            stem1_down = kernels.conv3d_bnrelu_wino_down2(stem0, p1.wino, p1.cout, p1.scale, p1.shift, p1.relu)
+        else:
+            stem1 = self.conv("stem1", stem0)
+            self._emit("stem1", stem1)
         outs = []
         prev = (stem0, stem1)
         n = len(self.m.cells)
@@ -477,7 +512,7 @@ class MatchingExecutor(CellGraphExecutor):
                 fused = self.conv("conv2", outs[4][1], x2=outs[8][1])
                 self._emit("conv2", fused)
                 prev = (outs[8][0], fused)
-            o = self.cell(i, prev[0], prev[1])
+            o = self.cell(i, prev[0], prev[1], down=(stem0_down, stem1_down) if i == 0 else None)
             self._emit(f"cell{i}", o[1])
             outs.append(o)
             prev = o

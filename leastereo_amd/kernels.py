@@ -1264,6 +1264,41 @@ def cv_stem_combine(lmaps: torch.Tensor, rmaps: torch.Tensor, cout: int, d3: int
     return out
 
 
+def cv_stem_down2_supported(lmaps: torch.Tensor, cout: int, d3: int) -> bool:
+    """Whether cv_stem_combine_down2 takes these maps: f32 NCDHW maps on the device and a shape
+    lea_cv_stem_down2_supported accepts (even D3 / H, W % 4 == 0, unsplit planes)."""
+    if not lmaps.is_cuda or lmaps.dtype != torch.float32 or lmaps.dim() != 5:
+        return False
+    return bool(_lib.load().lea_cv_stem_down2_supported(cout, d3, lmaps.shape[3], lmaps.shape[4], LEA_F32))
+
+
+def cv_stem_combine_down2(lmaps: torch.Tensor, rmaps: torch.Tensor, cout: int, d3: int,
+                          scale: torch.Tensor | None, shift: torch.Tensor | None, relu: bool = True):
+    """``cv_stem_combine`` (f32) with stem0's output also at the next level: returns (y, y2),
+    y2 [B, cout, D3/2, H/2, W/2] = resample_trilinear(y, (D3/2, H/2, W/2)) bit for bit, written
+    by the same launch from the row pair it holds in registers (no second pass over y)."""
+    _require_cuda(lmaps, rmaps, scale, shift)
+    b, _, _, h, w = lmaps.shape
+    lbs, rbs = _check_volume_view(lmaps, "lmaps"), _check_volume_view(rmaps, "rmaps")
+    if lmaps.shape[1] != 9 * cout or rmaps.shape[1] != 6 * cout:
+        raise ValueError("cv_stem_combine_down2: map channels must be 9 / 6 x cout")
+    if tuple(rmaps.shape[0:1]) != (b,) or tuple(rmaps.shape[3:5]) != (h, w):
+        raise ValueError("cv_stem_combine_down2: left/right maps differ in batch or size")
+    out = torch.empty((b, cout, d3, h, w), device=lmaps.device, dtype=torch.float32)
+    out2 = torch.empty((b, cout, d3 // 2, h // 2, w // 2), device=lmaps.device, dtype=torch.float32)
+    # algorithmic bytes: the maps and both outputs
+    nbytes = 4.0 * (lmaps.numel() + rmaps.numel() + out.numel() + out2.numel())
+    rec = _probe_launch("cv_stem_f32_down2_kernel", 0.0, nbytes)
+    check(_lib.load().lea_cv_stem_combine_down2(
+        lmaps.data_ptr(), lbs, rmaps.data_ptr(), rbs,
+        scale.data_ptr() if scale is not None else None,
+        shift.data_ptr() if shift is not None else None, out.data_ptr(), out.stride(0),
+        out2.data_ptr(), out2.stride(0), b, cout, d3, h, w, LEA_RELU if relu else 0, LEA_F32, _stream()),
+        "lea_cv_stem_combine_down2")
+    _probe_end(rec)
+    return out, out2
+
+
 # ---- host steps either side of forward (SURVEY.md §8f rank 3) ----
 
 def standardize_crop_u8(left: torch.Tensor, right: torch.Tensor, crop_height: int, crop_width: int):
@@ -1583,6 +1618,51 @@ def conv3d_bnrelu_wino(x: torch.Tensor, packed: torch.Tensor, cout: int,
         shift.data_ptr() if shift is not None else None,
         rptr, rbs, out.data_ptr(), ybs, b, cin + cin2, cout, d, h, w, flags, LEA_F32, _stream()),
         "lea_conv3d_bnrelu_wino")
+    _probe_end(rec)
+    return out
+
+
+def wino_down2_kernel_name(b, cin, cout, d, h, w):
+    """The instantiation conv3d_bnrelu_wino_down2 launches for this shape, or None."""
+    name = _lib.load().lea_conv3d_wino_down2_kernel_name(b, cin, cout, d, h, w)
+    return name.decode() if name else None
+
+
+def conv3d_wino_down2_supported(x: torch.Tensor, cout: int) -> bool:
+    """Whether conv3d_bnrelu_wino_down2 takes this input: an f32 NCDHW device tensor (16-byte
+    aligned, whole 16-byte batch strides) of a shape the planner puts on the F(4,3) x F(4,3)
+    tile (lea_conv3d_wino_down2_supported: even D / H, W % 4 == 0)."""
+    if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 5:
+        return False
+    b, cin, d, h, w = x.shape
+    if x.data_ptr() % 16 or x.stride(0) % 4 or x.stride()[1:] != (d * h * w, h * w, w, 1):
+        return False
+    return bool(_lib.load().lea_conv3d_wino_down2_supported(b, cin, cout, d, h, w))
+
+
+def conv3d_bnrelu_wino_down2(x: torch.Tensor, packed: torch.Tensor, cout: int,
+                             scale: torch.Tensor | None, shift: torch.Tensor | None,
+                             relu: bool = True) -> torch.Tensor:
+    """resample_trilinear(conv3d_bnrelu_wino(x, ...), (D/2, H/2, W/2)) bit for bit, as one launch
+    whose epilogue down-samples (the full-resolution output is never written)."""
+    _require_cuda(x, packed, scale, shift)
+    b, cin, d, h, w = x.shape
+    xbs = _check_volume_view(x, "x")
+    out = torch.empty((b, cout, d // 2, h // 2, w // 2), device=x.device, dtype=x.dtype)
+    rec = None
+    if _probe is not None:
+        name = wino_down2_kernel_name(b, cin, cout, d, h, w) or "conv3d_wino44_down2_kernel"
+        rec = _probe_begin(b, cin, cout, d, h, w, 3, False, b * d * h * w, False, name=name,
+                           mfma_scale=wino_mfma_scale(cout, "conv3d_wino44_kernel"))  # (the same tile)
+        if rec is not None:  # the bytes really moved: input + weights + the L1 output
+            nbytes = 4.0 * (x.numel() + out.numel()) + 4.0 * cout * cin * 27
+            rec = rec[:3] + (nbytes,) + rec[4:]
+    check(_lib.load().lea_conv3d_bnrelu_wino_down2(
+        x.data_ptr(), xbs, packed.data_ptr(),
+        scale.data_ptr() if scale is not None else None,
+        shift.data_ptr() if shift is not None else None,
+        out.data_ptr(), out.stride(0), b, cin, cout, d, h, w, LEA_RELU if relu else 0, LEA_F32, _stream()),
+        "lea_conv3d_bnrelu_wino_down2")
     _probe_end(rec)
     return out
 
