@@ -594,6 +594,45 @@ int lea_conv3d_bnrelu_wino_down2(const void* x, int64_t x_bstride, const float* 
                                  const float* scale, const float* shift, void* y, int64_t y_bstride,
                                  int B, int cin, int cout, int D, int H, int W, unsigned flags, int dtype,
                                  void* stream);
+/* The same on two sources, cat(x, x2) along the channels read in place as lea_conv3d_bnrelu_wino
+ * takes it (cin2 of the cin channels come from x2; both counts multiples of 4, both sources
+ * 16-byte aligned): the matching net's conv1, whose only reader sits one level down.  The
+ * launch reports "conv3d_wino44_down2_cat_kernel"; the one-input entry and name are unchanged. */
+int lea_conv3d_wino_down2_cat_supported(int B, int cin, int cin2, int cout, int D, int H, int W);
+const char* lea_conv3d_wino_down2_cat_kernel_name(int B, int cin, int cin2, int cout, int D, int H, int W);
+int lea_conv3d_bnrelu_wino_down2_cat(const void* x, int64_t x_bstride, const void* x2, int64_t x2_bstride,
+                                     int cin2, const float* w_packed, const float* scale, const float* shift,
+                                     void* y, int64_t y_bstride, int B, int cin, int cout, int D, int H,
+                                     int W, unsigned flags, int dtype, void* stream);
+/* The depth-paired tiles (couts <= 8) with the same epilogue, for a cell state whose only reader
+ * sits one level down: besides y (NULL: not at all -- the residual is still read) the launch
+ * writes y2 [B, cout, D/2, H/2, W/2] = lea_resample3d_trilinear(ConvBR(x) [+ residual],
+ * align_corners = 1), bit for bit.  flags: LEA_RELU, LEA_RESIDUAL (residual may be y: the
+ * accumulate form).  D and H even, W % 4 == 0, cout <= 8, and the planner's depth-paired tile
+ * with the buffer-addressed epilogue (lea_conv3d_wino_dp_down2_supported: 1; aligned operands
+ * assumed), otherwise LEA_E_UNSUPPORTED and nothing is launched.  y2 16-byte aligned, no
+ * overlap with x, y or the residual.  lea_conv3d_wino_dp_down2_kernel_name: the instantiation
+ * ("conv3d_wino_dp_down2_kernel<Q, ONLY>", ONLY = y is NULL), or NULL where unsupported. */
+int lea_conv3d_wino_dp_down2_supported(int B, int cin, int cout, int D, int H, int W);
+const char* lea_conv3d_wino_dp_down2_kernel_name(int B, int cin, int cout, int D, int H, int W, int only);
+int lea_conv3d_bnrelu_wino_dp_down2(const void* x, int64_t x_bstride, const float* w_packed,
+                                    const float* scale, const float* shift, const void* residual,
+                                    int64_t r_bstride, void* y, int64_t y_bstride, void* y2,
+                                    int64_t y2_bstride, int B, int cin, int cout, int D, int H, int W,
+                                    unsigned flags, int dtype, void* stream);
+/* lea_resample3d_trilinear (align_corners = 1) with a down-sampled side output (csrc/resample.hip):
+ * besides y [B, C, Do, Ho, Wo] it writes
+ *   y2 [B, C, Do/2, Ho/2, Wo/2] = lea_resample3d_trilinear(y -> half, align_corners = 1), bit for
+ * bit and without reading y back: the level-down copy of an up-sampling cell preprocess's
+ * output.  y is bit-identical to lea_resample3d_trilinear's.  Do and Ho even, Wo % 4 == 0,
+ * Do >= Di (no down-sampling along D), rows that fit the LDS, LEA_F32
+ * (lea_resample3d_down2_supported: 1), else LEA_E_UNSUPPORTED.  y 16-byte, y2 8-byte aligned.
+ * flags: LEA_RELU. */
+int lea_resample3d_down2_supported(int Di, int Hi, int Wi, int Do, int Ho, int Wo, int dtype);
+int lea_resample3d_trilinear_down2(const void* x, int64_t x_bstride, void* y, int64_t y_bstride, void* y2,
+                                   int64_t y2_bstride, int B, int C, int Di, int Hi, int Wi, int Do, int Ho,
+                                   int Wo, const float* scale, const float* shift, unsigned flags, int dtype,
+                                   void* stream);
 
 /* ---- Matching-net stem0 over the cost volume, factored (csrc/cv_stem.hip) ----
  * Replaces retrain/LEAStereo.py:34-48 + skip_model_3d.py:141 like

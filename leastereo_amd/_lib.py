@@ -118,6 +118,17 @@ SIGNATURES = {
     "lea_conv3d_wino_down2_supported": (_i, [_i, _i, _i, _i, _i, _i]),
     "lea_conv3d_wino_down2_kernel_name": (ctypes.c_char_p, [_i, _i, _i, _i, _i, _i]),
     "lea_conv3d_bnrelu_wino_down2": (_i, [_p, _i64, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _i, _i, _u, _i, _p]),
+    "lea_conv3d_wino_down2_cat_supported": (_i, [_i, _i, _i, _i, _i, _i, _i]),
+    "lea_conv3d_wino_down2_cat_kernel_name": (ctypes.c_char_p, [_i, _i, _i, _i, _i, _i, _i]),
+    "lea_conv3d_bnrelu_wino_down2_cat": (_i, [_p, _i64, _p, _i64, _i, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _i, _i,
+                                              _u, _i, _p]),
+    "lea_conv3d_wino_dp_down2_supported": (_i, [_i, _i, _i, _i, _i, _i]),
+    "lea_conv3d_wino_dp_down2_kernel_name": (ctypes.c_char_p, [_i, _i, _i, _i, _i, _i, _i]),
+    "lea_conv3d_bnrelu_wino_dp_down2": (_i, [_p, _i64, _p, _p, _p, _p, _i64, _p, _i64, _p, _i64, _i, _i, _i, _i, _i,
+                                             _i, _u, _i, _p]),
+    "lea_resample3d_down2_supported": (_i, [_i, _i, _i, _i, _i, _i, _i]),
+    "lea_resample3d_trilinear_down2": (_i, [_p, _i64, _p, _i64, _p, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p,
+                                            _u, _i, _p]),
     "lea_conv3d_wino_set_tile_override": (_i, [_i, _i, _i]),
     "lea_conv3d_wino_set_variant": (_i, [_i]),
     "lea_conv3d_wino2_set_walk": (_i, [_i]),

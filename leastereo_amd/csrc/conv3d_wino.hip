@@ -106,16 +106,36 @@ struct Cfg {
   static_assert(2 * STAGE * 4 * 2 <= 160 * 1024, "two double-buffered workgroups per CU");
 };
 
-template <int F, int Q, int MT, int NP, int TD, bool CV, bool H16 = false, bool FENCE = false>
-__global__ __launch_bounds__(kConvThreads, 2) void conv3d_wino_kernel(const ConvArgs a) {
+// DOWN (lea_conv3d_bnrelu_wino_dp_down2; the depth-paired tile, buffer-addressed epilogue): the
+// epilogue also writes the trilinear (align_corners) resample of the layer's output to (D/2, H/2,
+// W/2) into a.y2 -- 1: beside the output itself (side), 2: instead of it (only; the residual is
+// still read).  For in == 2 out every L1 voxel reads one aligned 2 x 2 x 2 block: a lane holds
+// the two W pairs of its four outputs, the other plane of the depth pair sits in lane ^ 32, the
+// other row in lane ^ 8 (Q = 8: two rows per lane group) or in the neighbouring wave (Q = 16:
+// TH = 4 rows, one per wave): the two rows swap halves of their W-lerped values (the wave pair
+// through 4 KB of LDS behind the stages) and each finishes two of the lane's four couts.  trilerp's expression tree (common.h: W innermost, then H, then D, contraction
+// off) with axis_index's own (i0, i1, l0, l1): bit-identical to resample3d_* of the plain
+// kernel's output.
+constexpr int kDownXch = 4 * 64 * 4;  // floats: four waves x 64 lanes x (2 couts x 2 L1 columns)
+__device__ __forceinline__ float lerp_dp(float l0, float v0, float l1, float v1) {
+#pragma clang fp contract(off)
+  return l0 * v0 + l1 * v1;
+}
+
+template <int F, int Q, int MT, int NP, int TD, bool CV, bool H16, bool FENCE, int DOWN>
+__device__ __forceinline__ void conv3d_wino_body(const ConvArgs& a) {
   using C = Cfg<F, Q, MT, NP, TD, H16>;
   static_assert(!(CV && H16), "16-byte halo: plain volumes only");
+  static_assert(DOWN == 0 || (C::DP && F == 4 && NP == 1 && !CV && (Q == 16 || Q == 8)),
+                "down-sampling epilogue: the depth-paired F(4,3) tiles");
+  constexpr int XCH = (DOWN != 0 && Q == 16) ? kDownXch : 0;
+  static_assert((2 * C::STAGE + XCH) * 4 * 2 <= 160 * 1024, "two workgroups per CU with the exchange region");
   constexpr int NX = C::NX;
   constexpr int XSLOTS = C::XSLOTS;
   constexpr int XSLOTS_W = (XSLOTS + kConvWaves - 1) / kConvWaves;
   constexpr int WSLOTS = C::WSLOTS;
   constexpr int WSLOTS_W = (WSLOTS + kConvWaves - 1) / kConvWaves;
-  __shared__ __attribute__((aligned(16))) float smem[2 * C::STAGE];
+  __shared__ __attribute__((aligned(16))) float smem[2 * C::STAGE + XCH];
   const unsigned lds0 = lds_addr(smem);
 
   const int tid = threadIdx.x;
@@ -369,6 +389,107 @@ __global__ __launch_bounds__(kConvThreads, 2) void conv3d_wino_kernel(const Conv
             buf_store4(yrs, off[t][j][m][r], y);
           }
   };
+  // the DOWN forms' L1 output: one float2 store per epilogue and lane (every lane issues it)
+  constexpr int NSD = 1;
+  // the lane's two L1 columns and its row pair (they do not change along the walk; unused and
+  // dropped in the plain form)
+  const Axis aw0 = axis_index(a.rw, w / 2, a.W, a.W / 2, 1), aw1 = axis_index(a.rw, w / 2 + 1, a.W, a.W / 2, 1);
+  const Axis ah = axis_index(a.rh, (h0 + wave * C::RPG + pr) / 2, a.H, a.H / 2, 1);
+  auto epilogue_down = [&](int d0) {
+    if constexpr (DOWN != 0) {
+      const int dp = ci >> 1;  // this lane's plane of the depth pair
+      const int d = d0 + dp;
+      const int h = h0 + wave * C::RPG + pr;
+      const bool lv = d < a.D && h < a.H && w < a.W;  // (even D, H and W % 4 == 0: whole blocks)
+      const int D2 = a.D / 2, H2 = a.H / 2, W2 = a.W / 2;
+      const long long V2 = (long long)D2 * H2 * W2;
+      unsigned off[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        off[r] = (lv && 4 * (ci & 1) + r < nco)
+                     ? (unsigned)((4 * (ci & 1) + r) * DHW + (long long)d * HW + h * a.W + w) * 4u
+                     : kEpiOob;
+      f32x4 rv[4];
+      if (resid) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rv[r] = buf_load4(rrs, off[r]);
+      }
+      const Axis ad = axis_index(a.rd, d0 / 2, a.D, D2, 1);
+      float wv[4][2];  // W-lerped: [cout][L1 column]
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {  // (the plain epilogue's expressions: the same bits)
+        const float m0 = 0.25f * acc[0][0][0][0][r];
+        const float m1 = (-1.f / 6.f) * acc[1][0][0][0][r], m2 = (-1.f / 6.f) * acc[2][0][0][0][r];
+        const float m3 = (1.f / 24.f) * acc[3][0][0][0][r], m4 = (1.f / 24.f) * acc[4][0][0][0][r];
+        const float m5 = acc[NX - 1][0][0][0][r];
+        const float sp = m1 + m2, sm = m1 - m2, tp = m3 + m4, tm = m3 - m4;
+        f32x4 y;
+        y[0] = (m0 + sp) + tp;
+        y[1] = fmaf(2.f, tm, sm);
+        y[2] = fmaf(4.f, tp, sp);
+        y[3] = fmaf(8.f, tm, sm) + m5;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float v = y[e] * sc[0][r] + sh[0][r];
+          if (relu) v = fmaxf(v, 0.f);
+          y[e] = resid ? v + rv[r][e] : v;
+        }
+        if constexpr (DOWN == 1) buf_store4(yrs, off[r], y);
+        wv[r][0] = lerp_dp(aw0.l0, (aw0.i0 & 1) ? y[1] : y[0], aw0.l1, (aw0.i1 & 1) ? y[1] : y[0]);
+        wv[r][1] = lerp_dp(aw1.l0, (aw1.i0 & 1) ? y[3] : y[2], aw1.l1, (aw1.i1 & 1) ? y[3] : y[2]);
+      }
+      // H: rows (h & ~1, h | 1) -> row0, row1 at this lane's plane.  The two lanes (Q = 8) or
+      // waves (Q = 16) of a row pair share the work: the even row finishes couts 0, 1 of the
+      // lane's four, the odd row couts 2, 3 -- each hands the other the half it does not finish
+      const int odd = Q == 8 ? pr : (wave & 1);
+      float mine[2][2], oth[2][2];
+      if constexpr (Q == 8) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+#pragma unroll
+          for (int c = 0; c < 2; ++c) {
+            mine[k][c] = odd ? wv[2 + k][c] : wv[k][c];
+            oth[k][c] = __shfl_xor(odd ? wv[k][c] : wv[2 + k][c], 8);
+          }
+      } else {
+        // through LDS: slot (row pair, sender's parity); the region is written again only after
+        // the next item's barrier (uniform: ch == nchunks - 1 is the workgroup's)
+        f32x4* const xq = reinterpret_cast<f32x4*>(smem + 2 * C::STAGE) + (wave >> 1) * 128 + lane;
+        if (odd) {  // (wave-uniform)
+          xq[64] = f32x4{wv[0][0], wv[0][1], wv[1][0], wv[1][1]};
+          mine[0][0] = wv[2][0], mine[0][1] = wv[2][1], mine[1][0] = wv[3][0], mine[1][1] = wv[3][1];
+        } else {
+          xq[0] = f32x4{wv[2][0], wv[2][1], wv[3][0], wv[3][1]};
+          mine[0][0] = wv[0][0], mine[0][1] = wv[0][1], mine[1][0] = wv[1][0], mine[1][1] = wv[1][1];
+        }
+        __syncthreads();
+        const f32x4 t = xq[64 * (1 - odd)];
+        oth[0][0] = t[0];
+        oth[0][1] = t[1];
+        oth[1][0] = t[2];
+        oth[1][1] = t[3];
+      }
+      // D: planes (d0, d0 + 1) -> pl0, pl1
+      float o[2][2];
+#pragma unroll
+      for (int k = 0; k < 2; ++k)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+          const float row0 = odd ? oth[k][c] : mine[k][c], row1 = odd ? mine[k][c] : oth[k][c];
+          const float hv = lerp_dp(ah.l0, (ah.i0 & 1) ? row1 : row0, ah.l1, (ah.i1 & 1) ? row1 : row0);
+          const float hp = __shfl_xor(hv, 32);
+          const float pl0 = dp ? hp : hv, pl1 = dp ? hv : hp;
+          o[k][c] = lerp_dp(ad.l0, (ad.i0 & 1) ? pl1 : pl0, ad.l1, (ad.i1 & 1) ? pl1 : pl0);
+        }
+      // both planes' lanes hold the two couts: plane dp stores cout 2 odd + dp of the lane's four
+      const __amdgpu_buffer_rsrc_t y2rs = block_rsrc(a.y2 + (long long)b * a.y2bs, nco * V2 * 4);
+      const long long vox = ((long long)(d0 / 2) * H2 + h / 2) * W2 + w / 2;
+      const int cr = 4 * (ci & 1) + 2 * odd + dp;
+      const f32x2 v2 = dp ? f32x2{o[1][0], o[1][1]} : f32x2{o[0][0], o[0][1]};
+      const unsigned off2 = (lv && cr < nco) ? (unsigned)(cr * V2 + vox) * 4u : kEpiOob;
+      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_t, v2), y2rs, off2, 0, 0);
+    }
+  };
   auto epilogue = [&](int d0) {
 #pragma unroll
   for (int t = 0; t < C::TDA; ++t) {
@@ -445,7 +566,8 @@ __global__ __launch_bounds__(kConvThreads, 2) void conv3d_wino_kernel(const Conv
   issue(0, smem);
   for (int it = 0; it < nitems; ++it) {
     const int ch = it % nchunks;
-    wait_item<NST>(ebuf && ch == 0 && it > 0);  // this wave's pieces of item it landed
+    // this wave's pieces of item it landed (the DOWN forms: always the buffer-addressed epilogue)
+    wait_item<DOWN == 0 ? NST : DOWN == 1 ? NST + NSD : NSD>((DOWN != 0 || ebuf) && ch == 0 && it > 0);
     __syncthreads();  // ... and everyone's; item it-1's stage is free
     if (it + 1 < nitems) issue(it + 1, smem + ((it + 1) & 1) * C::STAGE);
     const float* xs = smem + (it & 1) * C::STAGE;
@@ -570,7 +692,9 @@ __global__ __launch_bounds__(kConvThreads, 2) void conv3d_wino_kernel(const Conv
     }
     }
     if (ch == nchunks - 1) {  // the depth group's last chunk: its epilogue, fresh accumulators
-      if (ebuf)
+      if constexpr (DOWN != 0)
+        epilogue_down((dz0 + it / nchunks) * TD);
+      else if (ebuf)
         epilogue_buf((dz0 + it / nchunks) * TD);
       else
         epilogue((dz0 + it / nchunks) * TD);
@@ -584,6 +708,17 @@ __global__ __launch_bounds__(kConvThreads, 2) void conv3d_wino_kernel(const Conv
             for (int j = 0; j < NP; ++j) acc[x][t][m][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
   }
+}
+
+template <int F, int Q, int MT, int NP, int TD, bool CV, bool H16 = false, bool FENCE = false>
+__global__ __launch_bounds__(kConvThreads, 2) void conv3d_wino_kernel(const ConvArgs a) {
+  conv3d_wino_body<F, Q, MT, NP, TD, CV, H16, FENCE, 0>(a);
+}
+// the depth-paired tiles' DOWN forms (Q = 16: 16-byte halo, fenced schedule -- the plain launch's
+// default instantiation; Q = 8: the 32-wide row pairs); ONLY: no full-resolution store
+template <int Q, bool ONLY>
+__global__ __launch_bounds__(kConvThreads, 2) void conv3d_wino_dp_down2_kernel(const ConvArgs a) {
+  conv3d_wino_body<4, Q, 0, 1, 2, false, Q == 16, Q == 16, ONLY ? 2 : 1>(a);
 }
 
 // weights [cout][cin][3][3][3] -> per (cout block, chunk): [kd*3+kh][kw][ci][COP col]
@@ -1139,6 +1274,131 @@ extern "C" int lea_conv3d_bnrelu_costvolume_wino(const void* left, const void* r
   return wino::common(a, B, true, dtype, stream);
 }
 
+// ---- the depth-paired tiles with the down-sampling epilogue (conv3d_wino_body, DOWN) ----
+namespace lea {
+namespace wino {
+
+// does the planner put this layer on a depth-paired tile that has a DOWN form -- the 64-wide one
+// in its default instantiation (16-byte halo, fenced schedule) or the 32-wide row pairs -- with
+// the buffer-addressed epilogue?  `a` = the entry's arguments (alignment checked), or NULL for
+// the shape alone (aligned operands assumed).  Returns Q (16 / 8), or 0
+static int dp_down2_plan(int B, int cin, int cout, int D, int H, int W, ConvArgs* a) {
+  if (B <= 0 || cin <= 0 || cout <= 0 || cout > 8 || D < 2 || H < 2 || W < 4 || D % 2 || H % 2 || W % 4 ||
+      cin % CIN_B)
+    return 0;
+  if ((long long)D * H * W * 4 >= (1LL << 32) || (long long)(cout + 47) * D * H * W >= (1LL << 31)) return 0;
+  if (!g_epibuf || g_w22 == 2 || g_variant != 0 || g_override[0] != 0) return 0;
+  Plan p = make_plan(B, cout, D, H, W);
+  if (p.mt != 0 || p.d2 || p.f != 4 || p.np != 1 || p.td != 2) return 0;
+  plan_halo16(p, false, W, a, cin);
+  if (a && !epi_buf_ok(*a)) return 0;
+  if (p.q == 16) return (p.h16 && g_fence) ? 16 : 0;
+  return p.q == 8 ? 8 : 0;
+}
+
+static int run_dp_down2(ConvArgs a, int B, int q, bool only, hipStream_t st) {
+  a.ncob = 1;
+  const int tw = 4 * q, th = 4 * (16 / q);
+  a.tiles_w = (a.W + tw - 1) / tw;
+  a.ntiles = a.tiles_w * ((a.H + th - 1) / th);
+  a.ndz = (a.D + 1) / 2;
+  a.spw = std::max(1, std::min(g_spw > 0 ? g_spw : auto_walk(a, B, 2), a.ndz));
+  const long long n_ = (long long)a.ntiles * ((a.ndz + a.spw - 1) / a.spw) * B * a.ncob;
+  LEA_CHECK_ARG(n_ < (1LL << 31), "lea_conv3d_bnrelu_wino_dp_down2: grid too large");
+  a.nblk = (int)n_;
+  const dim3 grid((unsigned)n_);
+  if (q == 16) {
+    if (only)
+      conv3d_wino_dp_down2_kernel<16, true><<<grid, kConvThreads, 0, st>>>(a);
+    else
+      conv3d_wino_dp_down2_kernel<16, false><<<grid, kConvThreads, 0, st>>>(a);
+  } else {
+    if (only)
+      conv3d_wino_dp_down2_kernel<8, true><<<grid, kConvThreads, 0, st>>>(a);
+    else
+      conv3d_wino_dp_down2_kernel<8, false><<<grid, kConvThreads, 0, st>>>(a);
+  }
+  return launch_status("lea_conv3d_bnrelu_wino_dp_down2");
+}
+
+}  // namespace wino
+}  // namespace lea
+
+extern "C" int lea_conv3d_wino_dp_down2_supported(int B, int cin, int cout, int D, int H, int W) {
+  return wino::dp_down2_plan(B, cin, cout, D, H, W, nullptr) ? 1 : 0;
+}
+
+extern "C" const char* lea_conv3d_wino_dp_down2_kernel_name(int B, int cin, int cout, int D, int H, int W,
+                                                            int only) {
+  const int q = wino::dp_down2_plan(B, cin, cout, D, H, W, nullptr);
+  if (!q) return nullptr;
+  snprintf(wino::g_name, sizeof(wino::g_name), "conv3d_wino_dp_down2_kernel<%d, %s>", q, only ? "true" : "false");
+  return wino::g_name;
+}
+
+extern "C" int lea_conv3d_bnrelu_wino_dp_down2(const void* x, int64_t x_bstride, const float* w_packed,
+                                               const float* scale, const float* shift, const void* residual,
+                                               int64_t r_bstride, void* y, int64_t y_bstride, void* y2,
+                                               int64_t y2_bstride, int B, int cin, int cout, int D, int H, int W,
+                                               unsigned flags, int dtype, void* stream) {
+  const char* what = "lea_conv3d_bnrelu_wino_dp_down2";
+  clear_error();
+  ConvArgs a{};
+  a.x = (const float*)x;
+  a.xbs = x_bstride;
+  a.cin1 = cin;
+  a.wp = w_packed;
+  a.scale = scale;
+  a.shift = shift;
+  a.res = (const float*)residual;
+  a.rbs = r_bstride;
+  a.y = (float*)y;  // NULL: the `only` form
+  a.ybs = y_bstride;
+  a.y2 = (float*)y2;
+  a.y2bs = y2_bstride;
+  a.cin = cin;
+  a.cout = cout;
+  a.D = D;
+  a.H = H;
+  a.W = W;
+  LEA_CHECK_ARG(a.x && a.wp && a.y2, "%s: null pointer", what);
+  LEA_CHECK_ARG((scale == nullptr) == (shift == nullptr), "%s: scale/shift must both be set or both NULL", what);
+  LEA_CHECK_ARG(!(flags & LEA_RESIDUAL) || a.res, "%s: LEA_RESIDUAL without residual", what);
+  LEA_CHECK_ARG(B > 0 && cin > 0 && cout > 0 && D > 0 && H > 0 && W > 0,
+                "%s: bad shape B=%d cin=%d cout=%d D=%d H=%d W=%d", what, B, cin, cout, D, H, W);
+  LEA_CHECK_FLAGS(flags, LEA_RELU | LEA_RESIDUAL, what);
+  a.flags = flags;
+  if (dtype != LEA_F32) {
+    set_error("%s: dtype %d unsupported", what, dtype);
+    return LEA_E_UNSUPPORTED;
+  }
+  if (cout > 8 || D % 2 || H % 2 || W % 4 || cin % wino::CIN_B) {
+    set_error("%s: needs cout <= 8, even D and H, W %% 4 == 0, cin %% %d == 0 (cin=%d cout=%d D=%d H=%d W=%d)", what,
+              wino::CIN_B, cin, cout, D, H, W);
+    return LEA_E_UNSUPPORTED;
+  }
+  LEA_CHECK_ARG(a.x != a.y && a.x != a.y2 && a.y != a.y2 && a.res != a.y2, "%s: aliased output", what);
+  // float2 stores through 32-bit byte offsets of the L1 tensor
+  LEA_CHECK_ARG(((uintptr_t)y2 & 15) == 0 && y2_bstride % 4 == 0, "%s: y2 needs 16-byte alignment", what);
+  const bool only = a.y == nullptr;
+  if (only) {  // (the planner's alignment rules read a.y: the residual's stand in)
+    a.y = const_cast<float*>(a.res ? a.res : a.x);
+    a.ybs = a.res ? a.rbs : a.xbs;
+  }
+  const int q = wino::dp_down2_plan(B, cin, cout, D, H, W, &a);
+  if (!q) {
+    set_error("%s: the planner does not put B=%d cin=%d cout=%d D=%d H=%d W=%d on a depth-paired tile with the "
+              "buffer-addressed epilogue (or its settings / the operands' alignment rule it out)",
+              what, B, cin, cout, D, H, W);
+    return LEA_E_UNSUPPORTED;
+  }
+  a.flags |= wino::kEpiBuf;
+  a.rd = axis_ratio(D, D / 2, 1);
+  a.rh = axis_ratio(H, H / 2, 1);
+  a.rw = axis_ratio(W, W / 2, 1);
+  return wino::run_dp_down2(a, B, q, only, as_stream(stream));
+}
+
 // ---- the F(4,3) x F(4,3) tile with the down-sampling epilogue (conv3d_wino44.hip, DOWN) ----
 namespace lea {
 namespace wino {
@@ -1171,15 +1431,31 @@ extern "C" const char* lea_conv3d_wino_down2_kernel_name(int B, int cin, int cou
   return wino::down2_plan(B, cin, cout, D, H, W, nullptr, nullptr) ? "conv3d_wino44_down2_kernel" : nullptr;
 }
 
-extern "C" int lea_conv3d_bnrelu_wino_down2(const void* x, int64_t x_bstride, const float* w_packed,
-                                            const float* scale, const float* shift, void* y,
-                                            int64_t y_bstride, int B, int cin, int cout, int D, int H, int W,
-                                            unsigned flags, int dtype, void* stream) {
+// the two-input form (cat(x, x2) read in place, cin2 of the cin channels from x2): a chunk never
+// straddles the sources
+extern "C" int lea_conv3d_wino_down2_cat_supported(int B, int cin, int cin2, int cout, int D, int H, int W) {
+  if (cin2 <= 0 || cin2 >= cin || cin2 % wino::CIN_B) return 0;
+  return wino::down2_plan(B, cin, cout, D, H, W, nullptr, nullptr) ? 1 : 0;
+}
+
+extern "C" const char* lea_conv3d_wino_down2_cat_kernel_name(int B, int cin, int cin2, int cout, int D, int H,
+                                                             int W) {
+  return lea_conv3d_wino_down2_cat_supported(B, cin, cin2, cout, D, H, W) ? "conv3d_wino44_down2_cat_kernel"
+                                                                          : nullptr;
+}
+
+// both entries: `what` names the entry in messages; x2 == NULL is the one-input form
+static int wino_down2_entry(const char* what, const void* x, int64_t x_bstride, const void* x2, int64_t x2_bstride,
+                            int cin2, const float* w_packed, const float* scale, const float* shift, void* y,
+                            int64_t y_bstride, int B, int cin, int cout, int D, int H, int W, unsigned flags,
+                            int dtype, void* stream) {
   clear_error();
   ConvArgs a{};
   a.x = (const float*)x;
   a.xbs = x_bstride;
-  a.cin1 = cin;
+  a.x2 = (const float*)x2;
+  a.x2bs = x2_bstride;
+  a.cin1 = cin - cin2;
   a.wp = w_packed;
   a.scale = scale;
   a.shift = shift;
@@ -1190,35 +1466,37 @@ extern "C" int lea_conv3d_bnrelu_wino_down2(const void* x, int64_t x_bstride, co
   a.D = D;
   a.H = H;
   a.W = W;
-  LEA_CHECK_ARG(a.x && a.wp && a.y, "lea_conv3d_bnrelu_wino_down2: null pointer");
-  LEA_CHECK_ARG((scale == nullptr) == (shift == nullptr),
-                "lea_conv3d_bnrelu_wino_down2: scale/shift must both be set or both NULL");
+  LEA_CHECK_ARG(a.x && a.wp && a.y, "%s: null pointer", what);
+  LEA_CHECK_ARG((scale == nullptr) == (shift == nullptr), "%s: scale/shift must both be set or both NULL", what);
   LEA_CHECK_ARG(B > 0 && cin > 0 && cout > 0 && D > 0 && H > 0 && W > 0,
-                "lea_conv3d_bnrelu_wino_down2: bad shape B=%d cin=%d cout=%d D=%d H=%d W=%d", B, cin, cout, D, H, W);
+                "%s: bad shape B=%d cin=%d cout=%d D=%d H=%d W=%d", what, B, cin, cout, D, H, W);
   if (flags & (LEA_RESIDUAL | LEA_PAIR_SUM)) {
-    set_error("lea_conv3d_bnrelu_wino_down2: LEA_RESIDUAL / LEA_PAIR_SUM are not supported with the "
-              "down-sampling epilogue");
+    set_error("%s: LEA_RESIDUAL / LEA_PAIR_SUM are not supported with the down-sampling epilogue", what);
     return LEA_E_UNSUPPORTED;
   }
-  LEA_CHECK_FLAGS(flags, LEA_RELU, "lea_conv3d_bnrelu_wino_down2");
+  LEA_CHECK_FLAGS(flags, LEA_RELU, what);
   a.flags = flags;
   LEA_CHECK_ARG(D % 2 == 0 && H % 2 == 0 && W % 4 == 0,
-                "lea_conv3d_bnrelu_wino_down2: D and H must be even and W %% 4 == 0 (D=%d H=%d W=%d)", D, H, W);
-  LEA_CHECK_ARG(cin % wino::CIN_B == 0, "lea_conv3d_bnrelu_wino_down2: cin %d must be a multiple of %d", cin,
-                wino::CIN_B);
-  LEA_CHECK_ARG(a.x != a.y, "lea_conv3d_bnrelu_wino_down2: input aliases output");
+                "%s: D and H must be even and W %% 4 == 0 (D=%d H=%d W=%d)", what, D, H, W);
+  LEA_CHECK_ARG(cin % wino::CIN_B == 0, "%s: cin %d must be a multiple of %d", what, cin, wino::CIN_B);
+  if (x2) {
+    LEA_CHECK_ARG(cin2 > 0 && cin2 < cin && cin2 % wino::CIN_B == 0,
+                  "%s: the second source's %d of %d channels must be a multiple of %d in (0, cin)", what, cin2, cin,
+                  wino::CIN_B);
+    // 16-byte DMA pieces of both sources
+    LEA_CHECK_ARG(((uintptr_t)x2 & 15) == 0 && x2_bstride % 4 == 0, "%s: x2 needs 16-byte alignment", what);
+  }
+  LEA_CHECK_ARG(a.x != a.y && a.x2 != a.y, "%s: input aliases output", what);
   if (dtype != LEA_F32) {
-    set_error("lea_conv3d_bnrelu_wino_down2: dtype %d unsupported", dtype);
+    set_error("%s: dtype %d unsupported", what, dtype);
     return LEA_E_UNSUPPORTED;
   }
   // float2 stores through 32-bit byte offsets of a cout block of the L1 tensor
-  LEA_CHECK_ARG(((uintptr_t)y & 15) == 0 && y_bstride % 4 == 0,
-                "lea_conv3d_bnrelu_wino_down2: y needs 16-byte alignment");
+  LEA_CHECK_ARG(((uintptr_t)y & 15) == 0 && y_bstride % 4 == 0, "%s: y needs 16-byte alignment", what);
   wino::Plan2 q;
   if (!wino::down2_plan(B, cin, cout, D, H, W, &a, &q)) {
-    set_error("lea_conv3d_bnrelu_wino_down2: the planner does not put B=%d cin=%d cout=%d D=%d H=%d W=%d on "
-              "the F(4,3) x F(4,3) tile (or its settings / the operands' alignment rule it out)",
-              B, cin, cout, D, H, W);
+    set_error("%s: the planner does not put B=%d cin=%d cout=%d D=%d H=%d W=%d on the F(4,3) x F(4,3) tile "
+              "(or its settings / the operands' alignment rule it out)", what, B, cin, cout, D, H, W);
     return LEA_E_UNSUPPORTED;
   }
   a.rd = axis_ratio(D, D / 2, 1);
@@ -1226,4 +1504,23 @@ extern "C" int lea_conv3d_bnrelu_wino_down2(const void* x, int64_t x_bstride, co
   a.rw = axis_ratio(W, W / 2, 1);
   a.uoff = wino::l44_offset(cout, cin);
   return wino::run44(a, B, q.spw, as_stream(stream), true);
+}
+
+extern "C" int lea_conv3d_bnrelu_wino_down2(const void* x, int64_t x_bstride, const float* w_packed,
+                                            const float* scale, const float* shift, void* y,
+                                            int64_t y_bstride, int B, int cin, int cout, int D, int H, int W,
+                                            unsigned flags, int dtype, void* stream) {
+  return wino_down2_entry("lea_conv3d_bnrelu_wino_down2", x, x_bstride, nullptr, 0, 0, w_packed, scale, shift, y,
+                          y_bstride, B, cin, cout, D, H, W, flags, dtype, stream);
+}
+
+extern "C" int lea_conv3d_bnrelu_wino_down2_cat(const void* x, int64_t x_bstride, const void* x2,
+                                                int64_t x2_bstride, int cin2, const float* w_packed,
+                                                const float* scale, const float* shift, void* y,
+                                                int64_t y_bstride, int B, int cin, int cout, int D, int H, int W,
+                                                unsigned flags, int dtype, void* stream) {
+  clear_error();
+  LEA_CHECK_ARG(x2, "lea_conv3d_bnrelu_wino_down2_cat: null pointer");
+  return wino_down2_entry("lea_conv3d_bnrelu_wino_down2_cat", x, x_bstride, x2, x2_bstride, cin2, w_packed, scale,
+                          shift, y, y_bstride, B, cin, cout, D, H, W, flags, dtype, stream);
 }

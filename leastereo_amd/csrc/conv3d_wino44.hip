@@ -629,6 +629,11 @@ __global__ __launch_bounds__(256, 2) void conv3d_wino44_kernel(const ConvArgs a)
 __global__ __launch_bounds__(256, 2) void conv3d_wino44_down2_kernel(const ConvArgs a) {
   conv3d_wino44_body<false, 0, true>(a);
 }
+// the same body on cat(x, x2) read in place (lea_conv3d_bnrelu_wino_down2_cat: issue_halo takes a
+// chunk's channels from the source that holds them), under a name of its own in traces
+__global__ __launch_bounds__(256, 2) void conv3d_wino44_down2_cat_kernel(const ConvArgs a) {
+  conv3d_wino44_body<false, 0, true>(a);
+}
 
 // lea_conv3d_wino44_set (r06 default 1: -9.5 % on its layers, profiles/r06_w44_ab.txt; 2 since v45,
 // after the LDS-conflict fixes: the L0 8 -> 24 group 275.6 -> 259.7 us, profiles/r06_w44_modes_ab.txt)
@@ -653,7 +658,10 @@ int run44(ConvArgs a, int B, int spw, hipStream_t st, bool down) {
   a.grp = g_w44g >= 0 ? g_w44g : (n_ >= 2048 ? 16 : 0);
   const dim3 grid((unsigned)n_);
   if (down) {  // (the host entry checked: the plain form's default instantiation)
-    conv3d_wino44_down2_kernel<<<grid, 256, 0, st>>>(a);
+    if (a.x2 && a.cin1 < a.cin)
+      conv3d_wino44_down2_cat_kernel<<<grid, 256, 0, st>>>(a);
+    else
+      conv3d_wino44_down2_kernel<<<grid, 256, 0, st>>>(a);
     return launch_status("lea_conv3d(wino44 down2)");
   }
   if (g_w44u)

@@ -126,6 +126,7 @@ constexpr int OB = 16;
 
 // one row's right-half sums rs [OB][NT] and edge corrections corr [OB][dchunk] (rkh: the right
 // maps at that row)
+template <int OB = 16>
 __device__ __forceinline__ void stage_row_f32(const Args& a, const Tile& T, const float* rkh, float* rs,
                                               float* corr) {
   const int D = T.D, W = T.W, NU = T.NU, NT = T.NT, d0 = T.d0, d1 = T.d1, w0 = T.w0;
@@ -292,36 +293,44 @@ __global__ __launch_bounds__(kThreads) void cv_stem_f32_kernel(const Args a) {
 // resample of y to (D/2, H/2, W/2), bit-identical to resample3d_* on y (trilerp's expression
 // tree: W innermost, then H, then D, contraction off).  For in == 2 out both source indices of
 // output o are in {2o, 2o + 1}, so every y2 voxel reads one aligned 2 x 2 x 2 block of y: a
-// workgroup = (batch, 16 couts, row pair 2 hp and 2 hp + 1, 64 columns) walking every plane in
-// order, thread = (cout, 4 columns) of both rows -- two float4 stores per plane as above, and
-// per plane pair one float2 of y2.  The per-voxel arithmetic of y is cv_stem_f32_kernel's.
+// workgroup = (batch, 8 couts, row pair 2 hp and 2 hp + 1, 64 columns) walking every plane in
+// order, thread = (cout, row, 4 columns) with one row of the pair per half-wave -- one float4
+// store per plane as above, the other row's W-lerped values from lane ^ 32, and per plane pair one
+// float of y2 (the half-waves store the two L1 columns).  8 couts x 2 rows stage what the plain
+// kernel's 16 couts x 1 row do (the same LDS, the same registers per thread: the first form, 16
+// couts with both rows per thread, took 40.8 KB and 138 VGPRs -- three waves per SIMD against
+// seven).  The per-voxel arithmetic of y is cv_stem_f32_kernel's.
 __device__ __forceinline__ float lerp2(float l0, float v0, float l1, float v1) {
 #pragma clang fp contract(off)
   return l0 * v0 + l1 * v1;
 }
 
+constexpr int OBD = 8;  // couts per workgroup of the down-sampling variant
+
 __global__ __launch_bounds__(kThreads) void cv_stem_f32_down2_kernel(const Args a) {
-  extern __shared__ float rs[];  // per row: [OB][NT] sums, then [OB][D] edge corrections
+  extern __shared__ float rs[];  // per row: [OBD][NT] sums, then [OBD][D] edge corrections
   const Tile T = tile_of(a, a.H / 2);  // T.h: the row pair; nds == 1, so d0 = 0 and d1 = D
   const int D = T.D, H = T.H, W = T.W, NU = T.NU, NT = T.NT, w0 = T.w0, hp = T.h;
   const long long HW = T.HW;
   const float* lk = static_cast<const float*>(a.lk) + T.b * a.lbs;
   const float* rk = static_cast<const float*>(a.rk) + T.b * a.rbs;
-  const int rowf = OB * (NT + a.dchunk);  // staged floats per row
+  const int rowf = OBD * (NT + a.dchunk);  // staged floats per row
   const int tid = threadIdx.x;
 #pragma unroll
   for (int r = 0; r < 2; ++r)
-    stage_row_f32(a, T, rk + (long long)(2 * hp + r) * W, rs + r * rowf, rs + r * rowf + OB * NT);
+    stage_row_f32<OBD>(a, T, rk + (long long)(2 * hp + r) * W, rs + r * rowf, rs + r * rowf + OBD * NT);
   __syncthreads();
 
-  const int ol = tid >> 4, o = T.cob * OB + ol;
+  // lane = 32 r + 16 (cout & 1) + column quad; wave = cout >> 1: the two rows of a (cout, quad)
+  // sit in lanes l and l ^ 32, which leave or stay together below
+  const int r = (tid >> 5) & 1;
+  const int ol = ((tid >> 6) << 1) | ((tid >> 4) & 1), o = T.cob * OBD + ol;
   const int w = w0 + 4 * (tid & 15);
   if (o >= a.cout || w >= W) return;  // W % 4 == 0 (host)
   const bool band = w - (D - 1) <= 1;
-  // per row: the left half of the interior planes (gl, bl as above) and of planes 0 and D - 1
-  float gl[2][4], bl[2][4][4], lf[2][4], ll[2][4];
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
+  // this row's left half of the interior planes (gl, bl as above) and of planes 0 and D - 1
+  float gl[4], bl[4][4], lf[4], ll[4];
+  {
     float lkv[3][3][4];
 #pragma unroll
     for (int kd = 0; kd < 3; ++kd)
@@ -343,82 +352,73 @@ __global__ __launch_bounds__(kThreads) void cv_stem_f32_down2_kernel(const Args 
       for (int kd = 0; kd < 3; ++kd)
 #pragma unroll
         for (int t = 0; t < 3; ++t) l3[kd][t] = lkv[kd][t][j];
-      gl[r][j] = lkv[0][0][j] + lkv[1][0][j] + lkv[2][0][j];
+      gl[j] = lkv[0][0][j] + lkv[1][0][j] + lkv[2][0][j];
 #pragma unroll
-      for (int m = 0; m < 4; ++m) bl[r][m][j] = left_sum(l3, 1, m - 2, D);
-      lf[r][j] = left_sum(l3, 0, w + j, D);
-      ll[r][j] = left_sum(l3, D - 1, w + j - (D - 1), D);
+      for (int m = 0; m < 4; ++m) bl[m][j] = left_sum(l3, 1, m - 2, D);
+      lf[j] = left_sum(l3, 0, w + j, D);
+      ll[j] = left_sum(l3, D - 1, w + j - (D - 1), D);
     }
   }
   const float sc = a.scale ? a.scale[o] : 1.f, sh = a.scale ? a.shift[o] : 0.f;
   const float lo = (a.flags & LEA_RELU) ? 0.f : -INFINITY;  // ReLU as a floor
   const int jedge = W - 1 - w;
   const bool far = w0 - (D - 2) >= 2;  // every lane has u >= 2 on every interior plane
-  float* yp = static_cast<float*>(a.y) + T.b * a.ybs + (long long)o * D * HW + (long long)(2 * hp) * W + w;
+  float* yp = static_cast<float*>(a.y) + T.b * a.ybs + (long long)o * D * HW + (long long)(2 * hp + r) * W + w;
   const int D2 = D / 2, H2 = H / 2, W2 = W / 2;
-  float* y2p = a.y2 + T.b * a.y2bs + ((long long)o * D2 * H2 + hp) * W2 + w / 2;
+  // the lane stores L1 column w / 2 + r (its pair of lanes holds both)
+  float* y2p = a.y2 + T.b * a.y2bs + ((long long)o * D2 * H2 + hp) * W2 + w / 2 + r;
   // the lane's two L1 columns w / 2 + c read columns w + 2 c + {0, 1}; its L1 row hp rows 2 hp + {0, 1}
   Axis aw[2];
 #pragma unroll
   for (int c = 0; c < 2; ++c) aw[c] = axis_index(a.rw, w / 2 + c, W, W2, 1);
   const Axis ah = axis_index(a.rh, hp, H, H2, 1);
   const bool h0odd = ah.i0 & 1, h1odd = ah.i1 & 1;
+  const float* r0 = rs + r * rowf + ol * NT;
+  const float* cr = rs + r * rowf + OBD * NT + ol * a.dchunk;
 
   float ev[2] = {0.f, 0.f};  // the even plane's H-lerped values until the odd plane arrives
   for (int d = 0; d < D; ++d) {
-    float out[2][4];
+    const float c = cr[d];
+    float pre[4];
+    if (d == 0 || d == D - 1) {
+      const int pb = (d == 0 ? NU : NU + WS) + (w - w0);
 #pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const float* r0 = rs + r * rowf + ol * NT;
-      const float c = rs[r * rowf + OB * NT + ol * a.dchunk + d];
-      float pre[4];
-      if (d == 0 || d == D - 1) {
-        const int pb = (d == 0 ? NU : NU + WS) + (w - w0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) pre[j] = (d == 0 ? lf[r][j] : ll[r][j]) + r0[pb + j] - (j == jedge ? c : 0.f);
-      } else {
-        const int iu = w - d - T.u0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int u = w + j - d;
-          float l = (far || u >= 2) ? gl[r][j] : 0.f;
-          if (!far) {
-#pragma unroll
-            for (int m = 0; m < 4; ++m) l = u == m - 2 ? bl[r][m][j] : l;
-          }
-          pre[j] = l + r0[iu + j] - (j == jedge ? c : 0.f);
-        }
-      }
-      float4 o4;
-      float* po = reinterpret_cast<float*>(&o4);
+      for (int j = 0; j < 4; ++j) pre[j] = (d == 0 ? lf[j] : ll[j]) + r0[pb + j] - (j == jedge ? c : 0.f);
+    } else {
+      const int iu = w - d - T.u0;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        po[j] = fmaxf(pre[j] * sc + sh, lo);
-        out[r][j] = po[j];
+        const int u = w + j - d;
+        float l = (far || u >= 2) ? gl[j] : 0.f;
+        if (!far) {
+#pragma unroll
+          for (int m = 0; m < 4; ++m) l = u == m - 2 ? bl[m][j] : l;
+        }
+        pre[j] = l + r0[iu + j] - (j == jedge ? c : 0.f);
       }
-      *reinterpret_cast<float4*>(yp + (long long)d * HW + r * W) = o4;
     }
+    float4 o4;
+    float* out = reinterpret_cast<float*>(&o4);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) out[j] = fmaxf(pre[j] * sc + sh, lo);
+    *reinterpret_cast<float4*>(yp + (long long)d * HW) = o4;
     float hv[2];
 #pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      float wv[2];
-#pragma unroll
-      for (int r = 0; r < 2; ++r) {
-        const float v0 = (aw[c].i0 & 1) ? out[r][2 * c + 1] : out[r][2 * c];
-        const float v1 = (aw[c].i1 & 1) ? out[r][2 * c + 1] : out[r][2 * c];
-        wv[r] = lerp2(aw[c].l0, v0, aw[c].l1, v1);
-      }
-      hv[c] = lerp2(ah.l0, h0odd ? wv[1] : wv[0], ah.l1, h1odd ? wv[1] : wv[0]);
+    for (int k = 0; k < 2; ++k) {
+      const float v0 = (aw[k].i0 & 1) ? out[2 * k + 1] : out[2 * k];
+      const float v1 = (aw[k].i1 & 1) ? out[2 * k + 1] : out[2 * k];
+      const float mine = lerp2(aw[k].l0, v0, aw[k].l1, v1);
+      const float other = __shfl_xor(mine, 32);  // the pair's other row, W-lerped
+      const float row0 = r ? other : mine, row1 = r ? mine : other;
+      hv[k] = lerp2(ah.l0, h0odd ? row1 : row0, ah.l1, h1odd ? row1 : row0);
     }
     if (!(d & 1)) {
       ev[0] = hv[0];
       ev[1] = hv[1];
     } else {
       const Axis ad = axis_index(a.rd, d >> 1, D, D2, 1);
-      float2 o2;
-      o2.x = lerp2(ad.l0, (ad.i0 & 1) ? hv[0] : ev[0], ad.l1, (ad.i1 & 1) ? hv[0] : ev[0]);
-      o2.y = lerp2(ad.l0, (ad.i0 & 1) ? hv[1] : ev[1], ad.l1, (ad.i1 & 1) ? hv[1] : ev[1]);
-      *reinterpret_cast<float2*>(y2p + (long long)(d >> 1) * H2 * W2) = o2;
+      const float e = r ? ev[1] : ev[0], v = r ? hv[1] : hv[0];
+      y2p[(long long)(d >> 1) * H2 * W2] = lerp2(ad.l0, (ad.i0 & 1) ? v : e, ad.l1, (ad.i1 & 1) ? v : e);
     }
   }
 }
@@ -764,10 +764,10 @@ extern "C" int lea_cv_stem_combine_down2(const void* lmaps, int64_t l_bstride, c
   a.nseg = (W + cvs::WS - 1) / cvs::WS;
   a.dchunk = D3;
   a.nds = 1;
-  a.ncob = (cout + cvs::OB - 1) / cvs::OB;
+  a.ncob = (cout + cvs::OBD - 1) / cvs::OBD;
   const long long nblk = (long long)B * a.ncob * (H / 2) * a.nseg;
   LEA_CHECK_ARG(nblk < (1LL << 31), "lea_cv_stem_combine_down2: grid too large");
-  const size_t lds = (size_t)2 * cvs::OB * (2 * D3 + 3 * cvs::WS - 1) * sizeof(float);
+  const size_t lds = (size_t)2 * cvs::OBD * (2 * D3 + 3 * cvs::WS - 1) * sizeof(float);
   cvs::cv_stem_f32_down2_kernel<<<dim3((unsigned)nblk), cvs::kThreads, lds, as_stream(stream)>>>(a);
   return launch_status("lea_cv_stem_combine_down2");
 }

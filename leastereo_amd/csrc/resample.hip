@@ -200,6 +200,106 @@ __global__ __launch_bounds__(256) void resample3d_sep_f32(
   }
 }
 
+// The separable kernel with a down-sampled side output (lea_resample3d_trilinear_down2): besides
+// y it writes y2 = the trilinear (align_corners) resample of y to exactly half (an aligned
+// 2 x 2 x 2 block of y per y2 voxel), bit-identical to resampling y again, without reading y back.
+// A workgroup owns R (even) output rows of an output plane PAIR: the W-lerped source rows of the
+// pair's <= 3 source planes (an up-sampling along D: the first source plane of output plane
+// o + 1 is at most one past that of o); a thread owns a 2 x 2 x 4 block of y -- four float4 stores
+// by resample3d_sep_f32's own expression, then trilerp's tree on the block (W pairs in-lane, H,
+// D) and one float2 of y2.
+__global__ __launch_bounds__(256) void resample3d_sep_down2_f32(
+    const float* __restrict__ x, long long xbs, float* __restrict__ y, long long ybs, float* __restrict__ y2,
+    long long y2bs, int C, int Di, int Hi, int Wi, int Do, int Ho, int Wo, float rd, float rh, float rw,
+    float rd2, float rh2, float rw2, int R, int nrmax, const float* __restrict__ scale,
+    const float* __restrict__ shift, unsigned flags) {
+#pragma clang fp contract(off)
+  extern __shared__ float wrows[];  // [3][nrmax][Wo]: W-lerped source rows
+  const int D2 = Do / 2, H2 = Ho / 2, W2 = Wo / 2;
+  const int pp = blockIdx.y % D2;  // output planes 2 pp, 2 pp + 1
+  const int bc = blockIdx.y / D2;
+  const int b = bc / C, c = bc - b * C;
+  const int oh0 = blockIdx.x * R;
+  const int oh1 = min(oh0 + R, Ho);
+  const Axis ad[2] = {axis_index(rd, 2 * pp, Di, Do, 1), axis_index(rd, 2 * pp + 1, Di, Do, 1)};
+  const int db = ad[0].i0;
+  const int r_lo = axis_index(rh, oh0, Hi, Ho, 1).i0;
+  const int r_hi = axis_index(rh, oh1 - 1, Hi, Ho, 1).i1;
+  // nrmax = the host's exact bound (staged_rows); past it, or past the three-plane window: NaN
+  // outputs, never unstaged rows
+  const bool over = r_hi - r_lo + 1 > nrmax || ad[1].i1 - db > 2;
+  const int nr = over ? 0 : r_hi - r_lo + 1;
+  const long long HWi = (long long)Hi * Wi;
+  const float* xc = x + (long long)b * xbs + (long long)c * Di * HWi + (long long)r_lo * Wi;
+  for (int xo = threadIdx.x; xo < Wo; xo += blockDim.x) {
+    const Axis aw = axis_index(rw, xo, Wi, Wo, 1);
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+      const float* src = xc + min(db + p, Di - 1) * HWi;
+      for (int r = 0; r < nr; ++r) {
+        const float* q = src + (long long)r * Wi;
+        wrows[(p * nrmax + r) * Wo + xo] = aw.l0 * q[aw.i0] + aw.l1 * q[aw.i1];
+      }
+    }
+  }
+  __syncthreads();
+  const float sc = scale ? scale[c] : 1.f;
+  const float sh = scale ? shift[c] : 0.f;
+  const bool relu = flags & LEA_RELU;
+  const int wq = Wo / 4;
+  const int cells = ((oh1 - oh0) / 2) * wq;
+  const float4* w4 = reinterpret_cast<const float4*>(wrows);
+  const Axis ad2 = axis_index(rd2, pp, Do, D2, 1);
+  float* yc = y + (long long)b * ybs + (long long)c * Do * Ho * Wo;
+  float* y2c = y2 + (long long)b * y2bs + ((long long)c * D2 + pp) * H2 * W2;
+  for (int t = threadIdx.x; t < cells; t += blockDim.x) {
+    const int j = t / wq, q = t % wq;
+    const int oh = oh0 + 2 * j;
+    float v[2][2][4];  // [plane][row][column]
+#pragma unroll
+    for (int rr = 0; rr < 2; ++rr) {
+      const Axis ah = axis_index(rh, oh + rr, Hi, Ho, 1);
+      const int r0 = over ? 0 : ah.i0 - r_lo, r1 = over ? 0 : ah.i1 - r_lo;
+#pragma unroll
+      for (int pl = 0; pl < 2; ++pl) {
+        const int k0 = over ? 0 : ad[pl].i0 - db, k1 = over ? 0 : ad[pl].i1 - db;
+        const float4 a00 = w4[(k0 * nrmax + r0) * wq + q], a01 = w4[(k0 * nrmax + r1) * wq + q];
+        const float4 a10 = w4[(k1 * nrmax + r0) * wq + q], a11 = w4[(k1 * nrmax + r1) * wq + q];
+        const float p00[4] = {a00.x, a00.y, a00.z, a00.w}, p01[4] = {a01.x, a01.y, a01.z, a01.w};
+        const float p10[4] = {a10.x, a10.y, a10.z, a10.w}, p11[4] = {a11.x, a11.y, a11.z, a11.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float r = ad[pl].l0 * (ah.l0 * p00[e] + ah.l1 * p01[e]) + ad[pl].l1 * (ah.l0 * p10[e] + ah.l1 * p11[e]);
+          if (scale) r = r * sc + sh;
+          if (relu) r = fmaxf(r, 0.f);
+          v[pl][rr][e] = over ? __builtin_nanf("") : r;
+        }
+        *reinterpret_cast<float4*>(yc + ((long long)(2 * pp + pl) * Ho + oh + rr) * Wo + 4 * q) =
+            make_float4(v[pl][rr][0], v[pl][rr][1], v[pl][rr][2], v[pl][rr][3]);
+      }
+    }
+    // the block's resample to one y2 row pair of columns: trilerp's tree with the half-size axes
+    const Axis ah2 = axis_index(rh2, oh / 2, Ho, H2, 1);
+    float o2[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const Axis aw2 = axis_index(rw2, 2 * q + k, Wo, W2, 1);
+      float hl[2];
+#pragma unroll
+      for (int pl = 0; pl < 2; ++pl) {
+        float wl[2];
+#pragma unroll
+        for (int rr = 0; rr < 2; ++rr)
+          wl[rr] = aw2.l0 * ((aw2.i0 & 1) ? v[pl][rr][2 * k + 1] : v[pl][rr][2 * k]) +
+                   aw2.l1 * ((aw2.i1 & 1) ? v[pl][rr][2 * k + 1] : v[pl][rr][2 * k]);
+        hl[pl] = ah2.l0 * ((ah2.i0 & 1) ? wl[1] : wl[0]) + ah2.l1 * ((ah2.i1 & 1) ? wl[1] : wl[0]);
+      }
+      o2[k] = ad2.l0 * ((ad2.i0 & 1) ? hl[1] : hl[0]) + ad2.l1 * ((ad2.i1 & 1) ? hl[1] : hl[0]);
+    }
+    *reinterpret_cast<float2*>(y2c + (long long)(oh / 2) * W2 + 2 * q) = make_float2(o2[0], o2[1]);
+  }
+}
+
 int g_resample_mode = 0;  // lea_resample_set_mode: 0 auto, 1 row-staged, 2 gather
 
 }  // namespace lea
@@ -291,4 +391,55 @@ extern "C" int lea_resample3d_trilinear(const void* x, int64_t x_bstride, void* 
         (const float*)x, x_bstride, (float*)y, y_bstride, C, Di, Hi, Wi, Do, Ho, Wo, rd, rh, rw, ac,
         scale, shift, flags);
   return launch_status("lea_resample3d_trilinear");
+}
+
+// the largest even R whose W-lerped rows of three source planes fit 64 KB, or 0
+static int sep_down2_rows(int Hi, int Ho, int Wo, int* nrmax) {
+  for (int R = 8; R >= 2; R /= 2) {
+    const int n = lea::staged_rows(Hi, Ho, 1, R, 0);  // exact (common.h)
+    if ((size_t)3 * n * Wo * sizeof(float) > 65536) continue;
+    if (nrmax) *nrmax = n;
+    return R;
+  }
+  return 0;
+}
+
+// the shapes lea_resample3d_trilinear_down2 takes: an output volume with even D and H and
+// W % 4 == 0, no down-sampling along D (the three-plane window), rows that fit the LDS
+extern "C" int lea_resample3d_down2_supported(int Di, int Hi, int Wi, int Do, int Ho, int Wo, int dtype) {
+  if (dtype != LEA_F32 || Di <= 0 || Hi <= 0 || Wi <= 0 || Do < 2 || Ho < 2 || Wo < 4) return 0;
+  if (Do < Di || Do % 2 || Ho % 2 || Wo % 4 || Do > 2048) return 0;
+  return sep_down2_rows(Hi, Ho, Wo, nullptr) ? 1 : 0;
+}
+
+extern "C" int lea_resample3d_trilinear_down2(const void* x, int64_t x_bstride, void* y, int64_t y_bstride,
+                                              void* y2, int64_t y2_bstride, int B, int C, int Di, int Hi, int Wi,
+                                              int Do, int Ho, int Wo, const float* scale, const float* shift,
+                                              unsigned flags, int dtype, void* stream) {
+  using namespace lea;
+  const char* what = "lea_resample3d_trilinear_down2";
+  clear_error();
+  LEA_CHECK_FLAGS(flags, LEA_RELU, what);
+  LEA_CHECK_ARG(x && y && y2 && x != y && x != y2 && y != y2, "%s: null or aliased pointer", what);
+  LEA_CHECK_ARG((scale == nullptr) == (shift == nullptr), "%s: scale/shift must both be set or both NULL", what);
+  LEA_CHECK_ARG(B > 0 && C > 0 && Di > 0 && Hi > 0 && Wi > 0 && Do > 0 && Ho > 0 && Wo > 0, "%s: bad shape", what);
+  if (!lea_resample3d_down2_supported(Di, Hi, Wi, Do, Ho, Wo, dtype)) {
+    set_error("%s: needs LEA_F32, an output volume with even D and H and W %% 4 == 0, no down-sampling along D "
+              "and rows that fit the LDS (%d x %d x %d -> %d x %d x %d, dtype %d)", what, Di, Hi, Wi, Do, Ho, Wo,
+              dtype);
+    return LEA_E_UNSUPPORTED;
+  }
+  LEA_CHECK_ARG((long long)B * C * (Do / 2) <= 65535 && (long long)Ho * Wo < (1LL << 31),
+                "%s: grid too large (B*C*Do/2=%lld)", what, (long long)B * C * (Do / 2));
+  LEA_CHECK_ARG((uintptr_t)y % 16 == 0 && y_bstride % 4 == 0 && (uintptr_t)y2 % 8 == 0 && y2_bstride % 2 == 0,
+                "%s: y needs 16-byte, y2 8-byte alignment", what);
+  int nrmax = 0;
+  const int R = sep_down2_rows(Hi, Ho, Wo, &nrmax);
+  const size_t lds = (size_t)3 * nrmax * Wo * sizeof(float);
+  dim3 g((Ho + R - 1) / R, B * C * (Do / 2));
+  resample3d_sep_down2_f32<<<g, 256, lds, as_stream(stream)>>>(
+      (const float*)x, x_bstride, (float*)y, y_bstride, (float*)y2, y2_bstride, C, Di, Hi, Wi, Do, Ho, Wo,
+      axis_ratio(Di, Do, 1), axis_ratio(Hi, Ho, 1), axis_ratio(Wi, Wo, 1), axis_ratio(Do, Do / 2, 1),
+      axis_ratio(Ho, Ho / 2, 1), axis_ratio(Wo, Wo / 2, 1), R, nrmax, scale, shift, flags);
+  return launch_status(what);
 }

@@ -220,9 +220,13 @@ class CellGraphExecutor:
                         (torch.cat([f[0] for f in folded]).contiguous(),
                          torch.cat([f[1] for f in folded]).contiguous()))
 
-    def conv(self, name, x, out=None, accumulate=False, x2=None, size=None, residual=None):
+    def conv(self, name, x, out=None, accumulate=False, x2=None, size=None, residual=None, down=None,
+             down_only=False):
         """ConvBR ``name`` on x (or cat(x, x2)); with ``size`` != x's volume the input
-        is trilinearly resampled (align_corners=True) inside the conv."""
+        is trilinearly resampled (align_corners=True) inside the conv.  ``down``: the launch also
+        writes the output's trilinear resample to half its volume there (``down_only``: and leaves
+        ``out``, read as the residual, unfinished) -- the commuted up-sampling 1x1 and the
+        depth-paired Winograd tiles have that form; anywhere else it is an error."""
         p = self.p[name]
         cin = x.shape[1] + (x2.shape[1] if x2 is not None else 0)
         if cin != p.cin:
@@ -243,12 +247,24 @@ class CellGraphExecutor:
                 # interp and the 1x1 conv commute: conv at the low resolution, then
                 # resample the narrow result with the BN/ReLU epilogue into `out`
                 z = kernels.conv3d_bnrelu(x, p.packed, p.cout, 1, None, None, relu=False)
+                if down is not None:  # the level-down copy from the same launch
+                    return kernels.resample_trilinear_down2(z, size, out, down, p.scale, p.shift, p.relu)[0]
                 return kernels.resample_trilinear(z, size, True, out, p.scale, p.shift, p.relu)
+            if down is not None:
+                raise ValueError(f"{name}: no down-sampling form of this resampled conv")
             return kernels.conv3d_bnrelu_resampled(x, size, p.packed, p.cout, p.k, p.scale,
                                                    p.shift, p.relu, out, accumulate)
         if p.wino is not None and kernels.wino_preferred(x.shape[0], p.cout, p.cin, *x.shape[2:5]):
+            if down is not None:
+                if x2 is not None:
+                    raise ValueError(f"{name}: the down-sampling epilogue takes one input")
+                kernels.conv3d_bnrelu_wino_dp_down2(x, p.wino, p.cout, p.scale, p.shift, p.relu, out, down,
+                                                    accumulate, residual, only=down_only)
+                return out
             return kernels.conv3d_bnrelu_wino(x, p.wino, p.cout, p.scale, p.shift, p.relu, out,
                                               accumulate, x2, residual)
+        if down is not None:
+            raise ValueError(f"{name}: no down-sampling epilogue on this conv's engine")
         return kernels.conv3d_bnrelu(x, p.packed, p.cout, p.k, p.scale, p.shift, p.relu, out,
                                      accumulate, x2, residual)
 
@@ -309,12 +325,19 @@ class CellGraphExecutor:
     def _resample(x, size):
         return kernels.resample_trilinear(x, size)
 
+    def _cell_output_takes_down(self, i, size):
+        """Whether cell i's producers also write its output (at ``size``) one level down
+        (MatchingExecutor)."""
+        return False
+
     def cell(self, i, s0, s1, down=None):
         """Cell.forward (skip_model_3d.py:41-75 / new_model_2d.py:41-75).  The level
         change of s1 (:44-48) and the size match of s0 (:49-51) are fused into the
         1x1 preprocess convs (:52-53) that consume them.  ``down`` = (s0, s1) already at
         this cell's size (either may be None), written by their producers' down-sampling
-        epilogues: the preprocess convs then run at this level on them."""
+        epilogues: the preprocess convs then run at this level on them.  Where this cell's own
+        output is read only one level down (_cell_output_takes_down) that copy is left in
+        ``self._cell_down`` (None otherwise) for the caller to hand to the next cell."""
         cell = self.m.cells[i]
         c = cell.c_out
         if down is not None and down[0] is not None:
@@ -344,6 +367,13 @@ class CellGraphExecutor:
             out = self._empty(b, bm * c, size, s1)
         slot = {idx: self._channels(out, k * c, (k + 1) * c)
                 for k, idx in enumerate(range(n_states - bm, n_states))}
+        # the output's only reader is the next cell's down-sampling preprocess: its producers write
+        # that level too (dslot, the same channel order), the last state nothing else
+        dn = None
+        if self._cell_output_takes_down(i, size) and self._down_kernels_take(s1, c, self._volume(s1), size):
+            dn = self._empty(b, bm * c, tuple(n // 2 for n in size), s1)
+        self._cell_down = dn
+        dslot = {} if dn is None else {idx: self._channels(dn, k * c, (k + 1) * c) for k, idx in enumerate(slot)}
         group = self.s1_group.get(i, [])
         if memo is not None and memo[0] is s0 and memo[1] == size:
             s0 = memo[2]  # computed by the previous cell's stacked conv
@@ -361,7 +391,8 @@ class CellGraphExecutor:
             self._share_memo = (prev_input, size, self._channels(big, 0, c))
             s1 = self._channels(big, c, 2 * c)
         else:
-            s1 = self.conv(f"cells.{i}.preprocess", s1, out=slot.get(1), size=size)
+            s1 = self.conv(f"cells.{i}.preprocess", s1, out=slot.get(1), size=size,
+                           **({} if dn is None else {"down": dslot[1]}))
         states = [s0, s1]
         pairs = self.pair_steps.get(i)
         if pairs is not None:
@@ -403,14 +434,18 @@ class CellGraphExecutor:
             skips = [states[j] for k, j in terms if cell.op_kinds[k] != "conv"]
             if step in consumed:
                 skips.pop()
+            todo = [k for k, _ in terms if (step, k) not in done and cell.op_kinds[k] == "conv"]
             for k, j in terms:
                 if (step, k) in done or cell.op_kinds[k] != "conv":
                     continue
                 residual = None
                 if step not in written and skips:  # skip_connect term -> epilogue residual
                     residual = skips.pop()
+                kw = {}
+                if dn is not None and k == todo[-1]:  # the launch that finishes this state
+                    kw = {"down": dslot[len(states)], "down_only": len(states) == n_states - 1}
                 self.conv(f"cells.{i}._ops.{k}", states[j], out=dst, accumulate=step in written,
-                          residual=residual)
+                          residual=residual, **kw)
                 written.add(step)
             for t in skips:
                 if step in written:
@@ -433,6 +468,14 @@ class MatchingExecutor(CellGraphExecutor):
     # at L1 instead of each re-reading a whole L0 volume; LEASTEREO_FUSED_DOWN=0: the separate
     # resampling launches
     FUSED_DOWN = os.environ.get("LEASTEREO_FUSED_DOWN", "1") != "0"
+    # the same inside the cell chain, a switch of its own: conv1's only reader is cell 5's stacked
+    # 1x1 one level down (cells.5.share), so its epilogue writes that level and its own output never
+    # exists (lea_conv3d_bnrelu_wino_down2_cat); and cell 10's output, read only by the last cell's
+    # preprocess one level down: its producers write that level too (s1's up-sampling through
+    # lea_resample3d_trilinear_down2, each step's finishing launch through
+    # lea_conv3d_bnrelu_wino_dp_down2) and the last state's full-resolution values never exist;
+    # LEASTEREO_FUSED_DOWN_CELLS=0: the resampling 1x1s
+    FUSED_DOWN_CELLS = os.environ.get("LEASTEREO_FUSED_DOWN_CELLS", "1") != "0"
 
     def run(self, x):
         """newMatching.forward (skip_model_3d.py:140-174): [B,64,D3,H3,W3] -> [B,1,D3,H3,W3]."""
@@ -476,6 +519,59 @@ class MatchingExecutor(CellGraphExecutor):
                 and cells[0].downup_sample < 0 and cells[0].dims == 3
                 and all(n % 2 == 0 and scale_dimension(n, 0.5) == n // 2 for n in vol))
 
+    def _conv1_takes_down(self, vol):
+        """conv1 (cat(outs[1], outs[4]) -> cell 5's s1) has one reader, cell 5's stacked 1x1
+        (cells.5.share: cell 5's s1 and, through the share memo, cell 6's s0), which reads it at
+        exactly half of ``vol``: conv1 may write that level itself.  Never with a tap installed
+        nor in the c8 layout (as _cell0_takes_down)."""
+        cells = self.m.cells
+        return (self.FUSED_DOWN_CELLS and self.tap is None and not isinstance(self, _C8Layout)
+                and len(cells) == 12 and "cells.5.share" in self.p
+                and cells[5].downup_sample < 0 and cells[5].dims == 3
+                and all(n % 2 == 0 and scale_dimension(n, 0.5) == n // 2 for n in vol))
+
+    def _cell_output_takes_down(self, i, size):
+        """Cell i's output (at ``size``) has one reader, the down-sampling ``preprocess`` of the
+        next cell, at exactly half of an even volume: cell i + 1 is the last cell (no cell i + 2
+        reads the output as its s0), takes its s1 alone (no ``share``), and neither conv1 nor conv2
+        reads cell i.  The producers that have a down-sampling form must be the ones that run: s1
+        from the commuted up-sampling 1x1, every step finished by a conv launch (no skip term left
+        to add), the step launches not paired.  Never with a tap installed nor in the c8 layout."""
+        cells = self.m.cells
+        n = len(cells)
+        if not (self.FUSED_DOWN_CELLS and self.tap is None and not isinstance(self, _C8Layout)
+                and 0 <= i and i + 2 == n and not (n == 12 and i in (1, 4, 8))):
+            return False
+        cell, nxt = cells[i], cells[i + 1]
+        pre = self.p.get(f"cells.{i}.preprocess")
+        return (cell.dims == 3 and nxt.dims == 3
+                and nxt.downup_sample < 0 and f"cells.{i + 1}.share" not in self.p
+                and cell.downup_sample > 0 and f"cells.{i}.share" not in self.p
+                and pre is not None and pre.k == 1
+                and 2 + cell.steps - cell.block_multiplier == 1
+                and self.pair_steps.get(i) is None and self.s0_pair.get(i) is None
+                and all(cell.op_kinds[op] == "conv" for terms in cell.plan for op, _ in terms)
+                and all(self._finishing_op(i, step) is not None for step in range(len(cell.plan)))
+                and all(m % 2 == 0 and scale_dimension(m, 0.5) == m // 2 for m in size) and size[2] % 4 == 0)
+
+    def _finishing_op(self, i, step):
+        """The op whose launch writes step ``step``'s state last (the s1 sibling group runs first),
+        where that launch is a Winograd conv; else None."""
+        group = self.s1_group.get(i, [])
+        rest = [op for op, _ in self.m.cells[i].plan[step] if (step, op) not in group]
+        if not rest or self.p[f"cells.{i}._ops.{rest[-1]}"].wino is None:
+            return None
+        return rest[-1]
+
+    def _down_kernels_take(self, like, c, in_size, size):
+        """The *_supported queries of the launches _cell_output_takes_down's route runs, for f32
+        device tensors like ``like`` (the cell's s1)."""
+        b = like.shape[0]
+        return (like.is_cuda and like.dtype == torch.float32
+                and kernels.wino_preferred(b, c, c, *size)
+                and kernels.wino_dp_down2_kernel_name(b, c, c, *size) is not None
+                and kernels.resample_down2_shape_supported(in_size, size))
+
     def _cv_stem_pack(self, wl, wr):
         return kernels.pack_conv2d_weight(wl), kernels.pack_conv2d_weight(wr)
 
@@ -502,17 +598,30 @@ class MatchingExecutor(CellGraphExecutor):
             self._emit("stem1", stem1)
         outs = []
         prev = (stem0, stem1)
+        cell_down = None
         n = len(self.m.cells)
         for i in range(n):
+            down = (stem0_down, stem1_down) if i == 0 else None
+            if cell_down is not None:  # cell i - 1 wrote its output at this cell's level as well
+                down = (None, cell_down)
             if i == 5 and n == 12:   # :150-151, cat read in place by the conv
-                fused = self.conv("conv1", outs[1][1], x2=outs[4][1])
-                self._emit("conv1", fused)
-                prev = (outs[4][0], fused)
+                pc, xa, xb = self.p["conv1"], outs[1][1], outs[4][1]
+                if (self._conv1_takes_down(self._volume(xa)) and pc.wino is not None
+                        and kernels.wino_preferred(xa.shape[0], pc.cout, pc.cin, *xa.shape[2:5])
+                        and kernels.conv3d_wino_down2_cat_supported(xa, xb, pc.cout)):
+                    down = (None, kernels.conv3d_bnrelu_wino_down2_cat(xa, xb, pc.wino, pc.cout, pc.scale,
+                                                                       pc.shift, pc.relu))
+                    prev = (outs[4][0], None)
+                else:
+                    fused = self.conv("conv1", xa, x2=xb)
+                    self._emit("conv1", fused)
+                    prev = (outs[4][0], fused)
             elif i == 9 and n == 12:  # :155-156
                 fused = self.conv("conv2", outs[4][1], x2=outs[8][1])
                 self._emit("conv2", fused)
                 prev = (outs[8][0], fused)
-            o = self.cell(i, prev[0], prev[1], down=(stem0_down, stem1_down) if i == 0 else None)
+            o = self.cell(i, prev[0], prev[1], down=down)
+            cell_down, self._cell_down = self._cell_down, None
             self._emit(f"cell{i}", o[1])
             outs.append(o)
             prev = o

@@ -465,6 +465,52 @@ def resample_trilinear(x: torch.Tensor, size, align_corners: bool = True,
     return out
 
 
+def resample_down2_shape_supported(in_size, size) -> bool:
+    """lea_resample3d_down2_supported for f32: resampling ``in_size`` -> ``size`` (even D and H,
+    W % 4 == 0, no down-sampling along D) with the half-size side output."""
+    return bool(_lib.load().lea_resample3d_down2_supported(*(int(n) for n in in_size), *(int(n) for n in size),
+                                                          LEA_F32))
+
+
+def resample_down2_supported(x: torch.Tensor, size) -> bool:
+    """Whether resample_trilinear_down2 takes x -> ``size``: an f32 NCDHW device tensor and a shape
+    resample_down2_shape_supported accepts."""
+    if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 5:
+        return False
+    d, h, w = x.shape[2:]
+    if x.stride()[1:] != (d * h * w, h * w, w, 1):
+        return False
+    return resample_down2_shape_supported((d, h, w), size)
+
+
+def resample_trilinear_down2(x: torch.Tensor, size, out: torch.Tensor | None = None,
+                             down: torch.Tensor | None = None, scale: torch.Tensor | None = None,
+                             shift: torch.Tensor | None = None, relu: bool = False):
+    """(y, y2): y = resample_trilinear(x, size, True, out, scale, shift, relu) and y2 =
+    resample_trilinear(y, size / 2), both bit for bit, as one launch that never reads y back;
+    ``out`` / ``down`` may be channel slices of larger tensors."""
+    _require_cuda(x, out, down, scale, shift)
+    b, c, di, hi, wi = x.shape
+    do, ho, wo = (int(n) for n in size)
+    xbs = _check_volume_view(x, "x")
+    if out is None:
+        out = torch.empty((b, c, do, ho, wo), device=x.device, dtype=x.dtype)
+    if down is None:
+        down = torch.empty((b, c, do // 2, ho // 2, wo // 2), device=x.device, dtype=x.dtype)
+    if tuple(out.shape) != (b, c, do, ho, wo) or tuple(down.shape) != (b, c, do // 2, ho // 2, wo // 2):
+        raise ValueError(f"out / down shapes {tuple(out.shape)} / {tuple(down.shape)} for {(b, c, do, ho, wo)}")
+    ybs, dbs = _check_volume_view(out, "out"), _check_volume_view(down, "down")
+    rec = None if _probe is None else _probe_launch(
+        "resample3d_sep_down2_f32", 0.0, 4.0 * (x.numel() + out.numel() + down.numel()))
+    check(_lib.load().lea_resample3d_trilinear_down2(
+        x.data_ptr(), xbs, out.data_ptr(), ybs, down.data_ptr(), dbs, b, c, di, hi, wi, do, ho, wo,
+        scale.data_ptr() if scale is not None else None,
+        shift.data_ptr() if shift is not None else None, LEA_RELU if relu else 0, LEA_F32,
+        _stream()), "lea_resample3d_trilinear_down2")
+    _probe_end(rec)
+    return out, down
+
+
 def tapsum_upsample(q: torch.Tensor, cout: int, size, scale: torch.Tensor | None = None,
                     shift: torch.Tensor | None = None, relu: bool = False) -> torch.Tensor:
     """conv3x3x3(upsample(y)) from q = per-tap partial sums of y (27*cout channels at
@@ -1622,9 +1668,14 @@ def conv3d_bnrelu_wino(x: torch.Tensor, packed: torch.Tensor, cout: int,
     return out
 
 
-def wino_down2_kernel_name(b, cin, cout, d, h, w):
-    """The instantiation conv3d_bnrelu_wino_down2 launches for this shape, or None."""
-    name = _lib.load().lea_conv3d_wino_down2_kernel_name(b, cin, cout, d, h, w)
+def wino_down2_kernel_name(b, cin, cout, d, h, w, cin2=0):
+    """The instantiation conv3d_bnrelu_wino_down2 launches for this shape (cin2 > 0: the
+    two-input form, cin2 of the cin channels from x2), or None."""
+    lib = _lib.load()
+    if cin2:
+        name = lib.lea_conv3d_wino_down2_cat_kernel_name(b, cin, cin2, cout, d, h, w)
+    else:
+        name = lib.lea_conv3d_wino_down2_kernel_name(b, cin, cout, d, h, w)
     return name.decode() if name else None
 
 
@@ -1632,12 +1683,28 @@ def conv3d_wino_down2_supported(x: torch.Tensor, cout: int) -> bool:
     """Whether conv3d_bnrelu_wino_down2 takes this input: an f32 NCDHW device tensor (16-byte
     aligned, whole 16-byte batch strides) of a shape the planner puts on the F(4,3) x F(4,3)
     tile (lea_conv3d_wino_down2_supported: even D / H, W % 4 == 0)."""
-    if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 5:
-        return False
+    return _wino_down2_supported(x, cout, None)
+
+
+def conv3d_wino_down2_cat_supported(x: torch.Tensor, x2: torch.Tensor, cout: int) -> bool:
+    """The same for cat(x, x2) read in place (lea_conv3d_wino_down2_cat_supported): both sources
+    aligned, neither empty, channel counts in multiples of 4."""
+    return _wino_down2_supported(x, cout, x2)
+
+
+def _wino_down2_supported(x, cout, x2):
+    for t in (x,) if x2 is None else (x, x2):
+        if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 5:
+            return False
+        d, h, w = t.shape[2:]
+        if t.data_ptr() % 16 or t.stride(0) % 4 or t.stride()[1:] != (d * h * w, h * w, w, 1):
+            return False
     b, cin, d, h, w = x.shape
-    if x.data_ptr() % 16 or x.stride(0) % 4 or x.stride()[1:] != (d * h * w, h * w, w, 1):
+    if x2 is None:
+        return bool(_lib.load().lea_conv3d_wino_down2_supported(b, cin, cout, d, h, w))
+    if x2.shape[0] != b or tuple(x2.shape[2:]) != (d, h, w) or x2.device != x.device:
         return False
-    return bool(_lib.load().lea_conv3d_wino_down2_supported(b, cin, cout, d, h, w))
+    return bool(_lib.load().lea_conv3d_wino_down2_cat_supported(b, cin + x2.shape[1], x2.shape[1], cout, d, h, w))
 
 
 def conv3d_bnrelu_wino_down2(x: torch.Tensor, packed: torch.Tensor, cout: int,
@@ -1645,26 +1712,121 @@ def conv3d_bnrelu_wino_down2(x: torch.Tensor, packed: torch.Tensor, cout: int,
                              relu: bool = True) -> torch.Tensor:
     """resample_trilinear(conv3d_bnrelu_wino(x, ...), (D/2, H/2, W/2)) bit for bit, as one launch
     whose epilogue down-samples (the full-resolution output is never written)."""
-    _require_cuda(x, packed, scale, shift)
+    return _wino_down2(x, None, packed, cout, scale, shift, relu)
+
+
+def conv3d_bnrelu_wino_down2_cat(x: torch.Tensor, x2: torch.Tensor, packed: torch.Tensor, cout: int,
+                                 scale: torch.Tensor | None, shift: torch.Tensor | None,
+                                 relu: bool = True) -> torch.Tensor:
+    """The same on cat(x, x2) read in place, as conv3d_bnrelu_wino(x, ..., x2=x2) takes it
+    (lea_conv3d_bnrelu_wino_down2_cat)."""
+    return _wino_down2(x, x2, packed, cout, scale, shift, relu)
+
+
+def _wino_down2(x, x2, packed, cout, scale, shift, relu):
+    _require_cuda(x, x2, packed, scale, shift)
     b, cin, d, h, w = x.shape
     xbs = _check_volume_view(x, "x")
+    cin2, x2bs = 0, 0
+    if x2 is not None:
+        if x2.shape[0] != b or tuple(x2.shape[2:]) != (d, h, w):
+            raise ValueError("x2 must match x in batch and volume")
+        cin2 = x2.shape[1]
+        x2bs = _check_volume_view(x2, "x2")
+    cin += cin2
     out = torch.empty((b, cout, d // 2, h // 2, w // 2), device=x.device, dtype=x.dtype)
     rec = None
     if _probe is not None:
-        name = wino_down2_kernel_name(b, cin, cout, d, h, w) or "conv3d_wino44_down2_kernel"
+        name = wino_down2_kernel_name(b, cin, cout, d, h, w, cin2) or (
+            "conv3d_wino44_down2_cat_kernel" if cin2 else "conv3d_wino44_down2_kernel")
         rec = _probe_begin(b, cin, cout, d, h, w, 3, False, b * d * h * w, False, name=name,
                            mfma_scale=wino_mfma_scale(cout, "conv3d_wino44_kernel"))  # (the same tile)
         if rec is not None:  # the bytes really moved: input + weights + the L1 output
-            nbytes = 4.0 * (x.numel() + out.numel()) + 4.0 * cout * cin * 27
+            nbytes = 4.0 * (b * cin * d * h * w + out.numel()) + 4.0 * cout * cin * 27
             rec = rec[:3] + (nbytes,) + rec[4:]
-    check(_lib.load().lea_conv3d_bnrelu_wino_down2(
+    lib = _lib.load()
+    sp = scale.data_ptr() if scale is not None else None
+    hp = shift.data_ptr() if shift is not None else None
+    flags = LEA_RELU if relu else 0
+    if x2 is None:
+        check(lib.lea_conv3d_bnrelu_wino_down2(
+            x.data_ptr(), xbs, packed.data_ptr(), sp, hp,
+            out.data_ptr(), out.stride(0), b, cin, cout, d, h, w, flags, LEA_F32, _stream()),
+            "lea_conv3d_bnrelu_wino_down2")
+    else:
+        check(lib.lea_conv3d_bnrelu_wino_down2_cat(
+            x.data_ptr(), xbs, x2.data_ptr(), x2bs, cin2, packed.data_ptr(), sp, hp,
+            out.data_ptr(), out.stride(0), b, cin, cout, d, h, w, flags, LEA_F32, _stream()),
+            "lea_conv3d_bnrelu_wino_down2_cat")
+    _probe_end(rec)
+    return out
+
+
+def wino_dp_down2_kernel_name(b, cin, cout, d, h, w, only=False):
+    """The instantiation conv3d_bnrelu_wino_dp_down2 launches for this shape, or None."""
+    name = _lib.load().lea_conv3d_wino_dp_down2_kernel_name(b, cin, cout, d, h, w, 1 if only else 0)
+    return name.decode() if name else None
+
+
+def conv3d_wino_dp_down2_supported(x: torch.Tensor, cout: int) -> bool:
+    """Whether conv3d_bnrelu_wino_dp_down2 takes this input: an f32 NCDHW device tensor (16-byte
+    aligned, whole 16-byte batch strides) of a shape the planner puts on a depth-paired tile
+    (lea_conv3d_wino_dp_down2_supported: cout <= 8, even D / H, W % 4 == 0)."""
+    if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 5:
+        return False
+    b, cin, d, h, w = x.shape
+    if x.data_ptr() % 16 or x.stride(0) % 4 or x.stride()[1:] != (d * h * w, h * w, w, 1):
+        return False
+    return bool(_lib.load().lea_conv3d_wino_dp_down2_supported(b, cin, cout, d, h, w))
+
+
+def conv3d_bnrelu_wino_dp_down2(x: torch.Tensor, packed: torch.Tensor, cout: int,
+                                scale: torch.Tensor | None, shift: torch.Tensor | None, relu: bool,
+                                out: torch.Tensor | None, down: torch.Tensor, accumulate: bool = False,
+                                residual: torch.Tensor | None = None, only: bool = False) -> torch.Tensor:
+    """conv3d_bnrelu_wino (couts <= 8: the depth-paired tiles) whose epilogue also writes ``down``
+    [B, cout, D/2, H/2, W/2] = resample_trilinear(out, half), bit for bit.  ``only``: ``out`` is
+    read as the residual (``accumulate``) but not written -- its final values never exist."""
+    _require_cuda(x, packed, scale, shift, out, down, residual)
+    b, cin, d, h, w = x.shape
+    xbs = _check_volume_view(x, "x")
+    if out is None:
+        if not only or accumulate:
+            raise ValueError("no out: the `only` form without accumulate")
+        ybs = 0
+    else:
+        out, ybs = _conv_out(x.shape, cout, (d, h, w), out, accumulate, x.device, x.dtype)
+    if tuple(down.shape) != (b, cout, d // 2, h // 2, w // 2):
+        raise ValueError(f"down shape {tuple(down.shape)} != {(b, cout, d // 2, h // 2, w // 2)}")
+    dbs = _check_volume_view(down, "down")
+    if accumulate:
+        rptr, rbs = _residual(out, True, residual, ybs)
+    elif residual is not None:
+        _require_cuda(residual)
+        if tuple(residual.shape) != (b, cout, d, h, w):
+            raise ValueError(f"residual shape {tuple(residual.shape)} != {(b, cout, d, h, w)}")
+        rptr, rbs = residual.data_ptr(), _check_volume_view(residual, "residual")
+    else:
+        rptr, rbs = None, 0
+    flags = (LEA_RELU if relu else 0) | (LEA_RESIDUAL if rptr is not None else 0)
+    rec = None
+    if _probe is not None:
+        name = wino_dp_down2_kernel_name(b, cin, cout, d, h, w, only) or "conv3d_wino_dp_down2_kernel"
+        rec = _probe_begin(b, cin, cout, d, h, w, 3, rptr is not None, b * d * h * w, False, name=name,
+                           mfma_scale=wino_mfma_scale(cout, wino_kernel_name(b, cout, d, h, w, cin=cin)))
+        if rec is not None:  # the bytes really moved: input, weights, residual, L0 output unless `only`, L1
+            vox = b * cout * d * h * w
+            nbytes = 4.0 * (x.numel() + (vox if rptr is not None else 0) + (0 if only else vox) + down.numel()) \
+                + 4.0 * cout * cin * 27
+            rec = rec[:3] + (nbytes,) + rec[4:]
+    check(_lib.load().lea_conv3d_bnrelu_wino_dp_down2(
         x.data_ptr(), xbs, packed.data_ptr(),
         scale.data_ptr() if scale is not None else None,
         shift.data_ptr() if shift is not None else None,
-        out.data_ptr(), out.stride(0), b, cin, cout, d, h, w, LEA_RELU if relu else 0, LEA_F32, _stream()),
-        "lea_conv3d_bnrelu_wino_down2")
+        rptr, rbs, None if only else out.data_ptr(), ybs, down.data_ptr(), dbs, b, cin, cout, d, h, w, flags,
+        LEA_F32, _stream()), "lea_conv3d_bnrelu_wino_dp_down2")
     _probe_end(rec)
-    return out
+    return down
 
 
 def conv3d_bnrelu_costvolume_wino(fl: torch.Tensor, fr: torch.Tensor, maxdisp: int,
