@@ -477,6 +477,61 @@ int lea_disparity_speckle_f32(const float* disp, const uint8_t* exclude, int B, 
                               int32_t* labels, int32_t* size, uint8_t* state, float* filtered,
                               void* stream);
 
+/* Point cloud (additive: the ABI number stays 14): the reprojection of a disparity map to 3-D
+ * through a 4 x 4 matrix (OpenCV's reprojectImageTo3D), the validity of every pixel, and the
+ * valid points compacted in row-major pixel order with their colours, pixel indices and
+ * normals, on the device.  It is the last stage of the chain: after the left-right check, the
+ * speckle filter and the refinement.  Neither entry synchronises the host, allocates or reads
+ * anything back: the number of points stays on the device.
+ *
+ * Inputs.  disp: [B, H, W] f32.  exclude: [B, H, W] bytes or NULL (the state of
+ * lea_disparity_lr_check / lea_disparity_speckle_f32 can be passed as it is; any non-zero byte
+ * excludes).  image: uint8 [B, H, W, pix_stride] or NULL, pix_stride 3 or 4, the first three
+ * channels are the colour (what lea_standardize_crop_u8 takes).  Q: f32 [16] per image on the
+ * device, row-major, image b's at Q + b * q_bstride (floats; 0 = one matrix for all, else
+ * >= 16).  min_disp, max_disp: not NaN, infinities allowed.  normal_max_diff: >= 0, +inf
+ * allowed.  capacity: rows per image of the compact outputs.
+ * Point.  With d = disp[y, x] and every product and sum rounded on its own, in this order:
+ *   h_r = ((Q[r][0] * x + Q[r][1] * y) + Q[r][2] * d) + Q[r][3],  r = 0 .. 3
+ *   P = (h_0 / h_3, h_1 / h_3, h_2 / h_3)      (IEEE divisions)
+ * The pixel is valid when exclude is 0 (or NULL), d is finite, min_disp < d <= max_disp, and
+ * the three coordinates of P are finite (they are not where h_3 = 0).
+ * Normal of a valid pixel p.  Along an axis a neighbour q is usable when it is inside the
+ * image, valid, and fabsf(d_q - d_p) <= normal_max_diff (the speckle filter's connectivity).
+ * dx = P(x + 1) - P(x - 1) with both usable, one-sided against P(p) with one, absent with
+ * none; dy the same along y.  c = dx x dy, n = c / |c| (sqrtf of the sum of squares), negated
+ * when n . P > 0: towards a camera at the origin.  (0, 0, 0) when dx or dy is absent or |c|
+ * is 0 or not finite.
+ * Outputs, each optional through NULL (never written), at least one required:
+ *   points  [B, H, W, 3] f32   the organised cloud; a quiet NaN in all three where not valid
+ *   valid   [B, H, W] u8       1 / 0
+ *   count   [B] int32          the number of valid pixels, also where it exceeds capacity
+ *   xyz     [B, capacity, 3] f32   row k of image b: the point of its k-th valid pixel in
+ *                                  row-major order, the bits of points at that pixel
+ *   rgb     [B, capacity, 3] u8    its colour (needs image)
+ *   index   [B, capacity] int32    its y * W + x
+ *   normals [B, capacity, 3] f32   its normal
+ * Rows at and beyond min(count[b], capacity) are not written; with count[b] > capacity the
+ * first capacity points are kept.  A row is a function of the validity map alone (ballots and
+ * an exclusive scan, no atomics), so every output is the same bits call after call.
+ * workspace: lea_disparity_pointcloud_workspace_bytes(B, H, W) bytes on the device (0 for a
+ * non-positive size), 4-byte aligned; its contents need not be initialised.  Three launches
+ * on the stream (two without a compact output, one with points / valid alone); capturable,
+ * and a replay reads Q anew.
+ * LEA_E_INVALID, before any launch: a null disp, Q or workspace; every output null; rgb
+ * without image; pix_stride not 3 or 4 with an image; B, H or W < 1 (or B above 65535,
+ * B*H*W above 2^31 - 1); a Q stride that is neither 0 nor >= 16; capacity negative, or 0 with
+ * a compact output; min_disp, max_disp or normal_max_diff NaN, normal_max_diff negative; a
+ * misaligned workspace; an output overlapping an input, the workspace or another output; the
+ * workspace overlapping an input. */
+size_t lea_disparity_pointcloud_workspace_bytes(int B, int H, int W);
+int lea_disparity_pointcloud_f32(const float* disp, const uint8_t* exclude, const void* image,
+                                 int pix_stride, const float* Q, int64_t q_bstride, int B, int H,
+                                 int W, float min_disp, float max_disp, float normal_max_diff,
+                                 int capacity, void* workspace, float* points, uint8_t* valid,
+                                 int32_t* count, float* xyz, uint8_t* rgb, int32_t* index,
+                                 float* normals, void* stream);
+
 /* ---- bf16 path (BASELINE configs 3 and 4) ----
  * Activations are bf16 in the "c8" layout: NCDHW with channels blocked by 8
  * innermost, x[b][c/8][d][h][w][c%8] (one voxel's 8 channels = one 16-byte word;

@@ -79,6 +79,10 @@ SIGNATURES = {
     "lea_disparity_speckle_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
     "lea_disparity_speckle_f32": (_i, [_p, _p, _i, _i, _i, ctypes.c_float, _i, ctypes.c_float, _p, _p, _p, _p, _p,
                                        _p]),
+    # point cloud: reprojection, ordered compaction, normals (csrc/pointcloud.hip)
+    "lea_disparity_pointcloud_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "lea_disparity_pointcloud_f32": (_i, [_p, _p, _p, _i, _p, _i64, _i, _i, _i, ctypes.c_float, ctypes.c_float,
+                                          ctypes.c_float, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     # bf16 path (c8 layout)
     "lea_conv3d_packed_elems_bf16": (ctypes.c_size_t, [_i, _i, _i]),
     "lea_conv3d_pack_weights_bf16": (_i, [_p, _p, _i, _i, _i, _p]),

@@ -115,5 +115,22 @@ def obtain_predict_args(argv=None):
     parser.add_argument("--speckle_diff", type=float, default=1.0, metavar="D",
                         help="largest disparity step in pixels between connected neighbours under --speckle "
                              "(OpenCV's speckleRange, 1-2 recommended; untuned)")
+    parser.add_argument("--pointcloud", type=int, default=0,
+                        help="1: also write {index}.ply, the point cloud of the best map the other flags made "
+                             "(the refined map under --refine, else the disparity without the pixels --speckle "
+                             "and --lr_check flag), coloured from the left image; needs --pc_focal and "
+                             "--pc_baseline (not in the reference)")
+    parser.add_argument("--pc_focal", type=float, default=0.0, metavar="PX",
+                        help="focal length of the rectified pair in pixels under --pointcloud")
+    parser.add_argument("--pc_baseline", type=float, default=0.0, metavar="M",
+                        help="baseline of the pair under --pointcloud; its unit is the cloud's")
+    parser.add_argument("--pc_cx", type=float, default=None, metavar="X",
+                        help="principal point of the left image under --pointcloud (default: the image's centre)")
+    parser.add_argument("--pc_cy", type=float, default=None, metavar="Y", help="see --pc_cx")
+    parser.add_argument("--pc_max_depth", type=float, default=0.0, metavar="M",
+                        help="drop the points farther than this under --pointcloud (0 = keep all): the "
+                             "disparities at or below focal * baseline / M")
+    parser.add_argument("--pc_normals", type=int, default=0,
+                        help="1: also write the normals of the points under --pointcloud")
     add_leastereo_args(parser)
     return parser.parse_args(argv)

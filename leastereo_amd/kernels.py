@@ -12,6 +12,7 @@ import contextlib
 import math
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -948,6 +949,146 @@ def speckle_filter(disp: torch.Tensor, exclude: torch.Tensor = None, max_size: i
                                         _stream()), "lea_disparity_speckle_f32")
     _probe_end(rec)
     return DisparitySpeckle(disp, state, size, labels, filtered)
+
+
+# ---- point cloud: reprojection, ordered compaction, normals (csrc/pointcloud.hip) ----
+
+HostPointCloud = collections.namedtuple("HostPointCloud", "count xyz rgb index normals")
+HostPointCloud.__doc__ = """What ``PointCloud.to_host`` returns: ``count`` (int, the valid pixels of the item, which may
+exceed the rows) and the first min(count, capacity) rows of each compact array as numpy arrays (``None`` where the
+call did not make one)."""
+
+
+class PointCloud(collections.namedtuple("PointCloud", "points valid count xyz rgb index normals")):
+    """What ``reproject`` returns, on the device (``None`` where not asked for):
+      points   float32 [B, H, W, 3]: the organised cloud, NaN in all three where the pixel is not valid
+      valid    uint8 [B, H, W]: 1 / 0
+      count    int32 [B]: the number of valid pixels, also where it exceeds the capacity
+      xyz      float32 [B, capacity, 3]: the valid points in row-major pixel order
+      rgb      uint8 [B, capacity, 3]: their colours
+      index    int32 [B, capacity]: their y * W + x
+      normals  float32 [B, capacity, 3]: their normals, towards the camera; (0, 0, 0) where there is none
+    The leading B is absent where ``disp`` came as [H, W].  Rows at and beyond min(count, capacity) are
+    uninitialised memory: ``to_host`` cuts them off."""
+    __slots__ = ()
+
+    def to_host(self, b: int = 0) -> HostPointCloud:
+        """The one place that synchronises: reads ``count[b]`` and copies the first min(count, capacity) rows of
+        each compact array of item ``b`` to numpy."""
+        if self.count is None:
+            raise ValueError("PointCloud.to_host: the call made no compact output (want_compact=False)")
+        batched = self.count.dim() == 1
+        if not batched and b != 0:
+            raise IndexError(f"PointCloud.to_host: item {b} of an unbatched cloud")
+        n = int(self.count[b] if batched else self.count)
+        rows = None
+        out = []
+        for t in (self.xyz, self.rgb, self.index, self.normals):
+            if t is None:
+                out.append(None)
+                continue
+            t = t[b] if batched else t
+            rows = min(n, t.shape[0])
+            out.append(t[:rows].cpu().numpy())
+        return HostPointCloud(n, *out)
+
+
+def _as_q(Q, b: int, device) -> torch.Tensor:
+    """Q as a float32 tensor on the device, [4, 4] or [b, 4, 4]; one that is that already is used in
+    place (a captured call then replays with what it holds at the time)."""
+    if isinstance(Q, torch.Tensor):
+        q = Q
+    else:
+        q = torch.from_numpy(np.ascontiguousarray(np.asarray(Q, dtype=np.float64)).astype(np.float32))
+    if tuple(q.shape) not in ((4, 4), (b, 4, 4)):
+        raise ValueError(f"reproject: Q must be [4, 4] or [{b}, 4, 4], got {tuple(q.shape)}")
+    if not q.dtype.is_floating_point:
+        raise ValueError(f"reproject: Q must be a floating-point matrix, got {q.dtype}")
+    return q.to(device=device, dtype=torch.float32).contiguous()
+
+
+def reproject(disp: torch.Tensor, Q, image: torch.Tensor = None, exclude: torch.Tensor = None,
+              min_disp: float = 0.0, max_disp: float = float("inf"), normals: bool = False,
+              normal_max_diff: float = 1.0, capacity: int = None, want_points: bool = False,
+              want_valid: bool = False, want_compact: bool = True) -> PointCloud:
+    """``lea_disparity_pointcloud_f32`` (include/leastereo_hip.h): the points
+    P = (h0, h1, h2) / h3, h = Q (x, y, d, 1), of the pixels of a disparity map that are valid
+    (``exclude`` 0, d finite, ``min_disp`` < d <= ``max_disp``, P finite), organised
+    (``want_points``, ``want_valid``) and compacted in row-major pixel order (``want_compact``:
+    count, xyz, index; rgb with ``image``; ``normals=True`` for the normals, whose neighbours
+    must lie within ``normal_max_diff`` px of disparity).  ``disp`` [B, H, W] or [H, W] float32
+    on the device; ``Q`` a 4 x 4 or [B, 4, 4] array or tensor (``pointcloud.q_matrix``), a
+    float32 device tensor is read in place at every launch and replay; ``image`` uint8
+    [B, H, W, 3|4] or [H, W, 3|4] on the device (what ``load_images`` decodes); ``exclude`` as
+    for ``speckle_filter`` (``DisparityLR.state`` / ``DisparitySpeckle.state`` go as they are).
+    ``capacity``: rows per item of the compact arrays, H * W by default; the first ``capacity``
+    points are kept.  Up to three launches on the current stream; nothing is read back, the
+    number of points stays on the device (``PointCloud.to_host``)."""
+    if not isinstance(disp, torch.Tensor) or disp.dim() not in (2, 3):
+        raise ValueError(f"reproject: disp must be [B, H, W] or [H, W], got "
+                         f"{tuple(disp.shape) if isinstance(disp, torch.Tensor) else type(disp)}")
+    _require_cuda(disp)
+    shape = tuple(disp.shape)
+    if 0 in shape:
+        raise ValueError(f"reproject: empty map {shape}")
+    batched = len(shape) == 3
+    b = shape[0] if batched else 1
+    h, w = shape[-2:]
+    if b * h * w > 2 ** 31 - 1:
+        raise ValueError(f"reproject: B * H * W = {b * h * w} is above 2^31 - 1")
+    if exclude is not None:
+        if (not isinstance(exclude, torch.Tensor) or not exclude.is_cuda or tuple(exclude.shape) != shape
+                or exclude.dtype not in (torch.uint8, torch.bool)):
+            raise ValueError(f"reproject: exclude must be a {shape} uint8 or bool tensor on the device")
+    img = None
+    if image is not None:
+        if (not isinstance(image, torch.Tensor) or not image.is_cuda or image.dtype != torch.uint8
+                or tuple(image.shape[:-1]) != shape or image.shape[-1] not in (3, 4)):
+            raise ValueError(f"reproject: image must be a uint8 {shape + ('3|4',)} tensor on the device")
+        img = image.contiguous()
+    for name, v in (("min_disp", min_disp), ("max_disp", max_disp), ("normal_max_diff", normal_max_diff)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or math.isnan(v):
+            raise ValueError(f"reproject: {name} {v} must be a number")
+    if normal_max_diff < 0:
+        raise ValueError(f"reproject: normal_max_diff {normal_max_diff} must be >= 0")
+    if capacity is None:
+        capacity = h * w
+    if isinstance(capacity, bool) or not isinstance(capacity, int) or not 1 <= capacity <= 2 ** 31 - 1:
+        raise ValueError(f"reproject: capacity {capacity} must be an integer in 1 .. 2^31 - 1")
+    if normals and not want_compact:
+        raise ValueError("reproject: the normals are a compact output (want_compact=True)")
+    if not (want_points or want_valid or want_compact):
+        raise ValueError("reproject: nothing asked for")
+    d = disp.contiguous()
+    e = None
+    if exclude is not None:
+        e = (exclude.view(torch.uint8) if exclude.dtype == torch.bool else exclude).contiguous()
+    q = _as_q(Q, b, d.device)
+    dev = d.device
+    lib = _lib.load()
+    ws = torch.empty(lib.lea_disparity_pointcloud_workspace_bytes(b, h, w) // 4, device=dev, dtype=torch.int32)
+    lead = (b,) if batched else ()
+    new = lambda want, tail, dtype: torch.empty(lead + tail, device=dev, dtype=dtype) if want else None  # noqa: E731
+    points = new(want_points, (h, w, 3), torch.float32)
+    valid = new(want_valid, (h, w), torch.uint8)
+    count = new(want_compact, (), torch.int32)
+    xyz = new(want_compact, (capacity, 3), torch.float32)
+    rgb = new(want_compact and img is not None, (capacity, 3), torch.uint8)
+    index = new(want_compact, (capacity,), torch.int32)
+    nrm = new(want_compact and normals, (capacity, 3), torch.float32)
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    rec = None if _probe is None else _probe_launch(
+        "disparity_pointcloud", 0.0, d.numel() * ((8.0 if want_compact else 4.0) + (0.0 if e is None else 1.0) +
+                                                  (12.0 if want_points else 0.0) + (1.0 if want_valid else 0.0) +
+                                                  (16.0 if want_compact else 0.0) + (0.0 if rgb is None else 6.0) +
+                                                  (12.0 if nrm is not None else 0.0)))
+    check(lib.lea_disparity_pointcloud_f32(d.data_ptr(), ptr(e), ptr(img), 0 if img is None else img.shape[-1],
+                                           q.data_ptr(), 16 if q.dim() == 3 else 0, b, h, w, float(min_disp),
+                                           float(max_disp), float(normal_max_diff), int(capacity), ws.data_ptr(),
+                                           ptr(points), ptr(valid), ptr(count), ptr(xyz), ptr(rgb), ptr(index),
+                                           ptr(nrm), _stream()), "lea_disparity_pointcloud_f32")
+    _probe_end(rec)
+    return PointCloud(points, valid, count, xyz, rgb, index, nrm)
 
 
 # ------------------------------------------------------------------ bf16 path (c8)

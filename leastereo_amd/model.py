@@ -340,6 +340,24 @@ class LEAStereo(nn.Module):
                                               return_support=True)
         return kernels.DisparityRefined(st.disp, refined, support, st.peak, lr.disp_right, state)
 
+    _POINT_OPTS = ("min_disp", "max_disp", "normals", "normal_max_diff", "capacity", "want_points", "want_valid",
+                   "want_compact")
+
+    def forward_points(self, x, y, Q, image=None, refine=True, **opts):
+        """``forward_refined`` with the point cloud as the last stage, as
+        (``kernels.DisparityRefined``, ``kernels.PointCloud``): the chain of ``forward_refined``
+        (its keywords in ``opts``: lam, sigma, iterations, radius, lr_threshold, speckle), then
+        ``kernels.reproject`` of ``disp_refined`` through ``Q`` with ``exclude`` the chain's
+        ``state`` (the keywords of ``reproject`` in ``opts``: min_disp, max_disp, normals,
+        normal_max_diff, capacity, want_points, want_valid, want_compact).  ``refine=False``
+        reprojects the plain disparity ``disp`` instead.  ``image``: the uint8 left image
+        [B, H, W, 3|4] on the device, for the colours.  ``Q`` as for ``reproject``: a float32
+        device tensor is read in place.  Nothing is read back.  Inference only."""
+        pc = {k: opts.pop(k) for k in self._POINT_OPTS if k in opts}
+        out = self.forward_refined(x, y, **opts)
+        cloud = kernels.reproject(out.disp_refined if refine else out.disp, Q, image, out.state, **pc)
+        return out, cloud
+
     def forward_scene(self, left_u8, right_u8, tile, **kw):
         """A uint8 scene pair [H, W, 3|4] of any size through overlapping ``tile`` = (h, w)
         forwards, gathered and blended on the device: ``scene.SceneResult`` at the scene's
@@ -361,7 +379,7 @@ class LEAStereo(nn.Module):
         self.precision = precision
 
     def graphed(self, batch: int, height: int, width: int, confidence: bool = False, radius: int = 4,
-                lr_threshold=None, refine=None):
+                lr_threshold=None, refine=None, points=None):
         """``forward`` for one input shape captured into a HIP graph (SURVEY.md §7:
         one host call per batch instead of ~140 launches, for serving and for ranks
         that share a node's host CPUs).  The forward issues only library kernels on
@@ -369,8 +387,13 @@ class LEAStereo(nn.Module):
         ``confidence=True`` captures ``forward_with_confidence(..., radius)`` instead, a number
         for ``lr_threshold`` captures ``forward_lr(..., lr_threshold)``; not both in one capture.
         ``refine=dict(...)`` (the keywords of ``forward_refined``, ``speckle=dict(...)`` among them;
-        an empty dict for its defaults) captures ``forward_refined`` instead, on its own."""
-        return GraphedForward(self, batch, height, width, confidence, radius, lr_threshold, refine)
+        an empty dict for its defaults) captures ``forward_refined`` instead, on its own.
+        ``points=dict(Q=..., ...)`` (the other keywords of ``forward_points``: refine=False,
+        image=True for a static uint8 [B, H, W, 3] colour buffer, and those of
+        ``kernels.reproject``) captures ``forward_points`` with the ``refine`` dict's chain: the
+        output is (``DisparityRefined``, ``PointCloud``), and every replay reads the matrix the
+        captured device tensor ``.Q`` holds at the time (``__call__(x, y, Q=new)`` copies into it)."""
+        return GraphedForward(self, batch, height, width, confidence, radius, lr_threshold, refine, points)
 
 
 class GraphedForward:
@@ -379,10 +402,17 @@ class GraphedForward:
     replays, and returns the static output (overwritten by the next call): the disparity,
     with ``confidence`` the ``DisparityStats`` of ``forward_with_confidence``, or with
     ``lr_threshold`` the ``DisparityLR`` of ``forward_lr``, or with ``refine`` the
-    ``DisparityRefined`` of ``forward_refined``."""
+    ``DisparityRefined`` of ``forward_refined``, or with ``points`` the (``DisparityRefined``,
+    ``PointCloud``) of ``forward_points``: its matrix is the static device tensor ``Q`` ([4, 4]
+    or [B, 4, 4] float32), its colours the static uint8 ``image`` [B, H, W, 3] (``None`` without
+    ``image=True``); ``__call__(x, y, Q=None, image=None)`` copies into them what it is given."""
 
     def __init__(self, model: LEAStereo, batch: int, height: int, width: int, confidence: bool = False,
-                 radius: int = 4, lr_threshold=None, refine=None):
+                 radius: int = 4, lr_threshold=None, refine=None, points=None):
+        if points is not None:
+            if not isinstance(points, dict) or "Q" not in points:
+                raise ValueError(f"graphed(): points must be a dict with the matrix Q, got {points!r}")
+            refine = {} if refine is None else refine
         if refine is not None and (confidence or lr_threshold is not None):
             raise ValueError("graphed(): refine=dict(...) captures forward_refined on its own; give radius and "
                              "lr_threshold inside the dict")
@@ -398,7 +428,15 @@ class GraphedForward:
         model.check_shape(height, width)
         dev = next(model.parameters()).device
         self.model = model
-        run = ((lambda a, b: model.forward_refined(a, b, **refine)) if refine is not None else
+        self.Q = self.image = None
+        if points is not None:
+            pc = dict(points)
+            self.Q = kernels._as_q(pc.pop("Q"), batch, dev).clone()
+            if pc.pop("image", False):
+                self.image = torch.zeros(batch, height, width, 3, device=dev, dtype=torch.uint8)
+            pc.update(refine)
+        run = ((lambda a, b: model.forward_points(a, b, self.Q, self.image, **pc)) if points is not None else
+               (lambda a, b: model.forward_refined(a, b, **refine)) if refine is not None else
                (lambda a, b: model.forward_with_confidence(a, b, radius)) if confidence else
                (lambda a, b: model.forward_lr(a, b, lr_threshold)) if lr_threshold is not None else model)
         self.x = torch.zeros(batch, 3, height, width, device=dev)
@@ -413,8 +451,15 @@ class GraphedForward:
         with torch.no_grad(), torch.cuda.graph(self.graph):
             self.out = run(self.x, self.y)
 
-    def __call__(self, x, y):
+    def __call__(self, x, y, Q=None, image=None):
         self.x.copy_(x, non_blocking=True)
         self.y.copy_(y, non_blocking=True)
+        if Q is not None or image is not None:
+            if self.Q is None or (image is not None and self.image is None):
+                raise ValueError("GraphedForward: Q and image go with graphed(points=dict(Q=..., image=True))")
+            if Q is not None:
+                self.Q.copy_(kernels._as_q(Q, self.x.shape[0], self.Q.device).reshape(self.Q.shape), non_blocking=True)
+            if image is not None:
+                self.image.copy_(image[..., :3], non_blocking=True)
         self.graph.replay()
         return self.out

@@ -35,6 +35,13 @@ Restates the host-side steps around ``LEAStereo.forward`` (predict.py:144-243):
                        adds the speckle filter of ``kernels.speckle_filter`` on the written
                        disparity ({index}_speckle.png, {index}_despeckled.npy; the flags of
                        --lr_check are its walls), and feeds --refine 1 the removed pixels
+  * ``pointcloud_options`` / ``map_origin`` / ``pointcloud_of_map`` / ``save_pointcloud``  not in the
+                       reference: --pointcloud 1 --pc_focal PX --pc_baseline M [--pc_cx X --pc_cy Y
+                       --pc_max_depth M --pc_normals 1] reprojects the best map the other flags
+                       made (``kernels.reproject``: the refined map under --refine, else the
+                       disparity without the pixels --speckle and --lr_check flag) and writes
+                       {index}.ply, coloured from the decoded left image; the calibration is the
+                       source image's, whatever the crop
 Arithmetic runs on the HIP kernels; what stays on the host is file I/O (PIL, PFM, PNG).
 
     python predict.py --sceneflow=1 --maxdisp=192 --crop_height=576 --crop_width=960 \
@@ -248,6 +255,66 @@ def save_speckle(prefix, removed, despeckled):
     np.save(prefix + "_despeckled.npy", despeckled.astype(np.float32))
 
 
+def pointcloud_options(opt):
+    """--pointcloud 1 --pc_focal PX --pc_baseline M [--pc_cx X --pc_cy Y --pc_max_depth M
+    --pc_normals 1] as a dict (focal, baseline, cx, cy, max_depth, normals; cx / cy None for the
+    image's centre); None when the flag is off.  Refuses a focal length or baseline that is not a
+    finite number > 0, a negative or NaN depth limit, and --satellite."""
+    if not getattr(opt, "pointcloud", 0):
+        return None
+    focal, baseline, depth = opt.pc_focal, opt.pc_baseline, opt.pc_max_depth
+    if not (0 < focal < float("inf") and 0 < baseline < float("inf")):
+        raise ValueError(f"--pointcloud needs --pc_focal {focal} (pixels) and --pc_baseline {baseline} as finite "
+                         f"numbers > 0")
+    if not depth >= 0:
+        raise ValueError(f"--pc_max_depth {depth}: a depth > 0 in the baseline's unit, or 0 for no limit")
+    for name in ("pc_cx", "pc_cy"):
+        v = getattr(opt, name)
+        if v is not None and not abs(v) < float("inf"):
+            raise ValueError(f"--{name} {v}: a finite pixel coordinate")
+    if getattr(opt, "satellite", 0):
+        raise NotImplementedError("--pointcloud writes its file beside the --sceneflow outputs only")
+    return dict(focal=float(focal), baseline=float(baseline), cx=opt.pc_cx, cy=opt.pc_cy, max_depth=float(depth),
+                normals=bool(opt.pc_normals))
+
+
+def map_origin(height: int, width: int, map_height: int, map_width: int):
+    """(x0, y0): where pixel (0, 0) of a written map of ``map_height`` x ``map_width`` lies in
+    its ``height`` x ``width`` source image -- the centre crop that ``crop_output`` leaves of an
+    image larger than the crop and that ``main`` cuts out of the ground truth; (0, 0) for a map
+    of the image's own size (an image that fits the crop, and every map under --scene)."""
+    return max(int((width - map_width) / 2), 0), max(int((height - map_height) / 2), 0)
+
+
+def pointcloud_of_map(disp, exclude, left_u8, focal, baseline, cx=None, cy=None, max_depth=0.0, normals=False,
+                      device="cuda"):
+    """``kernels.reproject`` of a written map [h', w'] (numpy: the disparity or the refined
+    disparity, at the crop's or the scene's size) with the source image's calibration:
+    ``left_u8`` is the decoded left image the map was cut from, (``cx``, ``cy``) its principal
+    point (None: its centre), the map's origin in it is ``map_origin``'s.  ``exclude`` [h', w']
+    or None: non-zero pixels give no point.  ``max_depth`` > 0 becomes the disparity bound
+    min_disp = focal * baseline / max_depth here, so that validity stays a test on the
+    disparity.  Returns ``kernels.HostPointCloud`` (count, xyz, rgb, index, normals)."""
+    from . import kernels
+    from .pointcloud import q_matrix
+    h, w = left_u8.shape[:2]
+    mh, mw = disp.shape
+    x0, y0 = map_origin(h, w, mh, mw)
+    Q = q_matrix(focal, baseline, w / 2 if cx is None else cx, h / 2 if cy is None else cy, origin=(x0, y0))
+    d = torch.from_numpy(np.ascontiguousarray(disp, dtype=np.float32)).to(device)
+    e = None if exclude is None else torch.from_numpy(np.ascontiguousarray(exclude != 0).view(np.uint8)).to(device)
+    img = torch.from_numpy(np.ascontiguousarray(left_u8[y0:y0 + mh, x0:x0 + mw])).to(device)
+    cloud = kernels.reproject(d, Q, img, e, min_disp=focal * baseline / max_depth if max_depth > 0 else 0.0,
+                              normals=normals)
+    return cloud.to_host()
+
+
+def save_pointcloud(prefix, cloud):
+    """<prefix>.ply (binary little-endian: x y z, the normals when the cloud has them, red green blue)."""
+    from .pointcloud import write_ply
+    return write_ply(prefix + ".ply", cloud.xyz, cloud.rgb, cloud.normals)
+
+
 def save_refined(prefix, refined, support, max_disp=192):
     """<prefix>_refined.npy (float32), <prefix>_refined.png (coloured like the disparity) and
     <prefix>_support.png (8-bit: the smoothed confidence, in [0, 1], scaled by 255)."""
@@ -427,6 +494,7 @@ def main(argv=None):
     if opt.refine and opt.satellite:
         raise NotImplementedError("--refine writes its maps beside the --sceneflow outputs only")
     speckle = speckle_options(opt)
+    cloud_opt = pointcloud_options(opt)
     if not torch.cuda.is_available():
         raise RuntimeError("leastereo_amd runs on a ROCm device only")
     model = LEAStereo(opt, "cuda")
@@ -499,6 +567,15 @@ def main(argv=None):
             save_speckle(os.path.join(opt.save_path, f"{index}"), removed, despeckled)
             print(f"{index}: speckle filter at {speckle['max_size']} px, {speckle['max_diff']:g} px steps removes "
                   f"{100.0 * float(removed.mean()):.2f} % of the pixels")
+        if cloud_opt is not None:  # from the best map the other flags made, at its size
+            flagged = None if lr is None else lr[2] != 0
+            if speckle is not None:
+                flagged = removed if flagged is None else (flagged | removed)
+            best, flagged = (refined[0], None) if refined is not None else (disp, flagged)
+            cloud = pointcloud_of_map(best, flagged, load_images(leftname, rightname)[0], **cloud_opt)
+            save_pointcloud(os.path.join(opt.save_path, f"{index}"), cloud)
+            print(f"{index}: point cloud of {cloud.xyz.shape[0]} points "
+                  f"({100.0 * cloud.xyz.shape[0] / best.size:.2f} % of the pixels)")
         if opt.photo_check:
             warped, err, loss, l1, dssim = photometric_check(model, leftname, rightname, opt.crop_height,
                                                              opt.crop_width, opt.lr_check)

@@ -349,3 +349,38 @@ def speckle_scene(result: SceneResult, max_size: int = None, max_diff: float = N
     return kernels.speckle_filter(result.disp, result.state,
                                   kernels.SPECKLE_MAX_SIZE if max_size is None else max_size,
                                   kernels.SPECKLE_MAX_DIFF if max_diff is None else max_diff, fill)
+
+
+@torch.no_grad()
+def points_scene(result: SceneResult, Q, left_u8=None, use: str = "refined", refined: torch.Tensor = None,
+                 refine: dict = None, **kw):
+    """``kernels.reproject`` of a ``SceneResult``, once, at scene size, after the blend (never
+    per tile: the overlaps would give their points twice, and a tile's normals stop at its
+    cut), with ``exclude`` = ``result.state`` when the runner ran the left-right check (or
+    ``speckle_scene`` put its state there).  ``use`` names the map: "disp" (the blended
+    disparity), "filled" (``result.disp_filled``) or "refined" (``refined``, what
+    ``refine_scene`` returned for this result; None: it is called here, with the keywords in
+    ``refine``).  ``Q`` is the scene's matrix (``pointcloud.q_matrix``, origin (0, 0));
+    ``left_u8`` the uint8 scene [H, W, 3|4] for the colours, or None.  ``kw``: the other
+    keywords of ``reproject``.  Returns ``kernels.PointCloud`` without a batch axis."""
+    from . import kernels
+    if use not in ("refined", "filled", "disp"):
+        raise ValueError(f"points_scene: use {use!r}: one of refined, filled, disp")
+    if use == "refined" and refined is None:
+        if left_u8 is None:
+            raise ValueError("points_scene: use='refined' needs the scene left_u8 as the guide, or refined=")
+        refined = refine_scene(result, left_u8, **({} if refine is None else refine))
+    disp = {"refined": refined, "filled": result.disp_filled, "disp": result.disp}[use]
+    if disp is None:
+        raise ValueError("points_scene: use='filled', but the result holds no filled disparity (the runner ran no "
+                         "left-right check)")
+    if tuple(disp.shape) != tuple(result.disp.shape):
+        raise ValueError(f"points_scene: the map is {tuple(disp.shape)}, the scene {tuple(result.disp.shape)}")
+    image = left_u8
+    if image is not None:
+        if isinstance(image, np.ndarray):
+            image = torch.from_numpy(np.ascontiguousarray(image))
+        if image.dim() == 4 and image.shape[0] == 1:
+            image = image[0]
+        image = image.to(disp.device, non_blocking=True)
+    return kernels.reproject(disp, Q, image, result.state, **kw)
