@@ -532,6 +532,48 @@ int lea_disparity_pointcloud_f32(const float* disp, const uint8_t* exclude, cons
                                  int32_t* count, float* xyz, uint8_t* rgb, int32_t* index,
                                  float* normals, void* stream);
 
+/* Rectification (additive: the ABI number stays 14): the first stage of the chain.  One launch
+ * undistorts and rectifies both raw views of a batch, bilinear, uint8 in and out, from a
+ * calibration block in device memory or from given maps.  It takes no workspace, uses no
+ * atomics, makes no host copy and does not synchronise; capturable, the same bits call after
+ * call, and a replay reads calib (or maps_in) anew.
+ *
+ * Inputs.  left, right: uint8 [B, H, W, pix_stride], pix_stride 3 or 4, as decoded; every
+ * channel is interpolated, alpha included.  Exactly one of calib and maps_in.  fill: the
+ * border value, 0 .. 255.
+ *   calib    f32 [Bc, 2, 24] on the device, Bc 1 or B; view 0 is left.  The 24 floats of a view:
+ *            M[9] row-major, M = R_k^T K_new,k^-1 (a rectified pixel (u, v, 1) to a ray of the
+ *            raw camera); fx, fy, cx, cy of the raw camera; model (1.0f = fisheye, equidistant;
+ *            anything else = the pinhole rational model); k[8]; two pad floats.
+ *   maps_in  f32 [Bm, 2, 2, Ho, Wo] on the device, Bm 1 or B: view, then x / y.
+ * Map stage (calib), every operation a separately rounded float32 operation in this order:
+ *   X = (M0 u + M1 v) + M2, Y = (M3 u + M4 v) + M5, Wc = (M6 u + M7 v) + M8; unless Wc > 0 both
+ *   coordinates are NaN.  x = X / Wc, y = Y / Wc, xx = x x, yy = y y, r2 = xx + yy.
+ *   Pinhole, k = k1 k2 p1 p2 k3 k4 k5 k6:
+ *     rad = (1 + r2 (k1 + r2 (k2 + r2 k3))) / (1 + r2 (k4 + r2 (k5 + r2 k6)))
+ *     xd = x rad + ((2 p1) (x y) + p2 (r2 + 2 xx)),  yd = y rad + (p1 (r2 + 2 yy) + (2 p2) (x y))
+ *   Fisheye, k = k1 .. k4: r = sqrtf(r2), t = atanf(r), t2 = t t,
+ *     td = t (1 + t2 (k1 + t2 (k2 + t2 (k3 + t2 k4)))), (xd, yd) = (x, y) td / r (factor 1 where
+ *     r <= 1e-8f).
+ *   sx = fx xd + cx, sy = fy yd + cy.
+ * Pixel stage, the same for computed and given maps, exact: a pixel is valid when
+ * 0 <= sx <= W - 1 and 0 <= sy <= H - 1 (NaN fails); an invalid pixel is fill in every channel.
+ * A valid one: x0 = floorf(sx), ax = sx - x0, likewise y; the tap x0 + 1 is clamped to W - 1
+ * (its weight is 0 there); top = a + ax (b - a), bot = c + ax (d - c), v = top + ay (bot - top),
+ * each operation rounded on its own; the output is rintf(v) (half to even).
+ * Outputs.  out_left, out_right: uint8 [B, Ho, Wo, pix_stride].  valid: uint8 [B, 2, Ho, Wo]
+ * (1 / 0) or NULL.  maps_out: f32 [B, 2, 2, Ho, Wo] or NULL, the source coordinates the launch
+ * used.  Any 48 floats of calib and any values of maps_in are memory-safe (NaN, infinities,
+ * 1e30): no value is converted to an integer before the validity test has bounded it.
+ * LEA_E_INVALID, before the launch: a null image or output image; pix_stride not 3 or 4; B, H,
+ * W, Ho or Wo < 1 (or B above 32767, a size above 65535); both or neither of calib and maps_in;
+ * Bc or Bm neither 1 nor B; fill outside 0 .. 255; calib, maps_in or maps_out not 4-byte
+ * aligned; an output overlapping an input or another output. */
+int lea_rectify_pair_u8(const void* left, const void* right, int pix_stride, int B, int H, int W,
+                        const float* calib, int Bc, const float* maps_in, int Bm, int Ho, int Wo,
+                        int fill, void* out_left, void* out_right, uint8_t* valid, float* maps_out,
+                        void* stream);
+
 /* ---- bf16 path (BASELINE configs 3 and 4) ----
  * Activations are bf16 in the "c8" layout: NCDHW with channels blocked by 8
  * innermost, x[b][c/8][d][h][w][c%8] (one voxel's 8 channels = one 16-byte word;

@@ -196,6 +196,10 @@ int lea_conv3d_wino_set_small_cout(int mode);
  * Packing and launches must use the same setting. */
 int lea_conv3d_wino_set_block48(int on);
 
+/* lea_rectify_pair_u8's workgroup tile: 0 (default) = 128 x 8 output pixels (32 lanes of four
+ * pixels by 8 rows), 1 = 1024 x 1 (one row).  Bit-identical (tools/rectify_probe.py). */
+int lea_rectify_set_tile(int mode);
+
 #ifdef __cplusplus
 }
 #endif

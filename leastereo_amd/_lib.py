@@ -83,6 +83,9 @@ SIGNATURES = {
     "lea_disparity_pointcloud_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
     "lea_disparity_pointcloud_f32": (_i, [_p, _p, _p, _i, _p, _i64, _i, _i, _i, ctypes.c_float, ctypes.c_float,
                                           ctypes.c_float, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    # rectification of a raw pair: calibration or maps to images (csrc/rectify.hip)
+    "lea_rectify_pair_u8": (_i, [_p, _p, _i, _i, _i, _i, _p, _i, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "lea_rectify_set_tile": (_i, [_i]),
     # bf16 path (c8 layout)
     "lea_conv3d_packed_elems_bf16": (ctypes.c_size_t, [_i, _i, _i]),
     "lea_conv3d_pack_weights_bf16": (_i, [_p, _p, _i, _i, _i, _p]),

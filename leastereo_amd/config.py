@@ -132,5 +132,19 @@ def obtain_predict_args(argv=None):
                              "disparities at or below focal * baseline / M")
     parser.add_argument("--pc_normals", type=int, default=0,
                         help="1: also write the normals of the points under --pointcloud")
+    parser.add_argument("--calib", type=str, default="", metavar="FILE",
+                        help="a stereo calibration (.json or .npz with K1, D1, K2, D2, R, T, size, model: "
+                             "rectify.load_calibration): every decoded pair is undistorted and rectified on the "
+                             "device before anything else, and --pointcloud takes focal, baseline and principal "
+                             "point from the rectification (the --pc_focal/--pc_baseline/--pc_cx/--pc_cy flags are "
+                             "then refused) (not in the reference)")
+    parser.add_argument("--rect_size", type=int, nargs=2, default=None, metavar=("H", "W"),
+                        help="size of the rectified images under --calib (default: the raw images')")
+    parser.add_argument("--rect_fill", type=int, default=0, metavar="V",
+                        help="grey level 0..255 of the rectified pixels that have no source under --calib; the "
+                             "standardisation statistics include this border")
+    parser.add_argument("--save_rectified", type=int, default=0,
+                        help="1: also write {index}_rect_left.png, {index}_rect_right.png and "
+                             "{index}_rect_valid.png under --calib")
     add_leastereo_args(parser)
     return parser.parse_args(argv)

@@ -1091,6 +1091,91 @@ def reproject(disp: torch.Tensor, Q, image: torch.Tensor = None, exclude: torch.
     return PointCloud(points, valid, count, xyz, rgb, index, nrm)
 
 
+# ---- rectification of a raw pair: calibration or maps to images (csrc/rectify.hip) ----
+
+RectifiedPair = collections.namedtuple("RectifiedPair", "left right valid maps")
+RectifiedPair.__doc__ = """What ``rectify_u8`` returns, on the device: ``left`` / ``right`` uint8 [B, Ho, Wo, ps],
+``valid`` uint8 [B, 2, Ho, Wo] (view, 1 / 0) and ``maps`` float32 [B, 2, 2, Ho, Wo] (view, then x / y: the source
+coordinates the launch used), ``None`` where not asked for.  The leading B is absent where the images came as
+[H, W, ps]."""
+
+RECT_CALIB_FLOATS = 24
+
+
+def rectify_u8(left: torch.Tensor, right: torch.Tensor, calib=None, maps=None, size=None, fill: int = 0,
+               want_valid: bool = True, want_maps: bool = False) -> RectifiedPair:
+    """``lea_rectify_pair_u8`` (include/leastereo_hip.h): both raw views of a batch undistorted
+    and rectified in one launch, bilinear, every channel.  ``left`` / ``right`` uint8
+    [B, H, W, 3|4] or [H, W, 3|4] on the device, as decoded.  Exactly one of ``calib``
+    (float32 [1|B, 2, 24], ``rectify.Rectification.calib()``; a float32 device tensor is read
+    in place at every launch and replay) and ``maps`` (float32 [1|B, 2, 2, Ho, Wo]: any lens
+    model, maps made elsewhere).  ``size`` (Ho, Wo): the output's size with ``calib`` (default:
+    the input's); with ``maps`` it is theirs.  Pixels whose source lies outside the raw image
+    are ``fill`` in every channel and 0 in ``valid``.  The outputs feed ``standardize_crop_u8``,
+    ``standardize_tiles_u8``, ``forward_scene``, ``reproject(image=...)`` as they are."""
+    for t in (left, right):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8:
+            raise ValueError("rectify_u8: left and right must be uint8 tensors on the device")
+    if left.shape != right.shape or left.dim() not in (3, 4) or left.shape[-1] not in (3, 4) or 0 in left.shape:
+        raise ValueError(f"rectify_u8: left / right must both be [B, H, W, 3|4] or [H, W, 3|4], got "
+                         f"{tuple(left.shape)} and {tuple(right.shape)}")
+    batched = left.dim() == 4
+    if not batched:
+        left, right = left.unsqueeze(0), right.unsqueeze(0)
+    left, right = left.contiguous(), right.contiguous()
+    b, h, w, ps = left.shape
+    if (calib is None) == (maps is None):
+        raise ValueError("rectify_u8: exactly one of calib and maps must be given")
+    if isinstance(fill, bool) or not isinstance(fill, int) or not 0 <= fill <= 255:
+        raise ValueError(f"rectify_u8: fill {fill} must be an integer in 0 .. 255")
+    dev = left.device
+
+    def as_f32(a, name):
+        if not isinstance(a, torch.Tensor):
+            a = torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64)).astype(np.float32))
+        if not a.dtype.is_floating_point:
+            raise ValueError(f"rectify_u8: {name} must be floating point, got {a.dtype}")
+        return a.to(device=dev, dtype=torch.float32).contiguous()
+
+    c = m = None
+    if calib is not None:
+        c = as_f32(calib, "calib")
+        if c.dim() == 2:
+            c = c.unsqueeze(0)
+        if c.dim() != 3 or tuple(c.shape[1:]) != (2, RECT_CALIB_FLOATS) or c.shape[0] not in (1, b):
+            raise ValueError(f"rectify_u8: calib must be [1|{b}, 2, {RECT_CALIB_FLOATS}], got {tuple(c.shape)}")
+        ho, wo = (h, w) if size is None else (int(size[0]), int(size[1]))
+    else:
+        m = as_f32(maps, "maps")
+        if m.dim() == 4:
+            m = m.unsqueeze(0)
+        if m.dim() != 5 or tuple(m.shape[1:3]) != (2, 2) or m.shape[0] not in (1, b) or 0 in m.shape:
+            raise ValueError(f"rectify_u8: maps must be [1|{b}, 2, 2, Ho, Wo], got {tuple(m.shape)}")
+        ho, wo = m.shape[-2:]
+        if size is not None and (int(size[0]), int(size[1])) != (ho, wo):
+            raise ValueError(f"rectify_u8: size {tuple(size)} contradicts the maps' {(ho, wo)}")
+    if not (1 <= ho <= 65535 and 1 <= wo <= 65535):
+        raise ValueError(f"rectify_u8: output size {(ho, wo)} outside 1 .. 65535")
+    lib = _lib.load()
+    out_l = torch.empty((b, ho, wo, ps), device=dev, dtype=torch.uint8)
+    out_r = torch.empty_like(out_l)
+    valid = torch.empty((b, 2, ho, wo), device=dev, dtype=torch.uint8) if want_valid else None
+    mo = torch.empty((b, 2, 2, ho, wo), device=dev, dtype=torch.float32) if want_maps else None
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    n = 2.0 * b * ho * wo
+    rec = None if _probe is None else _probe_launch(
+        "rectify_pair", 50.0 * n, n * (2.0 * ps + (1.0 if want_valid else 0.0) + (8.0 if want_maps else 0.0) +
+                                       (8.0 if m is not None else 0.0)))
+    check(lib.lea_rectify_pair_u8(left.data_ptr(), right.data_ptr(), ps, b, h, w, ptr(c), 0 if c is None else c.shape[0],
+                                  ptr(m), 0 if m is None else m.shape[0], ho, wo, int(fill), out_l.data_ptr(),
+                                  out_r.data_ptr(), ptr(valid), ptr(mo), _stream()), "lea_rectify_pair_u8")
+    _probe_end(rec)
+    outs = (out_l, out_r, valid, mo)
+    if not batched:
+        outs = tuple(None if t is None else t[0] for t in outs)
+    return RectifiedPair(*outs)
+
+
 # ------------------------------------------------------------------ bf16 path (c8)
 # Activations: torch.bfloat16 [B, C/8, D, H, W, 8] ("c8": 8 channels per voxel word).
 

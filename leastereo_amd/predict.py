@@ -42,6 +42,12 @@ Restates the host-side steps around ``LEAStereo.forward`` (predict.py:144-243):
                        disparity without the pixels --speckle and --lr_check flag) and writes
                        {index}.ply, coloured from the decoded left image; the calibration is the
                        source image's, whatever the crop
+  * ``rectify_options`` / ``set_rectifier`` / ``load_pair`` / ``save_rectified``  not in the reference:
+                       --calib FILE [--rect_size H W --rect_fill V --save_rectified 1] rectifies every
+                       decoded pair on the device (``rectify.Rectifier``, ``kernels.rectify_u8``)
+                       before the transform or the scene path; --pointcloud 1 then takes focal,
+                       baseline and principal point from the rectification and leaves out the left
+                       pixels that have no source
 Arithmetic runs on the HIP kernels; what stays on the host is file I/O (PIL, PFM, PNG).
 
     python predict.py --sceneflow=1 --maxdisp=192 --crop_height=576 --crop_width=960 \
@@ -89,6 +95,39 @@ def load_images(leftname, rightname):
     return left, right
 
 
+_rectifier = None      # set_rectifier: the rectify.Rectifier of --calib, None without the flag
+_rectified_last = None  # the RectifiedPair of the last load_pair under --calib
+
+
+def set_rectifier(rectifier):
+    """Install (or, with None, remove) the ``rectify.Rectifier`` that ``load_pair`` applies."""
+    global _rectifier, _rectified_last
+    _rectifier, _rectified_last = rectifier, None
+
+
+def load_pair(leftname, rightname):
+    """``load_images``; under --calib the pair rectified on the device: two uint8 device
+    tensors [Ho, Wo, 3|4] (``last_rectified`` keeps the whole ``RectifiedPair``)."""
+    global _rectified_last
+    left, right = load_images(leftname, rightname)
+    if _rectifier is None:
+        return left, right
+    _rectified_last = _rectifier(left, right)
+    return _rectified_last.left, _rectified_last.right
+
+
+def last_rectified():
+    """The ``kernels.RectifiedPair`` of the last ``load_pair`` under --calib, else None."""
+    return _rectified_last
+
+
+def _device_u8(a, device):
+    """A decoded image (numpy) or a rectified one (device tensor) as a device tensor."""
+    if isinstance(a, torch.Tensor):
+        return a.to(device).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(a)).to(device, non_blocking=True)
+
+
 def load_transform(left_u8, right_u8, crop_height, crop_width, device="cuda"):
     """load_data (predict.py:162-184) + test_transform (:144-159) on the device:
     the uint8 images go up as they were decoded (a quarter of the float32 bytes)
@@ -96,8 +135,7 @@ def load_transform(left_u8, right_u8, crop_height, crop_width, device="cuda"):
     pads or crops in one pass.  Returns (left, right [1, 3, ch, cw], h, w)."""
     from . import kernels
     h, w = left_u8.shape[:2]
-    lt = torch.from_numpy(np.ascontiguousarray(left_u8)).to(device, non_blocking=True)
-    rt = torch.from_numpy(np.ascontiguousarray(right_u8)).to(device, non_blocking=True)
+    lt, rt = _device_u8(left_u8, device), _device_u8(right_u8, device)
     left, right = kernels.standardize_crop_u8(lt, rt, crop_height, crop_width)
     return left, right, h, w
 
@@ -116,7 +154,7 @@ def predict_pair(model, leftname, rightname, crop_height, crop_width, device="cu
     instead -- conf in [0, 1], ``DisparityStats.confidence`` or the peak mass within ``radius``
     of the winner; local the winner-window disparity under "peak", else None -- from
     ``model.forward_with_confidence``, each cropped like the disparity."""
-    left, right, h, w = load_transform(*load_images(leftname, rightname), crop_height, crop_width,
+    left, right, h, w = load_transform(*load_pair(leftname, rightname), crop_height, crop_width,
                                        device)
     if confidence in (None, "none"):
         with torch.no_grad():
@@ -145,7 +183,7 @@ def predict_pair_lr(model, leftname, rightname, crop_height, crop_width, thresho
     """``predict_pair`` through ``model.forward_lr``: (disparity, right-view disparity, state
     uint8, filled disparity), each cropped like the disparity.  The disparity is
     ``predict_pair``'s bit for bit."""
-    left, right, h, w = load_transform(*load_images(leftname, rightname), crop_height, crop_width,
+    left, right, h, w = load_transform(*load_pair(leftname, rightname), crop_height, crop_width,
                                        device)
     with torch.no_grad():
         lr = model.forward_lr(left, right, threshold)
@@ -157,7 +195,7 @@ def predict_scene(runner, leftname, rightname, confidence="none"):
     as ``predict_pair`` and ``predict_pair_lr`` shape them -- disp the disparity, or (disparity,
     conf, local) under ``confidence``; lr (disparity, right-view disparity, state, filled) when
     the runner has an ``lr_threshold``, else None."""
-    return _scene_maps(runner(*load_images(leftname, rightname)), runner.model.maxdisp, confidence)
+    return _scene_maps(runner(*load_pair(leftname, rightname)), runner.model.maxdisp, confidence)
 
 
 def _scene_maps(res, maxdisp, confidence):
@@ -181,7 +219,7 @@ def predict_pair_refined(model, leftname, rightname, crop_height, crop_width, la
     """``predict_pair`` through ``model.forward_refined``: (disparity, refined disparity,
     support), each cropped like the disparity.  The disparity is ``predict_pair``'s bit for bit.
     ``speckle``: the dict of ``forward_refined`` (None: the call as it is without it)."""
-    left, right, h, w = load_transform(*load_images(leftname, rightname), crop_height, crop_width,
+    left, right, h, w = load_transform(*load_pair(leftname, rightname), crop_height, crop_width,
                                        device)
     kw = {} if speckle is None else {"speckle": speckle}
     with torch.no_grad():
@@ -199,7 +237,7 @@ def predict_scene_refined(runner, leftname, rightname, lam, sigma, iterations, c
     confidence and exclusion.  ``speckle``: the dict of ``refine_scene`` (None: the call as it
     is without it)."""
     from .scene import refine_scene
-    left, right = load_images(leftname, rightname)
+    left, right = load_pair(leftname, rightname)
     res = runner(left, right)
     kw = {} if speckle is None else {"speckle": speckle}
     refined, support = refine_scene(res, left, lam, sigma, iterations, return_support=True, **kw)
@@ -263,6 +301,17 @@ def pointcloud_options(opt):
     if not getattr(opt, "pointcloud", 0):
         return None
     focal, baseline, depth = opt.pc_focal, opt.pc_baseline, opt.pc_max_depth
+    if getattr(opt, "calib", ""):  # the rectification is the calibration: main fills focal .. cx_right from it
+        given = [f"--{n}" for n in ("pc_focal", "pc_baseline") if getattr(opt, n)]
+        given += [f"--{n}" for n in ("pc_cx", "pc_cy") if getattr(opt, n) is not None]
+        if given:
+            raise ValueError(f"{', '.join(given)} with --calib: the point cloud takes focal, baseline and principal "
+                             f"point from the rectification, a second calibration would contradict it")
+        if not depth >= 0:
+            raise ValueError(f"--pc_max_depth {depth}: a depth > 0 in the baseline's unit, or 0 for no limit")
+        if getattr(opt, "satellite", 0):
+            raise NotImplementedError("--pointcloud writes its file beside the --sceneflow outputs only")
+        return dict(focal=None, baseline=None, cx=None, cy=None, max_depth=float(depth), normals=bool(opt.pc_normals))
     if not (0 < focal < float("inf") and 0 < baseline < float("inf")):
         raise ValueError(f"--pointcloud needs --pc_focal {focal} (pixels) and --pc_baseline {baseline} as finite "
                          f"numbers > 0")
@@ -286,24 +335,65 @@ def map_origin(height: int, width: int, map_height: int, map_width: int):
     return max(int((width - map_width) / 2), 0), max(int((height - map_height) / 2), 0)
 
 
+def rectify_options(opt):
+    """--calib FILE [--rect_size H W --rect_fill V --save_rectified 1] as a dict (path, size,
+    fill, save); None without --calib (the other three are then not looked at).  Refuses a fill
+    outside 0 .. 255, a size below 1 and --satellite."""
+    if not getattr(opt, "calib", ""):
+        return None
+    size = getattr(opt, "rect_size", None)
+    if size is not None and (len(size) != 2 or min(size) < 1):
+        raise ValueError(f"--rect_size {size}: a height and a width >= 1")
+    if not 0 <= opt.rect_fill <= 255:
+        raise ValueError(f"--rect_fill {opt.rect_fill}: a grey level in 0 .. 255")
+    if getattr(opt, "satellite", 0):
+        raise NotImplementedError("--calib rectifies the pairs of the --sceneflow list only")
+    return dict(path=opt.calib, size=None if size is None else (int(size[0]), int(size[1])), fill=int(opt.rect_fill),
+                save=bool(opt.save_rectified))
+
+
+def make_rectifier(path, size=None, fill=0, device="cuda", **_):
+    """The ``rectify.Rectifier`` of a calibration file (``rectify.load_calibration``), with
+    ``size`` (height, width) as the rectified images' size (None: the raw images')."""
+    from . import rectify
+    cam_l, cam_r, R, T, raw = rectify.load_calibration(path)
+    return rectify.Rectifier(rectify.stereo_rectify(cam_l, cam_r, R, T, raw, out_size=size), device, fill=fill)
+
+
+def save_rectified(prefix, pair):
+    """<prefix>_rect_left.png, <prefix>_rect_right.png (the rectified images as they go on) and
+    <prefix>_rect_valid.png (8-bit: 255 where the left pixel has a source in the raw image)."""
+    from PIL import Image
+    Image.fromarray(pair.left.cpu().numpy()).save(prefix + "_rect_left.png")
+    Image.fromarray(pair.right.cpu().numpy()).save(prefix + "_rect_right.png")
+    v = pair.valid.cpu().numpy()
+    Image.fromarray((v[0] * 255).astype(np.uint8)).save(prefix + "_rect_valid.png")
+
+
 def pointcloud_of_map(disp, exclude, left_u8, focal, baseline, cx=None, cy=None, max_depth=0.0, normals=False,
-                      device="cuda"):
+                      device="cuda", cx_right=None, valid=None):
     """``kernels.reproject`` of a written map [h', w'] (numpy: the disparity or the refined
     disparity, at the crop's or the scene's size) with the source image's calibration:
     ``left_u8`` is the decoded left image the map was cut from, (``cx``, ``cy``) its principal
     point (None: its centre), the map's origin in it is ``map_origin``'s.  ``exclude`` [h', w']
     or None: non-zero pixels give no point.  ``max_depth`` > 0 becomes the disparity bound
     min_disp = focal * baseline / max_depth here, so that validity stays a test on the
-    disparity.  Returns ``kernels.HostPointCloud`` (count, xyz, rgb, index, normals)."""
+    disparity.  Under --calib ``left_u8`` is the rectified left image (a device tensor),
+    ``cx_right`` the right view's principal point and ``valid`` [h, w] its validity map: pixels
+    without a source give no point.  Returns ``kernels.HostPointCloud`` (count, xyz, rgb, index,
+    normals)."""
     from . import kernels
     from .pointcloud import q_matrix
     h, w = left_u8.shape[:2]
     mh, mw = disp.shape
     x0, y0 = map_origin(h, w, mh, mw)
-    Q = q_matrix(focal, baseline, w / 2 if cx is None else cx, h / 2 if cy is None else cy, origin=(x0, y0))
+    Q = q_matrix(focal, baseline, w / 2 if cx is None else cx, h / 2 if cy is None else cy, cx_right, origin=(x0, y0))
     d = torch.from_numpy(np.ascontiguousarray(disp, dtype=np.float32)).to(device)
     e = None if exclude is None else torch.from_numpy(np.ascontiguousarray(exclude != 0).view(np.uint8)).to(device)
-    img = torch.from_numpy(np.ascontiguousarray(left_u8[y0:y0 + mh, x0:x0 + mw])).to(device)
+    if valid is not None:
+        border = (_device_u8(valid, device)[y0:y0 + mh, x0:x0 + mw] == 0).to(torch.uint8)
+        e = border if e is None else torch.maximum(e, border)
+    img = _device_u8(left_u8[y0:y0 + mh, x0:x0 + mw], device)
     cloud = kernels.reproject(d, Q, img, e, min_disp=focal * baseline / max_depth if max_depth > 0 else 0.0,
                               normals=normals)
     return cloud.to_host()
@@ -346,7 +436,7 @@ def photometric_check(model, leftname, rightname, crop_height, crop_width, lr_th
     image, in the padding of a pair smaller than the crop, or -- with ``lr_threshold`` > 0
     -- flagged by the left-right check (``DisparityLR.state`` passed as it is)."""
     from . import kernels
-    left, right, h, w = load_transform(*load_images(leftname, rightname), crop_height, crop_width,
+    left, right, h, w = load_transform(*load_pair(leftname, rightname), crop_height, crop_width,
                                        device)
     with torch.no_grad():
         if lr_threshold > 0:
@@ -495,8 +585,10 @@ def main(argv=None):
         raise NotImplementedError("--refine writes its maps beside the --sceneflow outputs only")
     speckle = speckle_options(opt)
     cloud_opt = pointcloud_options(opt)
+    rect_opt = rectify_options(opt)
     if not torch.cuda.is_available():
         raise RuntimeError("leastereo_amd runs on a ROCm device only")
+    set_rectifier(None if rect_opt is None else make_rectifier(**rect_opt))
     model = LEAStereo(opt, "cuda")
     if opt.resume:
         if not os.path.isfile(opt.resume):
@@ -550,6 +642,8 @@ def main(argv=None):
         if runner is None and opt.refine:  # its own call on the pair
             refined = refine_pair(model, None, leftname, rightname, opt)[2]
         print(f"Processing time: {time.time() - t0:.4f}")
+        if rect_opt is not None and rect_opt["save"]:
+            save_rectified(os.path.join(opt.save_path, f"{index}"), last_rectified())
         if lr is not None:
             save_lr(os.path.join(opt.save_path, f"{index}"), *lr[1:])
             print(f"{index}: left-right check at {opt.lr_check:g} px flags {100.0 * float((lr[2] != 0).mean()):.2f} % "
@@ -572,7 +666,13 @@ def main(argv=None):
             if speckle is not None:
                 flagged = removed if flagged is None else (flagged | removed)
             best, flagged = (refined[0], None) if refined is not None else (disp, flagged)
-            cloud = pointcloud_of_map(best, flagged, load_images(leftname, rightname)[0], **cloud_opt)
+            if rect_opt is None:
+                cloud = pointcloud_of_map(best, flagged, load_images(leftname, rightname)[0], **cloud_opt)
+            else:  # the rectification is the calibration; left pixels without a source give no point
+                pair, r = last_rectified(), _rectifier.rect
+                cloud = pointcloud_of_map(best, flagged, pair.left, **dict(
+                    cloud_opt, focal=r.focal, baseline=r.baseline, cx=r.cx, cy=r.cy, cx_right=r.cx_right,
+                    valid=pair.valid[0]))
             save_pointcloud(os.path.join(opt.save_path, f"{index}"), cloud)
             print(f"{index}: point cloud of {cloud.xyz.shape[0]} points "
                   f"({100.0 * cloud.xyz.shape[0] / best.size:.2f} % of the pixels)")
@@ -584,7 +684,7 @@ def main(argv=None):
                   f"{100.0 * float((err >= 0).mean()):.2f} % of the pixels")
         plot_disparity(opt.save_path + f"{index:d}.png", disp, 192)  # predict.py:240
         np.save(os.path.join(opt.save_path, f"{index}.npy"), disp.astype(np.float32))
-        if gt is not None:
+        if gt is not None and rect_opt is None:  # a ground truth of the raw view says nothing about a rectified pair
             ch, cw = disp.shape
             h, w = gt.shape
             y0, x0 = max(int((h - ch) / 2), 0), max(int((w - cw) / 2), 0)
