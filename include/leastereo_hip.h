@@ -574,6 +574,53 @@ int lea_rectify_pair_u8(const void* left, const void* right, int pix_stride, int
                         int fill, void* out_left, void* out_right, uint8_t* valid, float* maps_out,
                         void* stream);
 
+/* View synthesis (additive: the ABI number stays 14): an image pushed forward through its own
+ * disparity map into another view on the baseline, as a 1-D mesh render per scanline: neighbouring
+ * source pixels of one surface span a segment, each target pixel takes the nearest surface that
+ * covers it, and what nothing covers is a hole that the scanline rule of lea_disparity_lr_check
+ * can fill.  One launch, no workspace, no float atomics, no host copy, no synchronisation;
+ * capturable, the same bits call after call, and a replay reads scales anew.
+ *
+ * Inputs.  image: [B, C, H, W] f32, 1 <= C <= 4, batch stride image_bstride >= C*H*W (elements).
+ * disp: [B, H, W] f32, batch stride disp_bstride >= H*W; negative disparities are legal and
+ * "nearer" always means the larger d.  exclude: [B, H, W] bytes or NULL (the state of
+ * lea_disparity_lr_check / lea_disparity_speckle_f32 can be passed as it is; any non-zero byte
+ * excludes).  scales: B floats on the device.  max_diff: finite, >= 0.  1 <= max_stretch <= 64.
+ * fill: 0 or 1.  W <= LEA_FORWARD_WARP_MAX_W; B*H <= 2^31 - 1.
+ * Per item b and row y, with s = scales[b] and every operation a separately rounded float32
+ * operation:
+ *   t_x = x - (s * d_x);  ok(x): d_x finite, exclude 0 and t_x finite (a non-finite s makes the
+ *   whole item holes).
+ *   Point x, for every ok(x): covers u = rintf(t_x) when 0 <= u <= W - 1; z = d_x, a = 0.
+ *   Segment x, 0 <= x < W - 1: exists when ok(x), ok(x + 1), |d_{x+1} - d_x| <= max_diff and
+ *   0 < den = t_{x+1} - t_x <= max_stretch (fold-overs, degenerate spans and surfaces stretched
+ *   further are discontinuities).  It covers every integer u with t_x <= u <= t_{x+1} and
+ *   0 <= u <= W - 1;  a = (u - t_x) / den,  z = ((1 - a) * d_x) + (a * d_{x+1}).
+ *   Winner at u: the candidate of the largest z (as numbers, -0 = +0); among equal z the larger
+ *   source column; for one column the segment over the point.
+ *   Hit: state 0; warped_c = ((1 - a) * I_c[x]) + (a * I_c[x+1]), I_c[x] for a point; zview = z;
+ *   source = float(x) + a.  The lerp is exact at a = 0 and a = 1, so s = 0 returns image and
+ *   disp bit for bit (but for the sign of a zero: (1 * -0) + (0 * v) is +0).
+ *   Hole (no candidate): state 1, source -1.  fill = 0: warped = fill_value, zview = NaN.
+ *   fill = 1: colour and zview of the nearest hit to the left on the row or of the nearest to
+ *   the right, the one of the smaller zview (the background), the left one on a tie, the one that
+ *   exists if only one does; a row without a hit as fill = 0.  state stays 1.
+ * Outputs, each optional through NULL (never written), at least one required: warped
+ * [B, C, H, W] f32, zview [B, H, W] f32, state [B, H, W] u8, source [B, H, W] f32, contiguous.
+ * Any contents of disp and scales are memory-safe (NaN, infinities, 1e30, denormals): no value is
+ * converted to an integer before a float comparison has bounded it, and a segment covers at most
+ * max_stretch + 1 targets.
+ * LEA_E_INVALID, before the launch: a null image, disp or scales; every output null; B, H or
+ * W < 1 or beyond the limits above; C outside 1 .. 4; a batch stride below its block; max_diff
+ * negative or not finite; max_stretch outside 1 .. 64 or NaN; fill neither 0 nor 1; an output
+ * overlapping an input, scales or another output. */
+#define LEA_FORWARD_WARP_MAX_W 4096
+int lea_forward_warp_f32(const float* image, int64_t image_bstride, const float* disp,
+                         int64_t disp_bstride, const uint8_t* exclude, const float* scales, int B,
+                         int C, int H, int W, float max_diff, float max_stretch, int fill,
+                         float fill_value, float* warped, float* zview, uint8_t* state,
+                         float* source, void* stream);
+
 /* ---- bf16 path (BASELINE configs 3 and 4) ----
  * Activations are bf16 in the "c8" layout: NCDHW with channels blocked by 8
  * innermost, x[b][c/8][d][h][w][c%8] (one voxel's 8 channels = one 16-byte word;

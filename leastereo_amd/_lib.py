@@ -86,6 +86,9 @@ SIGNATURES = {
     # rectification of a raw pair: calibration or maps to images (csrc/rectify.hip)
     "lea_rectify_pair_u8": (_i, [_p, _p, _i, _i, _i, _i, _p, _i, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "lea_rectify_set_tile": (_i, [_i]),
+    # view synthesis: forward warp with occlusion and fill (csrc/forward_warp.hip)
+    "lea_forward_warp_f32": (_i, [_p, _i64, _p, _i64, _p, _p, _i, _i, _i, _i, ctypes.c_float, ctypes.c_float, _i,
+                                  ctypes.c_float, _p, _p, _p, _p, _p]),
     # bf16 path (c8 layout)
     "lea_conv3d_packed_elems_bf16": (ctypes.c_size_t, [_i, _i, _i]),
     "lea_conv3d_pack_weights_bf16": (_i, [_p, _p, _i, _i, _i, _p]),

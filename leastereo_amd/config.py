@@ -146,5 +146,14 @@ def obtain_predict_args(argv=None):
     parser.add_argument("--save_rectified", type=int, default=0,
                         help="1: also write {index}_rect_left.png, {index}_rect_right.png and "
                              "{index}_rect_valid.png under --calib")
+    parser.add_argument("--novel_view", type=float, default=None, metavar="S",
+                        help="also write {index}_view.png and {index}_view_holes.png: the left image warped forward "
+                             "to baseline fraction S (0 = the left camera, 1 = the right one, beyond either is "
+                             "legal) through the best map the other flags made (the refined map under --refine, "
+                             "else the filled one under --lr_check, else the disparity without the pixels "
+                             "--speckle flags); at S = 1 also print the mean absolute difference to the real "
+                             "right image (not in the reference)")
+    parser.add_argument("--view_fill", type=int, default=1, choices=(0, 1),
+                        help="1: the holes of --novel_view take the background beside them, 0: they stay black")
     add_leastereo_args(parser)
     return parser.parse_args(argv)

@@ -1176,6 +1176,92 @@ def rectify_u8(left: torch.Tensor, right: torch.Tensor, calib=None, maps=None, s
     return RectifiedPair(*outs)
 
 
+# ---- view synthesis: forward warp with occlusion and fill (csrc/forward_warp.hip) ----
+
+FORWARD_WARP_MAX_W = 4096  # LEA_FORWARD_WARP_MAX_W
+
+
+class WarpedView(collections.namedtuple("WarpedView", "image zview state source")):
+    """What ``forward_warp`` returns, on the device (``None`` where not asked for):
+      image   float32 [B, C, H, W]: the view; holes filled from the background, or ``fill_value``
+      zview   float32 [B, H, W]: the disparity of the surface seen at each pixel of the view
+              (of the source view's scale); NaN in an unfilled hole
+      state   uint8 [B, H, W]: 0 = a surface was seen, 1 = hole (also where it was filled)
+      source  float32 [B, H, W]: the source column, fractional, that is seen; -1 in a hole
+    None differentiable."""
+
+
+def forward_warp(image: torch.Tensor, disp: torch.Tensor, scale=1.0, exclude: torch.Tensor = None,
+                 max_diff: float = 1.0, max_stretch: float = 4.0, fill: bool = True, fill_value: float = 0.0,
+                 want_zview: bool = True, want_state: bool = True, want_source: bool = False) -> WarpedView:
+    """``lea_forward_warp_f32`` (include/leastereo_hip.h): ``image`` [B, C, H, W] float32,
+    C 1 .. 4, pushed forward through its own disparity ``disp`` [B, H, W] to where a camera
+    ``scale`` baselines along sees it (source column x lands on x - scale * d), as a 1-D mesh per
+    scanline: the nearest surface wins a pixel, neighbours further apart than ``max_diff`` px of
+    disparity or stretched beyond ``max_stretch`` px are torn apart, and holes take the
+    background beside them (``fill``) or ``fill_value``.  ``scale``: a Python float for every
+    item or a [B] float32 device tensor, read on the device at every launch and replay.
+    ``exclude``: [B, H, W] uint8 or bool, or None (``DisparityLR.state`` /
+    ``DisparitySpeckle.state`` go as they are).  One launch on the current stream; nothing is
+    read back.  Returns ``WarpedView``."""
+    _require_cuda(image, disp)
+    if image.dtype != torch.float32 or disp.dtype != torch.float32:
+        raise ValueError("forward_warp: image and disp must be float32")
+    if image.dim() != 4 or disp.dim() != 3 or 0 in image.shape:
+        raise ValueError(f"forward_warp: image must be [B, C, H, W] and disp [B, H, W], got "
+                         f"{tuple(image.shape)} and {tuple(disp.shape)}")
+    b, c, h, w = image.shape
+    if tuple(disp.shape) != (b, h, w):
+        raise ValueError(f"forward_warp: disp {tuple(disp.shape)} does not match image {tuple(image.shape)}")
+    if not 1 <= c <= 4:
+        raise ValueError(f"forward_warp: {c} channels, 1 .. 4 supported")
+    if w > FORWARD_WARP_MAX_W:
+        raise ValueError(f"forward_warp: width {w} is above the kernel's limit {FORWARD_WARP_MAX_W}")
+    if exclude is not None:
+        if (not isinstance(exclude, torch.Tensor) or not exclude.is_cuda or tuple(exclude.shape) != (b, h, w)
+                or exclude.dtype not in (torch.uint8, torch.bool)):
+            raise ValueError(f"forward_warp: exclude must be a {(b, h, w)} uint8 or bool tensor on the device")
+    if isinstance(max_diff, bool) or not isinstance(max_diff, (int, float)) or not (
+            max_diff >= 0 and math.isfinite(max_diff)):
+        raise ValueError(f"forward_warp: max_diff {max_diff} must be a finite number >= 0")
+    if isinstance(max_stretch, bool) or not isinstance(max_stretch, (int, float)) or not 1 <= max_stretch <= 64:
+        raise ValueError(f"forward_warp: max_stretch {max_stretch} must be in 1 .. 64")
+    if not isinstance(fill_value, (int, float)):
+        raise ValueError(f"forward_warp: fill_value {fill_value} must be a number")
+    dev = image.device
+    if isinstance(scale, torch.Tensor):
+        if not scale.is_cuda or scale.dtype != torch.float32 or tuple(scale.shape) != (b,):
+            raise ValueError(f"forward_warp: a tensor scale must be [{b}] float32 on the device")
+        sc = scale.contiguous()
+    elif isinstance(scale, (int, float)) and not isinstance(scale, bool):
+        sc = torch.full((b,), float(scale), device=dev, dtype=torch.float32)
+    else:
+        raise ValueError(f"forward_warp: scale must be a number or a [{b}] float32 device tensor")
+    if image.stride()[1:] != (h * w, w, 1) or (b > 1 and image.stride(0) < c * h * w):
+        image = image.contiguous()
+    ibs = image.stride(0) if b > 1 else c * h * w
+    d, dbs = _plane_view(disp, "disp")
+    e = None
+    if exclude is not None:
+        e = (exclude.view(torch.uint8) if exclude.dtype == torch.bool else exclude).contiguous()
+    out = torch.empty((b, c, h, w), device=dev, dtype=torch.float32)
+    zview = torch.empty((b, h, w), device=dev, dtype=torch.float32) if want_zview else None
+    state = torch.empty((b, h, w), device=dev, dtype=torch.uint8) if want_state else None
+    source = torch.empty((b, h, w), device=dev, dtype=torch.float32) if want_source else None
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    n = float(b * h * w)
+    rec = None if _probe is None else _probe_launch(
+        "forward_warp", 20.0 * n, n * (4.0 * (2 * c + 1) + (1.0 if e is not None else 0.0) +
+                                       (4.0 if want_zview else 0.0) + (1.0 if want_state else 0.0) +
+                                       (4.0 if want_source else 0.0)))
+    check(_lib.load().lea_forward_warp_f32(image.data_ptr(), ibs, d.data_ptr(), dbs, ptr(e), sc.data_ptr(), b, c, h, w,
+                                           float(max_diff), float(max_stretch), 1 if fill else 0, float(fill_value),
+                                           out.data_ptr(), ptr(zview), ptr(state), ptr(source), _stream()),
+          "lea_forward_warp_f32")
+    _probe_end(rec)
+    return WarpedView(out, zview, state, source)
+
+
 # ------------------------------------------------------------------ bf16 path (c8)
 # Activations: torch.bfloat16 [B, C/8, D, H, W, 8] ("c8": 8 channels per voxel word).
 

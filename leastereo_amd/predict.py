@@ -48,6 +48,13 @@ Restates the host-side steps around ``LEAStereo.forward`` (predict.py:144-243):
                        before the transform or the scene path; --pointcloud 1 then takes focal,
                        baseline and principal point from the rectification and leaves out the left
                        pixels that have no source
+  * ``novel_view_options`` / ``novel_view_of_map`` / ``save_view``  not in the reference: --novel_view S
+                       [--view_fill 0|1] warps the decoded left image forward to baseline fraction S
+                       (``kernels.forward_warp``) through the best map the other flags made -- the
+                       refined map under --refine, else the filled one under --lr_check, else the
+                       disparity; the pixels --lr_check and --speckle flag carry no surface -- and
+                       writes {index}_view.png and {index}_view_holes.png; at S = 1 the mean absolute
+                       difference to the real right image is printed
 Arithmetic runs on the HIP kernels; what stays on the host is file I/O (PIL, PFM, PNG).
 
     python predict.py --sceneflow=1 --maxdisp=192 --crop_height=576 --crop_width=960 \
@@ -405,6 +412,64 @@ def save_pointcloud(prefix, cloud):
     return write_ply(prefix + ".ply", cloud.xyz, cloud.rgb, cloud.normals)
 
 
+def novel_view_options(opt):
+    """--novel_view S [--view_fill 0|1] as a dict (s, fill); None without the flag.  Refuses an S
+    that is not finite, a fill that is neither 0 nor 1, and --satellite."""
+    s = getattr(opt, "novel_view", None)
+    if s is None:
+        return None
+    if not abs(s) < float("inf"):
+        raise ValueError(f"--novel_view {s}: a finite baseline fraction (0 = the left camera, 1 = the right one)")
+    fill = getattr(opt, "view_fill", 1)
+    if fill not in (0, 1):
+        raise ValueError(f"--view_fill {fill}: 0 or 1")
+    if getattr(opt, "satellite", 0):
+        raise NotImplementedError("--novel_view writes its files beside the --sceneflow outputs only")
+    return dict(s=float(s), fill=bool(fill))
+
+
+def novel_view_of_map(disp, exclude, left_u8, s, fill=True, right_u8=None, device="cuda"):
+    """``kernels.forward_warp`` of the decoded left image through a written map [h', w'] (numpy:
+    the disparity, the filled or the refined one, at the crop's or the scene's size) to baseline
+    fraction ``s``.  The map's origin in the image is ``map_origin``'s; ``exclude`` [h', w'] or
+    None: non-zero pixels carry no surface.  The image goes to float32 with torch ops, off the
+    hot path.  Returns (view uint8 [h', w', 3], holes bool [h', w'], mad): holes are the pixels
+    no surface covers (black with ``fill`` off, else taken from the background beside them);
+    mad is the mean absolute difference in grey levels to ``right_u8`` over the other pixels, or
+    None without it.  Refuses a map wider than the kernel's limit."""
+    from . import kernels
+    mh, mw = disp.shape
+    if mw > kernels.FORWARD_WARP_MAX_W:
+        raise ValueError(f"--novel_view: the map is {mw} pixels wide, the warp's limit is "
+                         f"{kernels.FORWARD_WARP_MAX_W}")
+    h, w = left_u8.shape[:2]
+    x0, y0 = map_origin(h, w, mh, mw)
+
+    def planes(img):
+        t = _device_u8(img[y0:y0 + mh, x0:x0 + mw], device)
+        return t[..., :3].permute(2, 0, 1).to(torch.float32).contiguous()[None]
+
+    d = torch.from_numpy(np.ascontiguousarray(disp, dtype=np.float32)).to(device)[None]
+    e = None if exclude is None else torch.from_numpy(np.ascontiguousarray(exclude != 0).view(np.uint8)).to(device)[None]
+    out = kernels.forward_warp(planes(left_u8), d, float(s), e, fill=bool(fill), want_zview=False)
+    holes = out.state[0] != 0
+    mad = None
+    if right_u8 is not None:
+        seen = ~holes
+        diff = (out.image[0] - planes(right_u8)[0]).abs().mean(0)
+        mad = float(diff[seen].mean().item()) if bool(seen.any().item()) else float("nan")
+    view = out.image[0].round().clamp(0, 255).to(torch.uint8).permute(1, 2, 0).contiguous()
+    return view.cpu().numpy(), holes.cpu().numpy(), mad
+
+
+def save_view(prefix, view, holes):
+    """<prefix>_view.png (the synthesised view) and <prefix>_view_holes.png (8-bit: 255 where no
+    surface of the source view covers the pixel)."""
+    from PIL import Image
+    Image.fromarray(view).save(prefix + "_view.png")
+    save_float_png(prefix + "_view_holes.png", np.where(holes, 255, 0).astype(np.uint8))
+
+
 def save_refined(prefix, refined, support, max_disp=192):
     """<prefix>_refined.npy (float32), <prefix>_refined.png (coloured like the disparity) and
     <prefix>_support.png (8-bit: the smoothed confidence, in [0, 1], scaled by 255)."""
@@ -586,6 +651,7 @@ def main(argv=None):
     speckle = speckle_options(opt)
     cloud_opt = pointcloud_options(opt)
     rect_opt = rectify_options(opt)
+    view_opt = novel_view_options(opt)
     if not torch.cuda.is_available():
         raise RuntimeError("leastereo_amd runs on a ROCm device only")
     set_rectifier(None if rect_opt is None else make_rectifier(**rect_opt))
@@ -676,6 +742,24 @@ def main(argv=None):
             save_pointcloud(os.path.join(opt.save_path, f"{index}"), cloud)
             print(f"{index}: point cloud of {cloud.xyz.shape[0]} points "
                   f"({100.0 * cloud.xyz.shape[0] / best.size:.2f} % of the pixels)")
+        if view_opt is not None:  # from the best map the other flags made, at its size
+            flagged = None if lr is None else lr[2] != 0
+            if speckle is not None:
+                flagged = removed if flagged is None else (flagged | removed)
+            if refined is not None:
+                best, flagged = refined[0], None
+            else:
+                best = disp if lr is None else lr[3]
+            if rect_opt is None:
+                left_img, right_img = load_images(leftname, rightname)
+            else:
+                left_img, right_img = last_rectified().left, last_rectified().right
+            view, holes, mad = novel_view_of_map(best, flagged, left_img, view_opt["s"], view_opt["fill"],
+                                                 right_img if view_opt["s"] == 1.0 else None)
+            save_view(os.path.join(opt.save_path, f"{index}"), view, holes)
+            print(f"{index}: view from baseline fraction {view_opt['s']:g}: {100.0 * float(holes.mean()):.2f} % of "
+                  f"the pixels are holes" + ("" if mad is None else
+                                             f"; mean absolute difference to the right image {mad:.3f} grey levels"))
         if opt.photo_check:
             warped, err, loss, l1, dssim = photometric_check(model, leftname, rightname, opt.crop_height,
                                                              opt.crop_width, opt.lr_check)

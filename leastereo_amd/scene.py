@@ -384,3 +384,44 @@ def points_scene(result: SceneResult, Q, left_u8=None, use: str = "refined", ref
             image = image[0]
         image = image.to(disp.device, non_blocking=True)
     return kernels.reproject(disp, Q, image, result.state, **kw)
+
+
+@torch.no_grad()
+def view_scene(result: SceneResult, left_u8, s: float = 1.0, use: str = "refined", refined: torch.Tensor = None,
+               refine: dict = None, **kw):
+    """``kernels.forward_warp`` of a ``SceneResult``, once, at scene size, after the blend: the
+    uint8 scene ``left_u8`` [H, W, 3|4] as seen from baseline fraction ``s`` (0 = the left camera,
+    1 = the right one) through the map ``use`` names, chosen as ``points_scene`` chooses it, with
+    ``exclude`` = ``result.state`` when the runner ran the left-right check (or ``speckle_scene``
+    put its state there) and the map is not the refined one, which has no flagged pixels left.
+    The image is converted to float32 with torch ops (the kernel takes no uint8), so the view's
+    colours are on the 0 .. 255 scale.  ``kw``: the other keywords of ``forward_warp``.  Returns
+    ``kernels.WarpedView`` without a batch axis (image [3, H, W]).  Refuses a scene wider than
+    ``kernels.FORWARD_WARP_MAX_W``."""
+    from . import kernels
+    if use not in ("refined", "filled", "disp"):
+        raise ValueError(f"view_scene: use {use!r}: one of refined, filled, disp")
+    if result.disp.shape[-1] > kernels.FORWARD_WARP_MAX_W:
+        raise ValueError(f"view_scene: the scene is {result.disp.shape[-1]} wide, the warp's limit is "
+                         f"{kernels.FORWARD_WARP_MAX_W}")
+    if use == "refined" and refined is None:
+        refined = refine_scene(result, left_u8, **({} if refine is None else refine))
+    disp = {"refined": refined, "filled": result.disp_filled, "disp": result.disp}[use]
+    if disp is None:
+        raise ValueError("view_scene: use='filled', but the result holds no filled disparity (the runner ran no "
+                         "left-right check)")
+    if tuple(disp.shape) != tuple(result.disp.shape):
+        raise ValueError(f"view_scene: the map is {tuple(disp.shape)}, the scene {tuple(result.disp.shape)}")
+    image = left_u8
+    if isinstance(image, np.ndarray):
+        image = torch.from_numpy(np.ascontiguousarray(image))
+    if image.dim() == 4 and image.shape[0] == 1:
+        image = image[0]
+    if image.dtype != torch.uint8 or image.dim() != 3 or tuple(image.shape[:2]) != tuple(disp.shape):
+        raise ValueError(f"view_scene: left_u8 must be uint8 [H, W, 3|4] of the result's size {tuple(disp.shape)}, got "
+                         f"{image.dtype} {tuple(image.shape)}")
+    image = image.to(disp.device, non_blocking=True)[..., :3].permute(2, 0, 1).to(torch.float32).contiguous()
+    exclude = None if use != "disp" else result.state
+    out = kernels.forward_warp(image[None], disp[None].contiguous(), float(s),
+                               None if exclude is None else exclude[None], **kw)
+    return kernels.WarpedView(*(None if t is None else t[0] for t in out))

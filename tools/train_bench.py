@@ -129,6 +129,11 @@ def main():
                     help="1 (with --whole 1): the step starts from decoded uint8 pairs of --src_height x "
                          "--src_width and their disparity, standardised, random-cropped to --height x --width "
                          "and cut to the target on the device (leastereo_amd.data.DeviceTrainTransform)")
+    ap.add_argument("--warp_aug", type=float, default=0.0, metavar="P",
+                    help="> 0 (with --whole 1): after the plain step, time the step with "
+                         "leastereo_amd.synthesis.DisparityScaleAugment(prob=P) in front of it -- the right view "
+                         "re-synthesised from the left image and the target (the data here is synthetic, so "
+                         "the from-left path) -- and print it on a second line beside the plain one; 0: off")
     ap.add_argument("--src_height", type=int, default=540)
     ap.add_argument("--src_width", type=int, default=960)
     ap.add_argument("--torch-modes", default="default,benchmark",
@@ -193,13 +198,24 @@ def whole_model(args, dev):
         disp_u8 = torch.rand(src, device=dev, generator=gen) * (args.maxdisp - 1)
         tf = DeviceTrainTransform(args.height, args.width, args.maxdisp, device=dev)
 
-    def step(edge_loss_w=args.edge_loss_w, photo_loss_w=args.photo_loss_w):
+    aug = None
+    if args.warp_aug:
+        from leastereo_amd.synthesis import DisparityScaleAugment
+        aug = DisparityScaleAugment(prob=args.warp_aug, device=dev, maxdisp=args.maxdisp)
+
+    def step(edge_loss_w=args.edge_loss_w, photo_loss_w=args.photo_loss_w, warp=False):
         nonlocal left, right, target
         opt.zero_grad()
         if tf is not None:
             batch = tf(left_u8, right_u8, disp_u8)
             left, right = batch.left.requires_grad_(True), batch.right.requires_grad_(True)
             target = batch.target.squeeze(1)
+        if warp:  # a fresh scale every step; the plain step's tensors stay as they are
+            pair = aug(left.detach(), right.detach(), target)
+            return finish(left, pair.right.requires_grad_(True), pair.disp_left, edge_loss_w, photo_loss_w)
+        return finish(left, right, target, edge_loss_w, photo_loss_w)
+
+    def finish(left, right, target, edge_loss_w, photo_loss_w):
         disp = model(left, right)
         if edge_loss_w:
             loss = losses.combined_loss(disp, target, args.maxdisp, edge_loss_w)
@@ -242,6 +258,10 @@ def whole_model(args, dev):
     if tf is not None:
         line.update({"device_transform": 1, "src_height": args.src_height, "src_width": args.src_width})
     print(json.dumps(line), flush=True)
+    if aug is not None:  # the same step behind the augmentation, in the same process
+        ms_aug = timed(lambda: step(warp=True), args.steps, args.warmup)
+        print(json.dumps(dict(line, what="whole_model_train_step_warp_aug", warp_aug=args.warp_aug, ms_plain=line["ms"],
+                              ms=round(ms_aug, 2))), flush=True)
 
 
 if __name__ == "__main__":
