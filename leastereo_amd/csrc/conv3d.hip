@@ -586,6 +586,7 @@ inline Plan make_plan(int B, int cout, int D, int H, int W, int k, bool resample
   }
   if (k == 3 && cout <= 2 && !resample) {
     p.engine = 3;
+    p.mt = cout;  // conv3d_valu_kernel<cout> (plan_name; one cout block either way)
     p.nt = 0;
     p.tw = 64;
     return p;

@@ -9,6 +9,11 @@ EPE of the PyTorch reference in fp32):
   disparity regression   |d| <= 2e-5 px
   ConvBR2d / feature net |d| <= 1e-4 + 1e-4*|ref| (per op), 1e-4 (whole net vs golden)
   end to end             EPE <= 1e-3 px vs reference fp32 and fp64 disparities
+
+The ConvBR3d bar here is coarse (N(0,1) inputs, 1e-4): the tight bar of the fp32 conv engines'
+dispatch paths (4 x a float32 model of each algorithm, seven input distributions) and of the
+disparity forms on sharp and shifted volumes is tests/test_gpu_f32_numerics.py (DESIGN.md,
+"fp32 engine numerics").
 """
 import numpy as np
 import pytest

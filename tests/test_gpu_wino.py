@@ -3,7 +3,12 @@ against float64 torch, with the tolerance of the direct fp32 engine
 (|d| <= 1e-4 + 1e-4 |ref|, test_gpu_parity.py) -- the transforms add a few fp32
 roundings per product, far inside it -- and against the direct engine itself.
 End to end the model runs on this engine by default, so test_gpu_parity.py's
-e2e / config-1 / full-size cases cover it at EPE <= 1e-3 px."""
+e2e / config-1 / full-size cases cover it at EPE <= 1e-3 px.
+
+That bar is a coarse one (two to three decimal digits above a correct float32 engine, on
+N(0,1) inputs only): the tight bar of every Winograd dispatch path -- 4 x a float32 model of
+its algorithm, on inputs with DC offsets, large magnitudes and outliers -- is
+tests/test_gpu_f32_numerics.py (DESIGN.md, "fp32 engine numerics")."""
 import os
 
 import numpy as np
