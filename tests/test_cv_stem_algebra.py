@@ -7,53 +7,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import torch_ref as ref
-
-
-def split_weights(w):
-    """lea_cv_stem_split_weights restated: [cout, 2C, 3, 3, 3] -> wl [9 cout, C, 3, 3],
-    wr [6 cout, C, 3, 3]."""
-    cout, c2 = w.shape[:2]
-    c = c2 // 2
-    wl = torch.zeros(9 * cout, c, 3, 3, dtype=w.dtype)
-    wr = torch.zeros(6 * cout, c, 3, 3, dtype=w.dtype)
-    for kd in range(3):
-        for t in range(3):
-            blk = w[:, :c, kd].clone()
-            blk[..., :t] = 0
-            wl[(3 * kd + t) * cout:(3 * kd + t + 1) * cout] = blk
-        wr[kd * cout:(kd + 1) * cout] = w[:, c:, kd]
-        wr[(3 + kd) * cout:(4 + kd) * cout, :, :, 1] = w[:, c:, kd, :, 2]
-    return wl, wr
-
-
-def combine(lm, rm, cout, d3):
-    """lea_cv_stem_combine's sum (pre-BN), restated with explicit loops over planes."""
-    b, _, h, wd = lm.shape
-    lk = lm.view(b, 3, 3, cout, h, wd)
-    bk = rm[:, :3 * cout].view(b, 3, cout, h, wd)
-    k2 = rm[:, 3 * cout:].view(b, 3, cout, h, wd)
-    out = torch.zeros(b, cout, d3, h, wd, dtype=lm.dtype)
-    cols = torch.arange(wd)
-    for d in range(d3):
-        u = cols - d
-        for kd in range(3):
-            if not 0 <= d + kd - 1 < d3:
-                continue
-            t = (kd - u).clamp(min=0)
-            left = torch.zeros(b, cout, h, wd, dtype=lm.dtype)
-            for tv in range(3):
-                sel = t == tv
-                left[..., sel] = lk[:, kd, tv][..., sel]
-            z = u - kd + 1
-            right = torch.zeros_like(left)
-            ok = (z >= 0) & (z < wd)
-            right[..., ok] = bk[:, kd][..., z[ok]]
-            right[..., z == -1] = k2[:, kd][..., 0:1].expand_as(right[..., z == -1])
-            x = u[-1] - kd + 2  # last column: taps past the volume's right edge
-            if 0 <= x < wd:
-                right[..., -1] -= k2[:, kd][..., x]
-            out[:, :, d] += left + right
-    return out
+from tests.feature_judge import combine, split_weights
 
 
 @pytest.mark.parametrize("b,c,cout,maxdisp,hw", [(1, 4, 8, 27, (5, 8)), (2, 3, 4, 48, (4, 21)),
