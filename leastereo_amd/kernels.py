@@ -16,11 +16,15 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import LEA_F32, LEA_PAIR_SUM, LEA_RELU, LEA_RESIDUAL, check
+from ._lib import LEA_BF16, LEA_F32, LEA_PAIR_SUM, LEA_RELU, LEA_RESIDUAL, check
 
 
 def _stream():
     return torch.cuda.current_stream().cuda_stream
+
+
+# one launch's probe record; positional use (r[0], r[2], r[6]) is part of the interface
+ProbeRecord = collections.namedtuple("ProbeRecord", "name flops bytes start end mfma_flops shape")
 
 
 class KernelProbe:
@@ -33,7 +37,7 @@ class KernelProbe:
 
     def __init__(self, names=None):
         self.names = None if names is None else set(names)
-        self.records = []  # (name, flops, bytes, start_event, end_event, mfma_flops, shape)
+        self.records = []  # ProbeRecord(name, flops, bytes, start_event, end_event, mfma_flops, shape)
 
     def __enter__(self):
         global _probe
@@ -44,41 +48,108 @@ class KernelProbe:
         global _probe
         _probe = None
 
-    def summary(self):
+    def _totals(self, key, name=None):
         torch.cuda.synchronize()
         out = {}
-        for name, flops, nbytes, e0, e1, mfma, _ in self.records:
-            d = out.setdefault(name, {"launches": 0, "flops": 0.0, "bytes": 0.0, "ms": 0.0,
-                                      "mfma_flops": 0.0})
+        for r in self.records:
+            if name is not None and r.name != name:
+                continue
+            d = out.setdefault(key(r), {"launches": 0, "flops": 0.0, "bytes": 0.0, "ms": 0.0, "mfma_flops": 0.0})
             d["launches"] += 1
-            d["flops"] += flops
-            d["bytes"] += nbytes
-            d["ms"] += e0.elapsed_time(e1)
-            d["mfma_flops"] += mfma
+            d["flops"] += r.flops
+            d["bytes"] += r.bytes
+            d["ms"] += r.start.elapsed_time(r.end)
+            d["mfma_flops"] += r.mfma_flops
         return out
+
+    def summary(self):
+        return self._totals(lambda r: r.name)
 
     def by_shape(self, name):
         """Launches of kernel ``name`` grouped by layer shape (B, cin, cout, D, H, W, k)."""
-        torch.cuda.synchronize()
-        out = {}
-        for n, flops, nbytes, e0, e1, mfma, shape in self.records:
-            if n != name:
-                continue
-            d = out.setdefault(shape, {"launches": 0, "flops": 0.0, "bytes": 0.0, "ms": 0.0, "mfma_flops": 0.0})
-            d["launches"] += 1
-            d["flops"] += flops
-            d["bytes"] += nbytes
-            d["ms"] += e0.elapsed_time(e1)
-            d["mfma_flops"] += mfma
-        return out
+        return self._totals(lambda r: r.shape, name)
 
 
 _probe = None
 
 
-def conv_kernel_name(b, cout, d, h, w, k, resampled=False):
-    name = _lib.load().lea_conv3d_kernel_name(b, cout, d, h, w, k, 1 if resampled else 0)
+def _conv_record(b, cin, cout, d, h, w, k, accumulate, in_vox, resampled, name=None, mfma_scale=1.0,
+                 esz=4, nbytes=None):
+    """The probe record of a 3D conv launch, or None if the active probe does not want its kernel.
+    ``flops`` is the direct convolution's (the reference algorithm's) count;
+    ``mfma_scale`` converts it to the products the kernel actually issues (2/3 for
+    Winograd F(2,3), times its cout padding); ``esz`` is the activation element size;
+    ``nbytes`` replaces the algorithmic byte count (input + output [+ residual] + weights)."""
+    if name is None:
+        name = conv_kernel_name(b, cout, d, h, w, k, resampled)
+    if _probe.names is not None and name not in _probe.names:
+        return None
+    vox = b * d * h * w
+    flops = 2.0 * vox * cout * cin * k ** 3
+    if nbytes is None:
+        nbytes = esz * (in_vox * cin + vox * cout * (2 if accumulate else 1)) + 4.0 * cout * cin * k ** 3
+    return ProbeRecord(name, flops, nbytes, None, None, flops * mfma_scale, (b, cin, cout, d, h, w, k))
+
+
+def _op_record(name, flops, nbytes, mfma=None, shape=None):
+    """The probe record of a launch that is not a 3D conv (2D convs, resamples, the head, the
+    disparity regression, layout conversions), or None if the active probe does not want it:
+    ``flops`` / ``nbytes`` are its algorithmic work, ``mfma`` the matrix-core products it issues
+    (default: flops)."""
+    if _probe.names is not None and name not in _probe.names:
+        return None
+    return ProbeRecord(name, float(flops), float(nbytes), None, None, float(flops if mfma is None else mfma), shape)
+
+
+@contextlib.contextmanager
+def _timed(record):
+    """HIP-event timing of what the block launches, as one record of the active probe.  ``record``
+    is a callable that returns the launch's ``_conv_record`` / ``_op_record``; it is called only
+    while a KernelProbe is active, so without one a launch costs no event, no kernel-name query
+    and no arithmetic.  A block that raises records nothing."""
+    probe = _probe
+    rec = None if probe is None or record is None else record()
+    if rec is None:
+        yield
+        return
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    yield
+    e1.record()
+    probe.records.append(rec._replace(start=e0, end=e1))
+
+
+def _call(entry, *args):
+    """The return code of library entry point ``entry`` (a key of ``_lib.SIGNATURES``) called with
+    ``args`` and, last, the current stream."""
+    return getattr(_lib.load(), entry)(*args, _stream())
+
+
+def _launch(entry, *args, probe=None):
+    """Launch ``entry`` on the current stream and raise on failure; ``probe``: see ``_timed``."""
+    if _probe is None or probe is None:
+        check(_call(entry, *args), entry)
+    else:
+        with _timed(probe):
+            check(_call(entry, *args), entry)
+
+
+# ---- operand checks shared by the wrappers ----
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _contiguous(t):
+    return None if t is None else t.contiguous()
+
+
+def _decode(name):
     return name.decode() if name else None
+
+
+def _flags(relu, residual=False, pair_sum=False):
+    return (LEA_RELU if relu else 0) | (LEA_RESIDUAL if residual else 0) | (LEA_PAIR_SUM if pair_sum else 0)
 
 
 def _require_cuda(*ts):
@@ -97,6 +168,155 @@ def _check_volume_view(t: torch.Tensor, name: str):
     return t.stride(0)
 
 
+def _f32_volume(t, aligned):
+    """Whether ``t`` is an f32 NCDHW device tensor with contiguous C,D,H,W, with ``aligned`` also
+    16-byte aligned with batch strides of whole 16-byte words (the ``*_supported`` queries)."""
+    if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 5:
+        return False
+    d, h, w = t.shape[2:]
+    if aligned and (t.data_ptr() % 16 or t.stride(0) % 4):
+        return False
+    return t.stride()[1:] == (d * h * w, h * w, w, 1)
+
+
+def _number(who, name, v, want, lo=None, hi=None, finite=False, integer=False, bools=False):
+    """ValueError ``who: name v must be want`` unless ``v`` is an int or float (an int with
+    ``integer``; a bool only with ``bools``), finite with ``finite``, and, given bounds,
+    lo <= v <= hi (which no NaN passes; ``lo=-inf`` is the check for NaN alone)."""
+    ok = isinstance(v, int if integer else (int, float)) and (bools or not isinstance(v, bool))
+    if ok and lo is not None:
+        ok = lo <= v <= (math.inf if hi is None else hi)
+    if not ok or (finite and not math.isfinite(v)):
+        raise ValueError(f"{who}: {name} {v} must be {want}")
+
+
+def _exclude_u8(exclude, shape, who=None):
+    """The exclude mask of the disparity post-processing: None, or a uint8 or bool device tensor
+    of ``shape``, returned as uint8 (a view; the caller makes it contiguous where it stages its
+    operands).  ``who`` prefixes the message and names the shape."""
+    if exclude is None:
+        return None
+    if (not isinstance(exclude, torch.Tensor) or not exclude.is_cuda or tuple(exclude.shape) != shape
+            or exclude.dtype not in (torch.uint8, torch.bool)):
+        raise ValueError("exclude must be a [B, H, W] uint8 or bool tensor on the device" if who is None else
+                         f"{who}: exclude must be a {shape} uint8 or bool tensor on the device")
+    return exclude.view(torch.uint8) if exclude.dtype == torch.bool else exclude
+
+
+def _as_f32(a, device, what) -> torch.Tensor:
+    """An array or tensor as a contiguous float32 tensor on the device; one that is that already
+    is used in place.  ``what`` opens the message for one that is not floating point."""
+    if not isinstance(a, torch.Tensor):
+        a = torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64)).astype(np.float32))
+    if not a.dtype.is_floating_point:
+        raise ValueError(f"{what}, got {a.dtype}")
+    return a.to(device=device, dtype=torch.float32).contiguous()
+
+
+def _feature_pair(fl, fr):
+    """The two feature maps of a cost-volume conv, read in place: returns (B, C, H, W)."""
+    if fl.shape != fr.shape or fl.dim() != 4:
+        raise ValueError("left/right features must both be [B, C, H, W]")
+    if fl.stride() != fr.stride() or fl.stride()[1:] != (fl.shape[2] * fl.shape[3], fl.shape[3], 1):
+        raise ValueError("left/right features need contiguous C,H,W and equal strides")
+    return fl.shape
+
+
+def _head_cost(cost):
+    """The matching cost of the disparity heads, contiguous, and its (B, D3, H3, W3)."""
+    _require_cuda(cost)
+    if cost.dim() != 5 or cost.shape[1] != 1:
+        raise ValueError("cost must be [B, 1, D3, H3, W3]")
+    cost = cost.contiguous()
+    b, _, d3, h3, w3 = cost.shape
+    return cost, b, d3, h3, w3
+
+
+def _sums_scales(sums, scales, of, parts):
+    """The backward operands of the two losses: ``sums`` as ``of`` returned it, ``scales`` two
+    float32 (``parts``) on the device."""
+    _require_cuda(scales)
+    if not sums.is_cuda or sums.dtype != torch.float64 or sums.numel() != 4 or not sums.is_contiguous():
+        raise ValueError(f"sums: the contiguous float64 [4] device tensor of {of}")
+    if scales.numel() != 2 or not scales.is_contiguous():
+        raise ValueError(f"scales: two contiguous float32 ({parts}) on the device")
+
+
+# Activation layouts: f32 NCDHW [B, C, D, H, W], or bf16 "c8" [B, C/8, D, H, W, 8] (8 channels per
+# voxel word); the helpers below take ``c8`` to choose.
+
+def _require_c8(*ts):
+    for t in ts:
+        if t is not None and (not t.is_cuda or t.dtype != torch.bfloat16 or t.dim() != 6
+                              or t.shape[-1] != 8):
+            raise _lib.HipKernelError(
+                f"bf16 path needs [B, C/8, D, H, W, 8] bfloat16 ROCm tensors, got {t.dtype} "
+                f"{tuple(t.shape)} on {t.device}")
+
+
+def _check_c8_view(t: torch.Tensor, name: str):
+    b, cb, d, h, w, _ = t.shape
+    if t.stride()[1:] != (d * h * w * 8, h * w * 8, w * 8, 8, 1):
+        raise ValueError(f"{name}: c8 block slice with contiguous blocks required, strides {t.stride()}")
+    return t.stride(0)
+
+
+def _batch_stride(t, name, c8=False):
+    return _check_c8_view(t, name) if c8 else _check_volume_view(t, name)
+
+
+def _act_shape(b, c, spatial, c8=False):
+    spatial = tuple(int(s) for s in spatial)
+    return (b, c // 8) + spatial + (8,) if c8 else (b, c) + spatial
+
+
+def _out_view(t, shape, device, c8=False, name="out"):
+    """``t``, or with None a new tensor, of ``shape`` in the layout (``t`` may be a channel slice
+    of a larger tensor); returns it and its batch stride."""
+    if t is None:
+        t = torch.empty(shape, device=device, dtype=torch.bfloat16 if c8 else torch.float32)
+    if tuple(t.shape) != shape:
+        raise ValueError(f"{name} shape {tuple(t.shape)} != {shape}")
+    return t, _batch_stride(t, name, c8)
+
+
+def _conv_out(b, cout, spatial, out, accumulate, device, c8=False):
+    if out is None and accumulate:
+        raise ValueError("accumulate needs out")
+    return _out_view(out, _act_shape(b, cout, spatial, c8), device, c8)
+
+
+def _residual(out, accumulate, residual, ybs, c8=False, shape=None):
+    """(pointer, batch stride) of the epilogue's residual: ``out`` itself under
+    ``accumulate``, else an explicit tensor of out's shape (``shape`` where there is no out),
+    or none."""
+    if accumulate:
+        if residual is not None:
+            raise ValueError("accumulate and residual are exclusive")
+        return out.data_ptr(), ybs
+    if residual is None:
+        return None, 0
+    (_require_c8 if c8 else _require_cuda)(residual)
+    shape = tuple(out.shape) if shape is None else shape
+    if tuple(residual.shape) != shape:
+        raise ValueError(f"residual shape {tuple(residual.shape)} != {shape}")
+    return residual.data_ptr(), _batch_stride(residual, "residual", c8)
+
+
+def _second_source(x2, b, spatial, c8=False):
+    """(pointer, batch stride, channels) of a conv's optional second source, read as
+    ``torch.cat((x, x2), 1)`` without the copy; (None, 0, 0) without one."""
+    if x2 is None:
+        return None, 0, 0
+    if x2.shape[0] != b or tuple(x2.shape[2:5]) != spatial:
+        raise ValueError("x2 must match x in batch and volume")
+    return x2.data_ptr(), _batch_stride(x2, "x2", c8), x2.shape[1] * (8 if c8 else 1)
+
+
+def conv_kernel_name(b, cout, d, h, w, k, resampled=False):
+    return _decode(_lib.load().lea_conv3d_kernel_name(b, cout, d, h, w, k, 1 if resampled else 0))
+
+
 def build_cost_volume(fl: torch.Tensor, fr: torch.Tensor, maxdisp: int) -> torch.Tensor:
     """retrain/LEAStereo.py:34-48 -> [B, 2C, int(maxdisp/3), H, W]."""
     _require_cuda(fl, fr)
@@ -106,8 +326,7 @@ def build_cost_volume(fl: torch.Tensor, fr: torch.Tensor, maxdisp: int) -> torch
     b, c, h, w = fl.shape
     d3 = int(maxdisp / 3)
     cost = torch.empty((b, 2 * c, d3, h, w), device=fl.device, dtype=fl.dtype)
-    check(_lib.load().lea_build_cost_volume(fl.data_ptr(), fr.data_ptr(), cost.data_ptr(), b, c, h,
-                                            w, d3, LEA_F32, _stream()), "lea_build_cost_volume")
+    _launch("lea_build_cost_volume", fl.data_ptr(), fr.data_ptr(), cost.data_ptr(), b, c, h, w, d3, LEA_F32)
     return cost
 
 
@@ -124,77 +343,8 @@ def pack_conv_weight(w: torch.Tensor) -> torch.Tensor:
     w = w.detach().contiguous()
     cout, cin, k = w.shape[0], w.shape[1], w.shape[-1]
     packed = torch.empty(packed_floats(cout, cin, k), device=w.device, dtype=torch.float32)
-    check(_lib.load().lea_conv3d_pack_weights(w.data_ptr(), packed.data_ptr(), cout, cin, k,
-                                              _stream()), "lea_conv3d_pack_weights")
+    _launch("lea_conv3d_pack_weights", w.data_ptr(), packed.data_ptr(), cout, cin, k)
     return packed
-
-
-def _probe_begin(b, cin, cout, d, h, w, k, accumulate, in_vox, resampled, name=None, mfma_scale=1.0,
-                 esz=4):
-    """Start HIP-event timing of this launch if the active probe wants its kernel.
-    ``flops`` is the direct convolution's (the reference algorithm's) count;
-    ``mfma_scale`` converts it to the products the kernel actually issues (2/3 for
-    Winograd F(2,3), times its cout padding); ``esz`` is the activation element size."""
-    probe = _probe
-    if probe is None:
-        return None
-    if name is None:
-        name = conv_kernel_name(b, cout, d, h, w, k, resampled)
-    if probe.names is not None and name not in probe.names:
-        return None
-    vox = b * d * h * w
-    flops = 2.0 * vox * cout * cin * k ** 3
-    nbytes = esz * (in_vox * cin + vox * cout * (2 if accumulate else 1)) + 4.0 * cout * cin * k ** 3
-    e0 = torch.cuda.Event(enable_timing=True)
-    e0.record()
-    return probe, name, flops, nbytes, e0, flops * mfma_scale, (b, cin, cout, d, h, w, k)
-
-
-def _probe_launch(name, flops, nbytes, mfma=None):
-    """Start HIP-event timing of a launch that is not a 3D conv (2D convs, resamples,
-    the head, the disparity regression, layout conversions): ``flops`` / ``nbytes`` are
-    its algorithmic work, ``mfma`` the matrix-core products it issues (default: flops)."""
-    probe = _probe
-    if probe is None or (probe.names is not None and name not in probe.names):
-        return None
-    e0 = torch.cuda.Event(enable_timing=True)
-    e0.record()
-    return probe, name, float(flops), float(nbytes), e0, float(flops if mfma is None else mfma), None
-
-
-def _probe_end(rec):
-    if rec is not None:
-        probe, name, flops, nbytes, e0, mfma, shape = rec
-        e1 = torch.cuda.Event(enable_timing=True)
-        e1.record()
-        probe.records.append((name, flops, nbytes, e0, e1, mfma, shape))
-
-
-def _conv_out(x_shape5, cout, spatial, out, accumulate, device, dtype):
-    b = x_shape5[0]
-    shape = (b, cout) + tuple(int(s) for s in spatial)
-    if out is None:
-        if accumulate:
-            raise ValueError("accumulate needs out")
-        out = torch.empty(shape, device=device, dtype=dtype)
-    if tuple(out.shape) != shape:
-        raise ValueError(f"out shape {tuple(out.shape)} != {shape}")
-    return out, _check_volume_view(out, "out")
-
-
-def _residual(out, accumulate, residual, ybs):
-    """(pointer, batch stride) of the epilogue's residual: ``out`` itself under
-    ``accumulate``, else an explicit tensor of out's shape (or none)."""
-    if accumulate:
-        if residual is not None:
-            raise ValueError("accumulate and residual are exclusive")
-        return out.data_ptr(), ybs
-    if residual is None:
-        return None, 0
-    _require_cuda(residual)
-    if tuple(residual.shape) != tuple(out.shape):
-        raise ValueError(f"residual shape {tuple(residual.shape)} != {tuple(out.shape)}")
-    return residual.data_ptr(), _check_volume_view(residual, "residual")
 
 
 def conv3d_bnrelu(x: torch.Tensor, packed: torch.Tensor, cout: int, k: int,
@@ -209,30 +359,18 @@ def conv3d_bnrelu(x: torch.Tensor, packed: torch.Tensor, cout: int, k: int,
     _require_cuda(x, x2, packed, scale, shift, out)
     b, cin, d, h, w = x.shape
     xbs = _check_volume_view(x, "x")
-    cin2, x2bs = 0, 0
-    if x2 is not None:
-        if x2.shape[0] != b or tuple(x2.shape[2:]) != (d, h, w):
-            raise ValueError("x2 must match x in batch and volume")
-        cin2 = x2.shape[1]
-        x2bs = _check_volume_view(x2, "x2")
-    out, ybs = _conv_out(x.shape, cout, (d, h, w), out, accumulate, x.device, x.dtype)
+    x2ptr, x2bs, cin2 = _second_source(x2, b, (d, h, w))
+    out, ybs = _conv_out(b, cout, (d, h, w), out, accumulate, x.device)
     rptr, rbs = _residual(out, accumulate, residual, ybs)
-    flags = (LEA_RELU if relu else 0) | (LEA_RESIDUAL if rptr is not None else 0)
-    rec = _probe_begin(b, cin + cin2, cout, d, h, w, k, rptr is not None, b * d * h * w, False)
-    check(_lib.load().lea_conv3d_bnrelu(
-        x.data_ptr(), xbs, x2.data_ptr() if x2 is not None else None, x2bs, cin2,
-        packed.data_ptr(),
-        scale.data_ptr() if scale is not None else None,
-        shift.data_ptr() if shift is not None else None,
-        rptr, rbs, out.data_ptr(), ybs, b, cin + cin2, cout, d, h, w, k, flags, LEA_F32, _stream()),
-        "lea_conv3d_bnrelu")
-    _probe_end(rec)
+    _launch("lea_conv3d_bnrelu", x.data_ptr(), xbs, x2ptr, x2bs, cin2, packed.data_ptr(), _ptr(scale),
+            _ptr(shift), rptr, rbs, out.data_ptr(), ybs, b, cin + cin2, cout, d, h, w, k,
+            _flags(relu, rptr is not None), LEA_F32,
+            probe=lambda: _conv_record(b, cin + cin2, cout, d, h, w, k, rptr is not None, b * d * h * w, False))
     return out
 
 
 def costvolume_kernel_name(b, cout, d3, h, w):
-    name = _lib.load().lea_conv3d_costvolume_kernel_name(b, cout, d3, h, w)
-    return name.decode() if name else None
+    return _decode(_lib.load().lea_conv3d_costvolume_kernel_name(b, cout, d3, h, w))
 
 
 def conv3d_bnrelu_costvolume(fl: torch.Tensor, fr: torch.Tensor, maxdisp: int, packed: torch.Tensor,
@@ -242,21 +380,13 @@ def conv3d_bnrelu_costvolume(fl: torch.Tensor, fr: torch.Tensor, maxdisp: int, p
     skip_model_3d.py:141) without materialising the volume; bit-identical to
     ``conv3d_bnrelu(build_cost_volume(fl, fr, maxdisp), ...)``."""
     _require_cuda(fl, fr, packed, scale, shift)
-    if fl.shape != fr.shape or fl.dim() != 4:
-        raise ValueError("left/right features must both be [B, C, H, W]")
-    if fl.stride() != fr.stride() or fl.stride()[1:] != (fl.shape[2] * fl.shape[3], fl.shape[3], 1):
-        raise ValueError("left/right features need contiguous C,H,W and equal strides")
-    b, c, h, w = fl.shape
+    b, c, h, w = _feature_pair(fl, fr)
     d3 = int(maxdisp / 3)
     out = torch.empty((b, cout, d3, h, w), device=fl.device, dtype=fl.dtype)
-    rec = None if _probe is None else _probe_begin(b, 2 * c, cout, d3, h, w, 3, False, 0, False,
-                                                   name=costvolume_kernel_name(b, cout, d3, h, w))
-    check(_lib.load().lea_conv3d_bnrelu_costvolume(
-        fl.data_ptr(), fr.data_ptr(), fl.stride(0), packed.data_ptr(),
-        scale.data_ptr() if scale is not None else None,
-        shift.data_ptr() if shift is not None else None, out.data_ptr(), out.stride(0), b, c, cout,
-        d3, h, w, LEA_RELU if relu else 0, LEA_F32, _stream()), "lea_conv3d_bnrelu_costvolume")
-    _probe_end(rec)
+    _launch("lea_conv3d_bnrelu_costvolume", fl.data_ptr(), fr.data_ptr(), fl.stride(0), packed.data_ptr(),
+            _ptr(scale), _ptr(shift), out.data_ptr(), out.stride(0), b, c, cout, d3, h, w, _flags(relu), LEA_F32,
+            probe=lambda: _conv_record(b, 2 * c, cout, d3, h, w, 3, False, 0, False,
+                                       name=costvolume_kernel_name(b, cout, d3, h, w)))
     return out
 
 
@@ -270,17 +400,12 @@ def conv3d_bnrelu_resampled(x: torch.Tensor, size, packed: torch.Tensor, cout: i
     b, cin, di, hi, wi = x.shape
     d, h, w = (int(s) for s in size)
     xbs = _check_volume_view(x, "x")
-    out, ybs = _conv_out(x.shape, cout, (d, h, w), out, accumulate, x.device, x.dtype)
-    flags = (LEA_RELU if relu else 0) | (LEA_RESIDUAL if accumulate else 0)
-    rec = _probe_begin(b, cin, cout, d, h, w, k, accumulate, b * di * hi * wi, True)
-    check(_lib.load().lea_conv3d_bnrelu_resampled(
-        x.data_ptr(), xbs, di, hi, wi, packed.data_ptr(),
-        scale.data_ptr() if scale is not None else None,
-        shift.data_ptr() if shift is not None else None,
-        out.data_ptr() if accumulate else None, ybs if accumulate else 0,
-        out.data_ptr(), ybs, b, cin, cout, d, h, w, k, flags, LEA_F32, _stream()),
-        "lea_conv3d_bnrelu_resampled")
-    _probe_end(rec)
+    out, ybs = _conv_out(b, cout, (d, h, w), out, accumulate, x.device)
+    rptr, rbs = _residual(out, accumulate, None, ybs)
+    _launch("lea_conv3d_bnrelu_resampled", x.data_ptr(), xbs, di, hi, wi, packed.data_ptr(), _ptr(scale),
+            _ptr(shift), rptr, rbs, out.data_ptr(), ybs, b, cin, cout, d, h, w, k, _flags(relu, accumulate),
+            LEA_F32,
+            probe=lambda: _conv_record(b, cin, cout, d, h, w, k, accumulate, b * di * hi * wi, True))
     return out
 
 
@@ -290,22 +415,25 @@ def conv3d_bnrelu_resampled(x: torch.Tensor, size, packed: torch.Tensor, cout: i
 
 def conv2d_kernel_name(b, cout, h, w, cin=None):
     lib = _lib.load()
-    name = (lib.lea_conv2d_kernel_name(b, cout, h, w) if cin is None
-            else lib.lea_conv2d_kernel_name_cin(b, cin, cout, h, w))
-    return name.decode() if name else None
+    return _decode(lib.lea_conv2d_kernel_name(b, cout, h, w) if cin is None
+                   else lib.lea_conv2d_kernel_name_cin(b, cin, cout, h, w))
 
 
-def pack_conv2d_weight(w: torch.Tensor) -> torch.Tensor:
-    """[cout, cin, 3, 3] fp32 device weight -> packed layout of lea_conv2d_bnrelu."""
+def _conv2d_weight(w):
+    """A [cout, cin, 3, 3] f32 device weight, contiguous, with its cout and cin."""
     _require_cuda(w)
     w = w.detach().contiguous()
     if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
         raise ValueError(f"expected a [cout, cin, 3, 3] weight, got {tuple(w.shape)}")
-    cout, cin = w.shape[:2]
+    return w, w.shape[0], w.shape[1]
+
+
+def pack_conv2d_weight(w: torch.Tensor) -> torch.Tensor:
+    """[cout, cin, 3, 3] fp32 device weight -> packed layout of lea_conv2d_bnrelu."""
+    w, cout, cin = _conv2d_weight(w)
     n = _lib.load().lea_conv2d_packed_floats(cout, cin)
     packed = torch.empty(n, device=w.device, dtype=torch.float32)
-    check(_lib.load().lea_conv2d_pack_weights(w.data_ptr(), packed.data_ptr(), cout, cin, _stream()),
-          "lea_conv2d_pack_weights")
+    _launch("lea_conv2d_pack_weights", w.data_ptr(), packed.data_ptr(), cout, cin)
     return packed
 
 
@@ -320,19 +448,13 @@ def conv2d_bnrelu(x: torch.Tensor, packed: torch.Tensor, cout: int,
     if d != 1:
         raise ValueError("conv2d_bnrelu takes [B, C, 1, H, W] views")
     xbs = _check_volume_view(x, "x")
-    out, ybs = _conv_out(x.shape, cout, (1, h, w), out, accumulate, x.device, x.dtype)
+    out, ybs = _conv_out(b, cout, (1, h, w), out, accumulate, x.device)
     rptr, rbs = _residual(out, accumulate, residual, ybs)
-    flags = (LEA_RELU if relu else 0) | (LEA_RESIDUAL if rptr is not None else 0)
-    rec = None if _probe is None else _probe_launch(
-        conv2d_kernel_name(b, cout, h, w, cin), 2.0 * b * h * w * cout * cin * 9,
-        4.0 * b * h * w * (cin + cout * (2 if rptr is not None else 1)) + 36.0 * cout * cin)
-    check(_lib.load().lea_conv2d_bnrelu(
-        x.data_ptr(), xbs, packed.data_ptr(),
-        scale.data_ptr() if scale is not None else None,
-        shift.data_ptr() if shift is not None else None,
-        rptr, rbs, out.data_ptr(), ybs, b, cin, cout, h, w, flags, LEA_F32, _stream()),
-        "lea_conv2d_bnrelu")
-    _probe_end(rec)
+    _launch("lea_conv2d_bnrelu", x.data_ptr(), xbs, packed.data_ptr(), _ptr(scale), _ptr(shift), rptr, rbs,
+            out.data_ptr(), ybs, b, cin, cout, h, w, _flags(relu, rptr is not None), LEA_F32,
+            probe=lambda: _op_record(
+                conv2d_kernel_name(b, cout, h, w, cin), 2.0 * b * h * w * cout * cin * 9,
+                4.0 * b * h * w * (cin + cout * (2 if rptr is not None else 1)) + 36.0 * cout * cin))
     return out
 
 
@@ -352,23 +474,17 @@ def conv2d_bnrelu_pair(x: torch.Tensor, packed: torch.Tensor, c1: int, cout: int
     if tuple(out1.shape) != (b, c1, 1, h, w) or tuple(out2.shape) != (b, cout - c1, 1, h, w):
         raise ValueError(f"conv2d_bnrelu_pair: outputs {tuple(out1.shape)} / {tuple(out2.shape)}")
     y1bs, y2bs = _check_volume_view(out1, "out1"), _check_volume_view(out2, "out2")
-    rptr, rbs = None, 0
+    rbs = 0
     if residual is not None:
         if tuple(residual.shape) != tuple(out1.shape):
             raise ValueError(f"conv2d_bnrelu_pair: residual {tuple(residual.shape)}")
         rbs = _check_volume_view(residual, "residual")
-        rptr = residual.data_ptr()
-    flags = (LEA_RELU if relu else 0) | (LEA_RESIDUAL if rptr is not None else 0)
-    rec = None if _probe is None else _probe_launch(
-        conv2d_kernel_name(b, cout, h, w, cin), 2.0 * b * h * w * cout * cin * 9,
-        4.0 * b * h * w * (cin + cout + (c1 if rptr is not None else 0)) + 36.0 * cout * cin)
-    check(_lib.load().lea_conv2d_bnrelu_pair(
-        x.data_ptr(), xbs, packed.data_ptr(),
-        scale.data_ptr() if scale is not None else None,
-        shift.data_ptr() if shift is not None else None,
-        rptr, rbs, out1.data_ptr(), y1bs, out2.data_ptr(), y2bs, b, cin, cout, c1, h, w, flags, _stream()),
-        "lea_conv2d_bnrelu_pair")
-    _probe_end(rec)
+    _launch("lea_conv2d_bnrelu_pair", x.data_ptr(), xbs, packed.data_ptr(), _ptr(scale), _ptr(shift),
+            _ptr(residual), rbs, out1.data_ptr(), y1bs, out2.data_ptr(), y2bs, b, cin, cout, c1, h, w,
+            _flags(relu, residual is not None),
+            probe=lambda: _op_record(
+                conv2d_kernel_name(b, cout, h, w, cin), 2.0 * b * h * w * cout * cin * 9,
+                4.0 * b * h * w * (cin + cout + (c1 if residual is not None else 0)) + 36.0 * cout * cin))
 
 
 def feature_stem(x: torch.Tensor, w0: torch.Tensor, scale0, shift0, w1: torch.Tensor, scale1, shift1,
@@ -398,21 +514,18 @@ def feature_stem(x: torch.Tensor, w0: torch.Tensor, scale0, shift0, w1: torch.Te
         out = torch.empty((nb, c1 // 8, 1, ho, wo, 8), device=x.device, dtype=torch.bfloat16)
     else:
         out = torch.empty((nb, c1, 1, ho, wo), device=x.device, dtype=torch.float32)
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
     if len(srcs) == 2 and b == 1:
         # one image per source: one launch whose batch stride is the distance between them
         srcs, b, xbs = [x], 2, (x2.data_ptr() - x.data_ptr()) // x.element_size()
     else:
         xbs = x.stride(0)
-    rec = None if _probe is None else _probe_launch(
-        "feature_stem_kernel", 2.0 * nb * ho * wo * (9 * 9 * cin * c0 + 9 * c0 * c1),
-        4.0 * nb * cin * hi * wi + out.numel() * out.element_size(), 0.0)
-    for i, src in enumerate(srcs):
-        check(_lib.load().lea_feature_stem_bnrelu(
-            src.data_ptr(), xbs, w0.data_ptr(), ptr(scale0), ptr(shift0), w1.data_ptr(),
-            ptr(scale1), ptr(shift1), out[i * b:].data_ptr(), out.stride(0), b, cin, c0, c1, hi, wi,
-            _lib.LEA_BF16 if c8 else LEA_F32, _stream()), "lea_feature_stem_bnrelu")
-    _probe_end(rec)
+    with _timed(lambda: _op_record(
+            "feature_stem_kernel", 2.0 * nb * ho * wo * (9 * 9 * cin * c0 + 9 * c0 * c1),
+            4.0 * nb * cin * hi * wi + out.numel() * out.element_size(), 0.0)):
+        for i, src in enumerate(srcs):
+            _launch("lea_feature_stem_bnrelu", src.data_ptr(), xbs, w0.data_ptr(), _ptr(scale0), _ptr(shift0),
+                    w1.data_ptr(), _ptr(scale1), _ptr(shift1), out[i * b:].data_ptr(), out.stride(0), b, cin, c0,
+                    c1, hi, wi, LEA_BF16 if c8 else LEA_F32)
     return out
 
 
@@ -430,13 +543,10 @@ def conv2d_s3_bnrelu(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor | Non
     xbs = _check_volume_view(x, "x")
     out = torch.empty((b, cout, 1, (hi - 1) // 3 + 1, (wi - 1) // 3 + 1), device=x.device,
                       dtype=x.dtype)
-    rec = None if _probe is None else _probe_launch(
-        "conv2d_s3_kernel", 2.0 * out.numel() * cin * 9, 4.0 * (x.numel() + out.numel()), 0.0)
-    check(_lib.load().lea_conv2d_s3_bnrelu(
-        x.data_ptr(), xbs, w.data_ptr(), scale.data_ptr() if scale is not None else None,
-        shift.data_ptr() if shift is not None else None, out.data_ptr(), out.stride(0), b, cin,
-        cout, hi, wi, LEA_RELU if relu else 0, LEA_F32, _stream()), "lea_conv2d_s3_bnrelu")
-    _probe_end(rec)
+    _launch("lea_conv2d_s3_bnrelu", x.data_ptr(), xbs, w.data_ptr(), _ptr(scale), _ptr(shift), out.data_ptr(),
+            out.stride(0), b, cin, cout, hi, wi, _flags(relu), LEA_F32,
+            probe=lambda: _op_record("conv2d_s3_kernel", 2.0 * out.numel() * cin * 9,
+                                     4.0 * (x.numel() + out.numel()), 0.0))
     return out
 
 
@@ -450,19 +560,10 @@ def resample_trilinear(x: torch.Tensor, size, align_corners: bool = True,
     b, c, di, hi, wi = x.shape
     do, ho, wo = (int(s) for s in size)
     xbs = _check_volume_view(x, "x")
-    if out is None:
-        out = torch.empty((b, c, do, ho, wo), device=x.device, dtype=x.dtype)
-    if tuple(out.shape) != (b, c, do, ho, wo):
-        raise ValueError(f"out shape {tuple(out.shape)} != {(b, c, do, ho, wo)}")
-    ybs = _check_volume_view(out, "out")
-    rec = None if _probe is None else _probe_launch(
-        "resample3d_f32", 0.0, 4.0 * b * c * (di * hi * wi + do * ho * wo))
-    check(_lib.load().lea_resample3d_trilinear(
-        x.data_ptr(), xbs, out.data_ptr(), ybs, b, c, di, hi, wi, do, ho, wo,
-        1 if align_corners else 0, scale.data_ptr() if scale is not None else None,
-        shift.data_ptr() if shift is not None else None, LEA_RELU if relu else 0, LEA_F32,
-        _stream()), "lea_resample3d_trilinear")
-    _probe_end(rec)
+    out, ybs = _out_view(out, (b, c, do, ho, wo), x.device)
+    _launch("lea_resample3d_trilinear", x.data_ptr(), xbs, out.data_ptr(), ybs, b, c, di, hi, wi, do, ho, wo,
+            1 if align_corners else 0, _ptr(scale), _ptr(shift), _flags(relu), LEA_F32,
+            probe=lambda: _op_record("resample3d_f32", 0.0, 4.0 * b * c * (di * hi * wi + do * ho * wo)))
     return out
 
 
@@ -476,12 +577,7 @@ def resample_down2_shape_supported(in_size, size) -> bool:
 def resample_down2_supported(x: torch.Tensor, size) -> bool:
     """Whether resample_trilinear_down2 takes x -> ``size``: an f32 NCDHW device tensor and a shape
     resample_down2_shape_supported accepts."""
-    if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 5:
-        return False
-    d, h, w = x.shape[2:]
-    if x.stride()[1:] != (d * h * w, h * w, w, 1):
-        return False
-    return resample_down2_shape_supported((d, h, w), size)
+    return _f32_volume(x, aligned=False) and resample_down2_shape_supported(x.shape[2:], size)
 
 
 def resample_trilinear_down2(x: torch.Tensor, size, out: torch.Tensor | None = None,
@@ -494,22 +590,25 @@ def resample_trilinear_down2(x: torch.Tensor, size, out: torch.Tensor | None = N
     b, c, di, hi, wi = x.shape
     do, ho, wo = (int(n) for n in size)
     xbs = _check_volume_view(x, "x")
-    if out is None:
-        out = torch.empty((b, c, do, ho, wo), device=x.device, dtype=x.dtype)
-    if down is None:
-        down = torch.empty((b, c, do // 2, ho // 2, wo // 2), device=x.device, dtype=x.dtype)
-    if tuple(out.shape) != (b, c, do, ho, wo) or tuple(down.shape) != (b, c, do // 2, ho // 2, wo // 2):
-        raise ValueError(f"out / down shapes {tuple(out.shape)} / {tuple(down.shape)} for {(b, c, do, ho, wo)}")
-    ybs, dbs = _check_volume_view(out, "out"), _check_volume_view(down, "down")
-    rec = None if _probe is None else _probe_launch(
-        "resample3d_sep_down2_f32", 0.0, 4.0 * (x.numel() + out.numel() + down.numel()))
-    check(_lib.load().lea_resample3d_trilinear_down2(
-        x.data_ptr(), xbs, out.data_ptr(), ybs, down.data_ptr(), dbs, b, c, di, hi, wi, do, ho, wo,
-        scale.data_ptr() if scale is not None else None,
-        shift.data_ptr() if shift is not None else None, LEA_RELU if relu else 0, LEA_F32,
-        _stream()), "lea_resample3d_trilinear_down2")
-    _probe_end(rec)
+    out, ybs = _out_view(out, (b, c, do, ho, wo), x.device)
+    down, dbs = _out_view(down, (b, c, do // 2, ho // 2, wo // 2), x.device, name="down")
+    _launch("lea_resample3d_trilinear_down2", x.data_ptr(), xbs, out.data_ptr(), ybs, down.data_ptr(), dbs, b, c,
+            di, hi, wi, do, ho, wo, _ptr(scale), _ptr(shift), _flags(relu), LEA_F32,
+            probe=lambda: _op_record("resample3d_sep_down2_f32", 0.0,
+                                     4.0 * (x.numel() + out.numel() + down.numel())))
     return out, down
+
+
+def _tapsum(q, qbs, cout, in_size, size, scale, shift, relu, dtype, probe):
+    """lea_tapsum_upsample of q (either layout, ``dtype`` LEA_F32 / LEA_BF16) -> f32 NCDHW."""
+    b, (di, hi, wi) = q.shape[0], in_size
+    do, ho, wo = (int(s) for s in size)
+    out = torch.empty((b, cout, do, ho, wo), device=q.device, dtype=torch.float32)
+    ws = torch.empty(_lib.load().lea_tapsum_workspace_bytes(b, cout, hi, wi, do) // 4, device=q.device,
+                     dtype=torch.float32)
+    _launch("lea_tapsum_upsample", q.data_ptr(), qbs, out.data_ptr(), out.stride(0), b, cout, di, hi, wi, do, ho,
+            wo, _ptr(scale), _ptr(shift), _flags(relu), ws.data_ptr(), dtype, probe=lambda: probe(out))
+    return out
 
 
 def tapsum_upsample(q: torch.Tensor, cout: int, size, scale: torch.Tensor | None = None,
@@ -520,39 +619,18 @@ def tapsum_upsample(q: torch.Tensor, cout: int, size, scale: torch.Tensor | None
     b, c27, di, hi, wi = q.shape
     if c27 != 27 * cout:
         raise ValueError(f"q has {c27} channels, expected 27*{cout}")
-    qbs = _check_volume_view(q, "q")
-    do, ho, wo = (int(s) for s in size)
-    out = torch.empty((b, cout, do, ho, wo), device=q.device, dtype=q.dtype)
-    lib = _lib.load()
-    ws = torch.empty(lib.lea_tapsum_workspace_bytes(b, cout, hi, wi, do) // 4, device=q.device,
-                     dtype=torch.float32)
-    rec = None if _probe is None else _probe_launch(
-        "tapsum_f32", 0.0, 4.0 * (q.shape[0] * q.shape[1] * di * hi * wi + out.numel()))
-    check(lib.lea_tapsum_upsample(
-        q.data_ptr(), qbs, out.data_ptr(), out.stride(0), b, cout, di, hi, wi, do, ho, wo,
-        scale.data_ptr() if scale is not None else None,
-        shift.data_ptr() if shift is not None else None, LEA_RELU if relu else 0,
-        ws.data_ptr(), LEA_F32, _stream()), "lea_tapsum_upsample")
-    _probe_end(rec)
-    return out
+    return _tapsum(q, _check_volume_view(q, "q"), cout, (di, hi, wi), size, scale, shift, relu, LEA_F32,
+                   lambda out: _op_record("tapsum_f32", 0.0, 4.0 * (b * c27 * di * hi * wi + out.numel())))
 
 
 def disparity_regression(cost: torch.Tensor, maxdisp: int, fast_exp: bool = False) -> torch.Tensor:
     """Disp + DisparityRegression (build_model_2d.py:52-57, 33-42): [B,1,D3,H3,W3] -> [B,3H3,3W3].
     ``fast_exp``: hardware exp (the bf16 path)."""
-    _require_cuda(cost)
-    if cost.dim() != 5 or cost.shape[1] != 1:
-        raise ValueError("cost must be [B, 1, D3, H3, W3]")
-    cost = cost.contiguous()
-    b, _, d3, h3, w3 = cost.shape
+    cost, b, d3, h3, w3 = _head_cost(cost)
     disp = torch.empty((b, 3 * h3, 3 * w3), device=cost.device, dtype=torch.float32)
-    rec = None if _probe is None else _probe_launch(
-        "disparity_regression", 0.0, 4.0 * (cost.numel() + disp.numel()))
-    check(_lib.load().lea_disparity_regression(cost.data_ptr(), disp.data_ptr(), b, d3, h3, w3,
-                                               maxdisp, _lib.LEA_BF16 if fast_exp else LEA_F32,
-                                               _stream()),
-          "lea_disparity_regression")
-    _probe_end(rec)
+    _launch("lea_disparity_regression", cost.data_ptr(), disp.data_ptr(), b, d3, h3, w3, maxdisp,
+            LEA_BF16 if fast_exp else LEA_F32,
+            probe=lambda: _op_record("disparity_regression", 0.0, 4.0 * (cost.numel() + disp.numel())))
     return disp
 
 
@@ -584,23 +662,17 @@ def disparity_regression_stats(cost: torch.Tensor, maxdisp: int, radius: int = 4
     ``lea_disparity_regression_stats`` (include/leastereo_hip.h) from the same launch:
     [B,1,D3,H3,W3] -> DisparityStats of [B,3H3,3W3].  ``disp`` is ``disparity_regression``'s
     bit for bit at the configured depths.  ``maxdisp`` must be 3 * D3."""
-    _require_cuda(cost)
-    if cost.dim() != 5 or cost.shape[1] != 1:
-        raise ValueError("cost must be [B, 1, D3, H3, W3]")
+    cost, b, d3, h3, w3 = _head_cost(cost)
     if not (entropy or peak or local):
         raise ValueError("disparity_regression_stats: ask for at least one of entropy, peak, local "
                          "(disparity_regression gives the disparity alone)")
-    cost = cost.contiguous()
-    b, _, d3, h3, w3 = cost.shape
     # one allocation per output: a hole (an output not asked for) is a null pointer
     outs = [torch.empty((b, 3 * h3, 3 * w3), device=cost.device, dtype=torch.float32) if want else None
             for want in (True, entropy, peak, local)]
-    rec = None if _probe is None else _probe_launch(
-        "disparity_regression_stats", 0.0, 4.0 * (cost.numel() + sum(o.numel() for o in outs if o is not None)))
-    check(_lib.load().lea_disparity_regression_stats(
-        cost.data_ptr(), *(None if o is None else o.data_ptr() for o in outs), b, d3, h3, w3, maxdisp,
-        radius, _lib.LEA_BF16 if fast_exp else LEA_F32, _stream()), "lea_disparity_regression_stats")
-    _probe_end(rec)
+    _launch("lea_disparity_regression_stats", cost.data_ptr(), *map(_ptr, outs), b, d3, h3, w3, maxdisp, radius,
+            LEA_BF16 if fast_exp else LEA_F32,
+            probe=lambda: _op_record("disparity_regression_stats", 0.0,
+                                     4.0 * (cost.numel() + sum(o.numel() for o in outs if o is not None))))
     return DisparityStats(*outs, maxdisp)
 
 
@@ -622,18 +694,11 @@ def disparity_regression_right(cost: torch.Tensor, maxdisp: int, fast_exp: bool 
     (``lea_disparity_regression_right``, include/leastereo_hip.h): the up-sampled cost read
     along its diagonals, right pixel xr at disparity od being left pixel xr + od, soft-argmin
     over the candidates in view.  [B,1,D3,H3,W3] -> [B,3H3,3W3]; ``maxdisp`` must be 3 * D3."""
-    _require_cuda(cost)
-    if cost.dim() != 5 or cost.shape[1] != 1:
-        raise ValueError("cost must be [B, 1, D3, H3, W3]")
-    cost = cost.contiguous()
-    b, _, d3, h3, w3 = cost.shape
+    cost, b, d3, h3, w3 = _head_cost(cost)
     out = torch.empty((b, 3 * h3, 3 * w3), device=cost.device, dtype=torch.float32)
-    rec = None if _probe is None else _probe_launch(
-        "disparity_regression_right", 0.0, 4.0 * (cost.numel() + out.numel()))
-    check(_lib.load().lea_disparity_regression_right(
-        cost.data_ptr(), out.data_ptr(), b, d3, h3, w3, maxdisp, _lib.LEA_BF16 if fast_exp else LEA_F32,
-        _stream()), "lea_disparity_regression_right")
-    _probe_end(rec)
+    _launch("lea_disparity_regression_right", cost.data_ptr(), out.data_ptr(), b, d3, h3, w3, maxdisp,
+            LEA_BF16 if fast_exp else LEA_F32,
+            probe=lambda: _op_record("disparity_regression_right", 0.0, 4.0 * (cost.numel() + out.numel())))
     return out
 
 
@@ -651,13 +716,10 @@ def lr_check(disp_left: torch.Tensor, disp_right: torch.Tensor, threshold: float
     b, h, w = dl.shape
     state = torch.empty((b, h, w), device=dl.device, dtype=torch.uint8) if want_state else None
     filled = torch.empty((b, h, w), device=dl.device, dtype=torch.float32) if want_filled else None
-    rec = None if _probe is None else _probe_launch(
-        "disparity_lr_check", 0.0, dl.numel() * (8.0 + (1.0 if want_state else 0.0) + (16.0 if want_filled else 0.0)))
-    check(_lib.load().lea_disparity_lr_check(
-        dl.data_ptr(), dr.data_ptr(), None if state is None else state.data_ptr(),
-        None if filled is None else filled.data_ptr(), b, h, w, float(threshold), _stream()),
-        "lea_disparity_lr_check")
-    _probe_end(rec)
+    _launch("lea_disparity_lr_check", dl.data_ptr(), dr.data_ptr(), _ptr(state), _ptr(filled), b, h, w,
+            float(threshold),
+            probe=lambda: _op_record("disparity_lr_check", 0.0, dl.numel() * (
+                8.0 + (1.0 if want_state else 0.0) + (16.0 if want_filled else 0.0))))
     return DisparityLR(disp_left, disp_right, state, filled)
 
 
@@ -685,10 +747,8 @@ def median_blur5(x: torch.Tensor, iterations: int = 1) -> torch.Tensor:
     x3, xbs = _plane_view(x3, "x")
     b, h, w = x3.shape
     y = torch.empty((b, h, w), device=x.device, dtype=torch.float32)
-    rec = None if _probe is None else _probe_launch("median5x5", 0.0, 8.0 * y.numel())
-    check(_lib.load().lea_median5x5_f32(x3.data_ptr(), xbs, y.data_ptr(), h * w, b, h, w, int(iterations),
-                                        _stream()), "lea_median5x5_f32")
-    _probe_end(rec)
+    _launch("lea_median5x5_f32", x3.data_ptr(), xbs, y.data_ptr(), h * w, b, h, w, int(iterations),
+            probe=lambda: _op_record("median5x5", 0.0, 8.0 * y.numel()))
     return y.squeeze(0) if x.dim() == 2 else y
 
 
@@ -709,13 +769,10 @@ def edge_loss_sums(pred: torch.Tensor, target: torch.Tensor, tsmooth: torch.Tens
     device in the order of ``EDGE_LOSS_FIELDS``; nothing is read back."""
     (p, pbs), (t, tbs), (s, sbs) = _edge_maps(pred, target, tsmooth)
     b, h, w = p.shape
-    lib = _lib.load()
-    ws = torch.empty(lib.lea_edge_loss_workspace_bytes(b, h, w) // 8, device=p.device, dtype=torch.float64)
+    ws = torch.empty(_lib.load().lea_edge_loss_workspace_bytes(b, h, w) // 8, device=p.device, dtype=torch.float64)
     sums = torch.empty(4, device=p.device, dtype=torch.float64)
-    rec = None if _probe is None else _probe_launch("edge_loss", 0.0, 12.0 * p.numel())
-    check(lib.lea_edge_loss_f32(p.data_ptr(), pbs, t.data_ptr(), tbs, s.data_ptr(), sbs, b, h, w, float(maxdisp),
-                                sums.data_ptr(), ws.data_ptr(), _stream()), "lea_edge_loss_f32")
-    _probe_end(rec)
+    _launch("lea_edge_loss_f32", p.data_ptr(), pbs, t.data_ptr(), tbs, s.data_ptr(), sbs, b, h, w, float(maxdisp),
+            sums.data_ptr(), ws.data_ptr(), probe=lambda: _op_record("edge_loss", 0.0, 12.0 * p.numel()))
     return sums
 
 
@@ -725,18 +782,12 @@ def edge_loss_grad(pred: torch.Tensor, target: torch.Tensor, tsmooth: torch.Tens
     ``scales[0] * direct + scales[1] * edge``; ``sums`` is what ``edge_loss_sums`` returned
     for the same maps, ``scales`` two float32 on the device."""
     (p, pbs), (t, tbs), (s, sbs) = _edge_maps(pred, target, tsmooth)
-    _require_cuda(scales)
-    if not sums.is_cuda or sums.dtype != torch.float64 or sums.numel() != 4 or not sums.is_contiguous():
-        raise ValueError("sums: the contiguous float64 [4] device tensor of edge_loss_sums")
-    if scales.numel() != 2 or not scales.is_contiguous():
-        raise ValueError("scales: two contiguous float32 (g_direct, g_edge) on the device")
+    _sums_scales(sums, scales, "edge_loss_sums", "g_direct, g_edge")
     b, h, w = p.shape
     dpred = torch.empty((b, h, w), device=p.device, dtype=torch.float32)
-    rec = None if _probe is None else _probe_launch("edge_loss_grad", 0.0, 16.0 * p.numel())
-    check(_lib.load().lea_edge_loss_grad_f32(p.data_ptr(), pbs, t.data_ptr(), tbs, s.data_ptr(), sbs,
-                                             sums.data_ptr(), scales.data_ptr(), dpred.data_ptr(), h * w, b, h, w,
-                                             float(maxdisp), _stream()), "lea_edge_loss_grad_f32")
-    _probe_end(rec)
+    _launch("lea_edge_loss_grad_f32", p.data_ptr(), pbs, t.data_ptr(), tbs, s.data_ptr(), sbs, sums.data_ptr(),
+            scales.data_ptr(), dpred.data_ptr(), h * w, b, h, w, float(maxdisp),
+            probe=lambda: _op_record("edge_loss_grad", 0.0, 16.0 * p.numel()))
     return dpred
 
 
@@ -766,13 +817,9 @@ def _photo_maps(left, right, disp, exclude):
         raise ValueError("photometric: H >= 3 and W >= 3 are needed")
     if tuple(disp.shape) != (b, h, w):
         raise ValueError(f"disp must be [B, H, W] = {(b, h, w)}, got {tuple(disp.shape)}")
-    ex = (None, 0)
-    if exclude is not None:
-        if not exclude.is_cuda or tuple(exclude.shape) != (b, h, w) or exclude.dtype not in (torch.uint8, torch.bool):
-            raise ValueError("exclude must be a [B, H, W] uint8 or bool tensor on the device")
-        e = exclude.view(torch.uint8) if exclude.dtype == torch.bool else exclude
-        ex = _plane_view(e, "exclude")
-    return _image_view(left), _image_view(right), _plane_view(disp, "disp"), ex
+    e = _exclude_u8(exclude, (b, h, w))
+    return (_image_view(left), _image_view(right), _plane_view(disp, "disp"),
+            (None, 0) if e is None else _plane_view(e, "exclude"))
 
 
 def photometric_sums(left: torch.Tensor, right: torch.Tensor, disp: torch.Tensor, exclude: torch.Tensor = None,
@@ -783,18 +830,14 @@ def photometric_sums(left: torch.Tensor, right: torch.Tensor, disp: torch.Tensor
     or ``want_err`` returns ``(sums, warped, err)``, the map not asked for being None."""
     (l, lbs), (r, rbs), (d, dbs), (e, ebs) = _photo_maps(left, right, disp, exclude)
     b, c, h, w = l.shape
-    lib = _lib.load()
-    ws = torch.empty(lib.lea_photometric_workspace_bytes(b, h, w) // 8, device=l.device, dtype=torch.float64)
+    ws = torch.empty(_lib.load().lea_photometric_workspace_bytes(b, h, w) // 8, device=l.device,
+                     dtype=torch.float64)
     sums = torch.empty(4, device=l.device, dtype=torch.float64)
     warped = torch.empty((b, c, h, w), device=l.device, dtype=torch.float32) if want_warped else None
     err = torch.empty((b, h, w), device=l.device, dtype=torch.float32) if want_err else None
-    rec = None if _probe is None else _probe_launch("photometric", 0.0, 4.0 * (l.numel() + r.numel() + d.numel()))
-    check(lib.lea_photometric_f32(l.data_ptr(), lbs, r.data_ptr(), rbs, d.data_ptr(), dbs,
-                                  None if e is None else e.data_ptr(), ebs, b, c, h, w, float(alpha), float(c1),
-                                  float(c2), sums.data_ptr(), ws.data_ptr(),
-                                  None if warped is None else warped.data_ptr(),
-                                  None if err is None else err.data_ptr(), _stream()), "lea_photometric_f32")
-    _probe_end(rec)
+    _launch("lea_photometric_f32", l.data_ptr(), lbs, r.data_ptr(), rbs, d.data_ptr(), dbs, _ptr(e), ebs, b, c, h,
+            w, float(alpha), float(c1), float(c2), sums.data_ptr(), ws.data_ptr(), _ptr(warped), _ptr(err),
+            probe=lambda: _op_record("photometric", 0.0, 4.0 * (l.numel() + r.numel() + d.numel())))
     return (sums, warped, err) if (want_warped or want_err) else sums
 
 
@@ -805,20 +848,12 @@ def photometric_grad(left: torch.Tensor, right: torch.Tensor, disp: torch.Tensor
     ``scales[0] * l1 + scales[1] * dssim`` (the two means); ``sums`` is what
     ``photometric_sums`` returned for the same inputs, ``scales`` two float32 on the device."""
     (l, lbs), (r, rbs), (d, dbs), (e, ebs) = _photo_maps(left, right, disp, exclude)
-    _require_cuda(scales)
-    if not sums.is_cuda or sums.dtype != torch.float64 or sums.numel() != 4 or not sums.is_contiguous():
-        raise ValueError("sums: the contiguous float64 [4] device tensor of photometric_sums")
-    if scales.numel() != 2 or not scales.is_contiguous():
-        raise ValueError("scales: two contiguous float32 (g_l1, g_dssim) on the device")
+    _sums_scales(sums, scales, "photometric_sums", "g_l1, g_dssim")
     b, c, h, w = l.shape
     ddisp = torch.empty((b, h, w), device=l.device, dtype=torch.float32)
-    rec = None if _probe is None else _probe_launch("photometric_grad", 0.0,
-                                                    4.0 * (l.numel() + r.numel() + 2 * d.numel()))
-    check(_lib.load().lea_photometric_grad_f32(l.data_ptr(), lbs, r.data_ptr(), rbs, d.data_ptr(), dbs,
-                                               None if e is None else e.data_ptr(), ebs, b, c, h, w, float(c1),
-                                               float(c2), sums.data_ptr(), scales.data_ptr(), ddisp.data_ptr(),
-                                               h * w, _stream()), "lea_photometric_grad_f32")
-    _probe_end(rec)
+    _launch("lea_photometric_grad_f32", l.data_ptr(), lbs, r.data_ptr(), rbs, d.data_ptr(), dbs, _ptr(e), ebs, b,
+            c, h, w, float(c1), float(c2), sums.data_ptr(), scales.data_ptr(), ddisp.data_ptr(), h * w,
+            probe=lambda: _op_record("photometric_grad", 0.0, 4.0 * (l.numel() + r.numel() + 2 * d.numel())))
     return ddisp
 
 
@@ -856,29 +891,21 @@ def fgs_refine(guide: torch.Tensor, disp: torch.Tensor, conf: torch.Tensor = Non
         raise ValueError(f"disp must be [B, H, W] = {(b, h, w)}, got {tuple(disp.shape)}")
     if conf is not None and tuple(conf.shape) != (b, h, w):
         raise ValueError(f"conf must be [B, H, W] = {(b, h, w)}, got {tuple(conf.shape)}")
-    e = None
-    if exclude is not None:
-        if not exclude.is_cuda or tuple(exclude.shape) != (b, h, w) or exclude.dtype not in (torch.uint8, torch.bool):
-            raise ValueError("exclude must be a [B, H, W] uint8 or bool tensor on the device")
-        e = (exclude.view(torch.uint8) if exclude.dtype == torch.bool else exclude).contiguous()
+    e = _contiguous(_exclude_u8(exclude, (b, h, w)))
     if not (lam > 0 and math.isfinite(lam) and sigma > 0 and math.isfinite(sigma)):
         raise ValueError(f"fgs_refine: lam {lam} and sigma {sigma} must be finite numbers > 0")
     if not 1 <= int(iterations) <= 8 or int(iterations) != iterations:
         raise ValueError(f"fgs_refine: iterations {iterations} (1..8)")
     g, gbs = _image_view(guide)
     d = disp.contiguous()
-    cf = None if conf is None else conf.contiguous()
-    lib = _lib.load()
-    ws = torch.empty(lib.lea_disparity_refine_workspace_bytes(b, h, w) // 4, device=d.device, dtype=torch.float32)
+    cf = _contiguous(conf)
+    ws = torch.empty(_lib.load().lea_disparity_refine_workspace_bytes(b, h, w) // 4, device=d.device,
+                     dtype=torch.float32)
     refined = torch.empty((b, h, w), device=d.device, dtype=torch.float32)
     support = torch.empty_like(refined) if return_support else None
-    rec = None if _probe is None else _probe_launch("disparity_refine", 0.0, 4.0 * d.numel() * (c + 3 + 22 * iterations))
-    check(lib.lea_disparity_refine_f32(g.data_ptr(), gbs, d.data_ptr(), None if cf is None else cf.data_ptr(),
-                                       None if e is None else e.data_ptr(), b, c, h, w, float(lam), float(sigma),
-                                       int(iterations), ws.data_ptr(), refined.data_ptr(),
-                                       None if support is None else support.data_ptr(), _stream()),
-          "lea_disparity_refine_f32")
-    _probe_end(rec)
+    _launch("lea_disparity_refine_f32", g.data_ptr(), gbs, d.data_ptr(), _ptr(cf), _ptr(e), b, c, h, w, float(lam),
+            float(sigma), int(iterations), ws.data_ptr(), refined.data_ptr(), _ptr(support),
+            probe=lambda: _op_record("disparity_refine", 0.0, 4.0 * d.numel() * (c + 3 + 22 * iterations)))
     return (refined, support) if return_support else refined
 
 
@@ -896,6 +923,15 @@ DisparitySpeckle.__doc__ = """What ``speckle_filter`` returns, all [B, H, W] (``
 None differentiable."""
 
 
+def _disparity_map(who, disp):
+    """The [B, H, W] or [H, W] float32 device disparity of the post-processing calls; its shape."""
+    if not isinstance(disp, torch.Tensor) or disp.dim() not in (2, 3):
+        raise ValueError(f"{who}: disp must be [B, H, W] or [H, W], got "
+                         f"{tuple(disp.shape) if isinstance(disp, torch.Tensor) else type(disp)}")
+    _require_cuda(disp)
+    return tuple(disp.shape)
+
+
 def speckle_filter(disp: torch.Tensor, exclude: torch.Tensor = None, max_size: int = SPECKLE_MAX_SIZE,
                    max_diff: float = SPECKLE_MAX_DIFF, fill: float = 0.0, want_labels: bool = False,
                    want_size: bool = True, want_filtered: bool = True) -> DisparitySpeckle:
@@ -908,46 +944,31 @@ def speckle_filter(disp: torch.Tensor, exclude: torch.Tensor = None, max_size: i
     defaults (200 px, 1.0 px) are the middle of OpenCV's recommended 50-200 window and 1-2
     range and are **untuned**: there is no trained checkpoint and no real pair here to tune
     them on.  Four launches on the current stream; nothing is read back."""
-    if not isinstance(disp, torch.Tensor) or disp.dim() not in (2, 3):
-        raise ValueError(f"speckle_filter: disp must be [B, H, W] or [H, W], got "
-                         f"{tuple(disp.shape) if isinstance(disp, torch.Tensor) else type(disp)}")
-    _require_cuda(disp)
-    shape = tuple(disp.shape)
-    if exclude is not None:
-        if (not isinstance(exclude, torch.Tensor) or not exclude.is_cuda or tuple(exclude.shape) != shape
-                or exclude.dtype not in (torch.uint8, torch.bool)):
-            raise ValueError(f"speckle_filter: exclude must be a {shape} uint8 or bool tensor on the device")
-    if isinstance(max_diff, bool) or not isinstance(max_diff, (int, float)) or not (
-            max_diff >= 0 and math.isfinite(max_diff)):
-        raise ValueError(f"speckle_filter: max_diff {max_diff} must be a finite number >= 0")
-    if isinstance(max_size, bool) or not isinstance(max_size, int) or not 0 <= max_size <= 2 ** 31 - 1:
-        raise ValueError(f"speckle_filter: max_size {max_size} must be an integer in 0 .. 2^31 - 1")
-    if not isinstance(fill, (int, float)):
-        raise ValueError(f"speckle_filter: fill {fill} must be a number")
+    who = "speckle_filter"
+    shape = _disparity_map(who, disp)
+    e = _exclude_u8(exclude, shape, who)
+    _number(who, "max_diff", max_diff, "a finite number >= 0", lo=0, finite=True)
+    _number(who, "max_size", max_size, "an integer in 0 .. 2^31 - 1", lo=0, hi=2 ** 31 - 1, integer=True)
+    _number(who, "fill", fill, "a number", bools=True)
     if 0 in shape:
         raise ValueError(f"speckle_filter: empty map {shape}")
     if shape[-2] * shape[-1] >= 2 ** 31:
         raise ValueError(f"speckle_filter: H * W = {shape[-2] * shape[-1]} is not below 2^31")
     d = disp.contiguous()
-    e = None
-    if exclude is not None:
-        e = (exclude.view(torch.uint8) if exclude.dtype == torch.bool else exclude).contiguous()
+    e = _contiguous(e)
     b = shape[0] if len(shape) == 3 else 1
     h, w = shape[-2:]
-    lib = _lib.load()
-    ws = torch.empty(lib.lea_disparity_speckle_workspace_bytes(b, h, w) // 4, device=d.device, dtype=torch.int32)
+    ws = torch.empty(_lib.load().lea_disparity_speckle_workspace_bytes(b, h, w) // 4, device=d.device,
+                     dtype=torch.int32)
     state = torch.empty(shape, device=d.device, dtype=torch.uint8)
     size = torch.empty(shape, device=d.device, dtype=torch.int32) if want_size else None
     labels = torch.empty(shape, device=d.device, dtype=torch.int32) if want_labels else None
     filtered = torch.empty(shape, device=d.device, dtype=torch.float32) if want_filtered else None
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    rec = None if _probe is None else _probe_launch(
-        "disparity_speckle", 0.0, d.numel() * (30.0 + (4.0 if want_size else 0.0) + (4.0 if want_labels else 0.0) +
-                                               (8.0 if want_filtered else 0.0)))
-    check(lib.lea_disparity_speckle_f32(d.data_ptr(), ptr(e), b, h, w, float(max_diff), int(max_size), float(fill),
-                                        ws.data_ptr(), ptr(labels), ptr(size), state.data_ptr(), ptr(filtered),
-                                        _stream()), "lea_disparity_speckle_f32")
-    _probe_end(rec)
+    _launch("lea_disparity_speckle_f32", d.data_ptr(), _ptr(e), b, h, w, float(max_diff), int(max_size),
+            float(fill), ws.data_ptr(), _ptr(labels), _ptr(size), state.data_ptr(), _ptr(filtered),
+            probe=lambda: _op_record("disparity_speckle", 0.0, d.numel() * (
+                30.0 + (4.0 if want_size else 0.0) + (4.0 if want_labels else 0.0) +
+                (8.0 if want_filtered else 0.0))))
     return DisparitySpeckle(disp, state, size, labels, filtered)
 
 
@@ -996,15 +1017,10 @@ class PointCloud(collections.namedtuple("PointCloud", "points valid count xyz rg
 def _as_q(Q, b: int, device) -> torch.Tensor:
     """Q as a float32 tensor on the device, [4, 4] or [b, 4, 4]; one that is that already is used in
     place (a captured call then replays with what it holds at the time)."""
-    if isinstance(Q, torch.Tensor):
-        q = Q
-    else:
-        q = torch.from_numpy(np.ascontiguousarray(np.asarray(Q, dtype=np.float64)).astype(np.float32))
-    if tuple(q.shape) not in ((4, 4), (b, 4, 4)):
-        raise ValueError(f"reproject: Q must be [4, 4] or [{b}, 4, 4], got {tuple(q.shape)}")
-    if not q.dtype.is_floating_point:
-        raise ValueError(f"reproject: Q must be a floating-point matrix, got {q.dtype}")
-    return q.to(device=device, dtype=torch.float32).contiguous()
+    shape = tuple(Q.shape) if isinstance(Q, torch.Tensor) else np.shape(Q)
+    if shape not in ((4, 4), (b, 4, 4)):
+        raise ValueError(f"reproject: Q must be [4, 4] or [{b}, 4, 4], got {shape}")
+    return _as_f32(Q, device, "reproject: Q must be a floating-point matrix")
 
 
 def reproject(disp: torch.Tensor, Q, image: torch.Tensor = None, exclude: torch.Tensor = None,
@@ -1024,11 +1040,8 @@ def reproject(disp: torch.Tensor, Q, image: torch.Tensor = None, exclude: torch.
     ``capacity``: rows per item of the compact arrays, H * W by default; the first ``capacity``
     points are kept.  Up to three launches on the current stream; nothing is read back, the
     number of points stays on the device (``PointCloud.to_host``)."""
-    if not isinstance(disp, torch.Tensor) or disp.dim() not in (2, 3):
-        raise ValueError(f"reproject: disp must be [B, H, W] or [H, W], got "
-                         f"{tuple(disp.shape) if isinstance(disp, torch.Tensor) else type(disp)}")
-    _require_cuda(disp)
-    shape = tuple(disp.shape)
+    who = "reproject"
+    shape = _disparity_map(who, disp)
     if 0 in shape:
         raise ValueError(f"reproject: empty map {shape}")
     batched = len(shape) == 3
@@ -1036,10 +1049,7 @@ def reproject(disp: torch.Tensor, Q, image: torch.Tensor = None, exclude: torch.
     h, w = shape[-2:]
     if b * h * w > 2 ** 31 - 1:
         raise ValueError(f"reproject: B * H * W = {b * h * w} is above 2^31 - 1")
-    if exclude is not None:
-        if (not isinstance(exclude, torch.Tensor) or not exclude.is_cuda or tuple(exclude.shape) != shape
-                or exclude.dtype not in (torch.uint8, torch.bool)):
-            raise ValueError(f"reproject: exclude must be a {shape} uint8 or bool tensor on the device")
+    e = _exclude_u8(exclude, shape, who)
     img = None
     if image is not None:
         if (not isinstance(image, torch.Tensor) or not image.is_cuda or image.dtype != torch.uint8
@@ -1047,26 +1057,21 @@ def reproject(disp: torch.Tensor, Q, image: torch.Tensor = None, exclude: torch.
             raise ValueError(f"reproject: image must be a uint8 {shape + ('3|4',)} tensor on the device")
         img = image.contiguous()
     for name, v in (("min_disp", min_disp), ("max_disp", max_disp), ("normal_max_diff", normal_max_diff)):
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or math.isnan(v):
-            raise ValueError(f"reproject: {name} {v} must be a number")
-    if normal_max_diff < 0:
-        raise ValueError(f"reproject: normal_max_diff {normal_max_diff} must be >= 0")
+        _number(who, name, v, "a number", lo=-math.inf)
+    _number(who, "normal_max_diff", normal_max_diff, ">= 0", lo=0)
     if capacity is None:
         capacity = h * w
-    if isinstance(capacity, bool) or not isinstance(capacity, int) or not 1 <= capacity <= 2 ** 31 - 1:
-        raise ValueError(f"reproject: capacity {capacity} must be an integer in 1 .. 2^31 - 1")
+    _number(who, "capacity", capacity, "an integer in 1 .. 2^31 - 1", lo=1, hi=2 ** 31 - 1, integer=True)
     if normals and not want_compact:
         raise ValueError("reproject: the normals are a compact output (want_compact=True)")
     if not (want_points or want_valid or want_compact):
         raise ValueError("reproject: nothing asked for")
     d = disp.contiguous()
-    e = None
-    if exclude is not None:
-        e = (exclude.view(torch.uint8) if exclude.dtype == torch.bool else exclude).contiguous()
+    e = _contiguous(e)
     q = _as_q(Q, b, d.device)
     dev = d.device
-    lib = _lib.load()
-    ws = torch.empty(lib.lea_disparity_pointcloud_workspace_bytes(b, h, w) // 4, device=dev, dtype=torch.int32)
+    ws = torch.empty(_lib.load().lea_disparity_pointcloud_workspace_bytes(b, h, w) // 4, device=dev,
+                     dtype=torch.int32)
     lead = (b,) if batched else ()
     new = lambda want, tail, dtype: torch.empty(lead + tail, device=dev, dtype=dtype) if want else None  # noqa: E731
     points = new(want_points, (h, w, 3), torch.float32)
@@ -1076,18 +1081,15 @@ def reproject(disp: torch.Tensor, Q, image: torch.Tensor = None, exclude: torch.
     rgb = new(want_compact and img is not None, (capacity, 3), torch.uint8)
     index = new(want_compact, (capacity,), torch.int32)
     nrm = new(want_compact and normals, (capacity, 3), torch.float32)
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    rec = None if _probe is None else _probe_launch(
-        "disparity_pointcloud", 0.0, d.numel() * ((8.0 if want_compact else 4.0) + (0.0 if e is None else 1.0) +
-                                                  (12.0 if want_points else 0.0) + (1.0 if want_valid else 0.0) +
-                                                  (16.0 if want_compact else 0.0) + (0.0 if rgb is None else 6.0) +
-                                                  (12.0 if nrm is not None else 0.0)))
-    check(lib.lea_disparity_pointcloud_f32(d.data_ptr(), ptr(e), ptr(img), 0 if img is None else img.shape[-1],
-                                           q.data_ptr(), 16 if q.dim() == 3 else 0, b, h, w, float(min_disp),
-                                           float(max_disp), float(normal_max_diff), int(capacity), ws.data_ptr(),
-                                           ptr(points), ptr(valid), ptr(count), ptr(xyz), ptr(rgb), ptr(index),
-                                           ptr(nrm), _stream()), "lea_disparity_pointcloud_f32")
-    _probe_end(rec)
+    _launch("lea_disparity_pointcloud_f32", d.data_ptr(), _ptr(e), _ptr(img), 0 if img is None else img.shape[-1],
+            q.data_ptr(), 16 if q.dim() == 3 else 0, b, h, w, float(min_disp), float(max_disp),
+            float(normal_max_diff), int(capacity), ws.data_ptr(), _ptr(points), _ptr(valid), _ptr(count), _ptr(xyz),
+            _ptr(rgb), _ptr(index), _ptr(nrm),
+            probe=lambda: _op_record("disparity_pointcloud", 0.0, d.numel() * (
+                (8.0 if want_compact else 4.0) + (0.0 if e is None else 1.0) +
+                (12.0 if want_points else 0.0) + (1.0 if want_valid else 0.0) +
+                (16.0 if want_compact else 0.0) + (0.0 if rgb is None else 6.0) +
+                (12.0 if nrm is not None else 0.0))))
     return PointCloud(points, valid, count, xyz, rgb, index, nrm)
 
 
@@ -1126,27 +1128,18 @@ def rectify_u8(left: torch.Tensor, right: torch.Tensor, calib=None, maps=None, s
     b, h, w, ps = left.shape
     if (calib is None) == (maps is None):
         raise ValueError("rectify_u8: exactly one of calib and maps must be given")
-    if isinstance(fill, bool) or not isinstance(fill, int) or not 0 <= fill <= 255:
-        raise ValueError(f"rectify_u8: fill {fill} must be an integer in 0 .. 255")
+    _number("rectify_u8", "fill", fill, "an integer in 0 .. 255", lo=0, hi=255, integer=True)
     dev = left.device
-
-    def as_f32(a, name):
-        if not isinstance(a, torch.Tensor):
-            a = torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64)).astype(np.float32))
-        if not a.dtype.is_floating_point:
-            raise ValueError(f"rectify_u8: {name} must be floating point, got {a.dtype}")
-        return a.to(device=dev, dtype=torch.float32).contiguous()
-
     c = m = None
     if calib is not None:
-        c = as_f32(calib, "calib")
+        c = _as_f32(calib, dev, "rectify_u8: calib must be floating point")
         if c.dim() == 2:
             c = c.unsqueeze(0)
         if c.dim() != 3 or tuple(c.shape[1:]) != (2, RECT_CALIB_FLOATS) or c.shape[0] not in (1, b):
             raise ValueError(f"rectify_u8: calib must be [1|{b}, 2, {RECT_CALIB_FLOATS}], got {tuple(c.shape)}")
         ho, wo = (h, w) if size is None else (int(size[0]), int(size[1]))
     else:
-        m = as_f32(maps, "maps")
+        m = _as_f32(maps, dev, "rectify_u8: maps must be floating point")
         if m.dim() == 4:
             m = m.unsqueeze(0)
         if m.dim() != 5 or tuple(m.shape[1:3]) != (2, 2) or m.shape[0] not in (1, b) or 0 in m.shape:
@@ -1156,20 +1149,17 @@ def rectify_u8(left: torch.Tensor, right: torch.Tensor, calib=None, maps=None, s
             raise ValueError(f"rectify_u8: size {tuple(size)} contradicts the maps' {(ho, wo)}")
     if not (1 <= ho <= 65535 and 1 <= wo <= 65535):
         raise ValueError(f"rectify_u8: output size {(ho, wo)} outside 1 .. 65535")
-    lib = _lib.load()
     out_l = torch.empty((b, ho, wo, ps), device=dev, dtype=torch.uint8)
     out_r = torch.empty_like(out_l)
     valid = torch.empty((b, 2, ho, wo), device=dev, dtype=torch.uint8) if want_valid else None
     mo = torch.empty((b, 2, 2, ho, wo), device=dev, dtype=torch.float32) if want_maps else None
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     n = 2.0 * b * ho * wo
-    rec = None if _probe is None else _probe_launch(
-        "rectify_pair", 50.0 * n, n * (2.0 * ps + (1.0 if want_valid else 0.0) + (8.0 if want_maps else 0.0) +
-                                       (8.0 if m is not None else 0.0)))
-    check(lib.lea_rectify_pair_u8(left.data_ptr(), right.data_ptr(), ps, b, h, w, ptr(c), 0 if c is None else c.shape[0],
-                                  ptr(m), 0 if m is None else m.shape[0], ho, wo, int(fill), out_l.data_ptr(),
-                                  out_r.data_ptr(), ptr(valid), ptr(mo), _stream()), "lea_rectify_pair_u8")
-    _probe_end(rec)
+    _launch("lea_rectify_pair_u8", left.data_ptr(), right.data_ptr(), ps, b, h, w, _ptr(c),
+            0 if c is None else c.shape[0], _ptr(m), 0 if m is None else m.shape[0], ho, wo, int(fill),
+            out_l.data_ptr(), out_r.data_ptr(), _ptr(valid), _ptr(mo),
+            probe=lambda: _op_record("rectify_pair", 50.0 * n, n * (
+                2.0 * ps + (1.0 if want_valid else 0.0) + (8.0 if want_maps else 0.0) +
+                (8.0 if m is not None else 0.0))))
     outs = (out_l, out_r, valid, mo)
     if not batched:
         outs = tuple(None if t is None else t[0] for t in outs)
@@ -1204,6 +1194,7 @@ def forward_warp(image: torch.Tensor, disp: torch.Tensor, scale=1.0, exclude: to
     ``exclude``: [B, H, W] uint8 or bool, or None (``DisparityLR.state`` /
     ``DisparitySpeckle.state`` go as they are).  One launch on the current stream; nothing is
     read back.  Returns ``WarpedView``."""
+    who = "forward_warp"
     _require_cuda(image, disp)
     if image.dtype != torch.float32 or disp.dtype != torch.float32:
         raise ValueError("forward_warp: image and disp must be float32")
@@ -1217,17 +1208,10 @@ def forward_warp(image: torch.Tensor, disp: torch.Tensor, scale=1.0, exclude: to
         raise ValueError(f"forward_warp: {c} channels, 1 .. 4 supported")
     if w > FORWARD_WARP_MAX_W:
         raise ValueError(f"forward_warp: width {w} is above the kernel's limit {FORWARD_WARP_MAX_W}")
-    if exclude is not None:
-        if (not isinstance(exclude, torch.Tensor) or not exclude.is_cuda or tuple(exclude.shape) != (b, h, w)
-                or exclude.dtype not in (torch.uint8, torch.bool)):
-            raise ValueError(f"forward_warp: exclude must be a {(b, h, w)} uint8 or bool tensor on the device")
-    if isinstance(max_diff, bool) or not isinstance(max_diff, (int, float)) or not (
-            max_diff >= 0 and math.isfinite(max_diff)):
-        raise ValueError(f"forward_warp: max_diff {max_diff} must be a finite number >= 0")
-    if isinstance(max_stretch, bool) or not isinstance(max_stretch, (int, float)) or not 1 <= max_stretch <= 64:
-        raise ValueError(f"forward_warp: max_stretch {max_stretch} must be in 1 .. 64")
-    if not isinstance(fill_value, (int, float)):
-        raise ValueError(f"forward_warp: fill_value {fill_value} must be a number")
+    e = _exclude_u8(exclude, (b, h, w), who)
+    _number(who, "max_diff", max_diff, "a finite number >= 0", lo=0, finite=True)
+    _number(who, "max_stretch", max_stretch, "in 1 .. 64", lo=1, hi=64)
+    _number(who, "fill_value", fill_value, "a number", bools=True)
     dev = image.device
     if isinstance(scale, torch.Tensor):
         if not scale.is_cuda or scale.dtype != torch.float32 or tuple(scale.shape) != (b,):
@@ -1237,49 +1221,25 @@ def forward_warp(image: torch.Tensor, disp: torch.Tensor, scale=1.0, exclude: to
         sc = torch.full((b,), float(scale), device=dev, dtype=torch.float32)
     else:
         raise ValueError(f"forward_warp: scale must be a number or a [{b}] float32 device tensor")
-    if image.stride()[1:] != (h * w, w, 1) or (b > 1 and image.stride(0) < c * h * w):
-        image = image.contiguous()
-    ibs = image.stride(0) if b > 1 else c * h * w
+    image, ibs = _image_view(image)
     d, dbs = _plane_view(disp, "disp")
-    e = None
-    if exclude is not None:
-        e = (exclude.view(torch.uint8) if exclude.dtype == torch.bool else exclude).contiguous()
+    e = _contiguous(e)
     out = torch.empty((b, c, h, w), device=dev, dtype=torch.float32)
     zview = torch.empty((b, h, w), device=dev, dtype=torch.float32) if want_zview else None
     state = torch.empty((b, h, w), device=dev, dtype=torch.uint8) if want_state else None
     source = torch.empty((b, h, w), device=dev, dtype=torch.float32) if want_source else None
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     n = float(b * h * w)
-    rec = None if _probe is None else _probe_launch(
-        "forward_warp", 20.0 * n, n * (4.0 * (2 * c + 1) + (1.0 if e is not None else 0.0) +
-                                       (4.0 if want_zview else 0.0) + (1.0 if want_state else 0.0) +
-                                       (4.0 if want_source else 0.0)))
-    check(_lib.load().lea_forward_warp_f32(image.data_ptr(), ibs, d.data_ptr(), dbs, ptr(e), sc.data_ptr(), b, c, h, w,
-                                           float(max_diff), float(max_stretch), 1 if fill else 0, float(fill_value),
-                                           out.data_ptr(), ptr(zview), ptr(state), ptr(source), _stream()),
-          "lea_forward_warp_f32")
-    _probe_end(rec)
+    _launch("lea_forward_warp_f32", image.data_ptr(), ibs, d.data_ptr(), dbs, _ptr(e), sc.data_ptr(), b, c, h, w,
+            float(max_diff), float(max_stretch), 1 if fill else 0, float(fill_value), out.data_ptr(), _ptr(zview),
+            _ptr(state), _ptr(source),
+            probe=lambda: _op_record("forward_warp", 20.0 * n, n * (
+                4.0 * (2 * c + 1) + (1.0 if e is not None else 0.0) + (4.0 if want_zview else 0.0) +
+                (1.0 if want_state else 0.0) + (4.0 if want_source else 0.0))))
     return WarpedView(out, zview, state, source)
 
 
 # ------------------------------------------------------------------ bf16 path (c8)
 # Activations: torch.bfloat16 [B, C/8, D, H, W, 8] ("c8": 8 channels per voxel word).
-
-def _require_c8(*ts):
-    for t in ts:
-        if t is not None and (not t.is_cuda or t.dtype != torch.bfloat16 or t.dim() != 6
-                              or t.shape[-1] != 8):
-            raise _lib.HipKernelError(
-                f"bf16 path needs [B, C/8, D, H, W, 8] bfloat16 ROCm tensors, got {t.dtype} "
-                f"{tuple(t.shape)} on {t.device}")
-
-
-def _check_c8_view(t: torch.Tensor, name: str):
-    b, cb, d, h, w, _ = t.shape
-    if t.stride()[1:] != (d * h * w * 8, h * w * 8, w * 8, 8, 1):
-        raise ValueError(f"{name}: c8 block slice with contiguous blocks required, strides {t.stride()}")
-    return t.stride(0)
-
 
 def c8_channels(t: torch.Tensor) -> int:
     return t.shape[1] * 8
@@ -1292,10 +1252,8 @@ def to_c8(x: torch.Tensor) -> torch.Tensor:
     b, c, d, h, w = x5.shape
     xbs = _check_volume_view(x5, "x")
     out = torch.empty((b, c // 8, d, h, w, 8), device=x.device, dtype=torch.bfloat16)
-    rec = None if _probe is None else _probe_launch("to_c8_bf16", 0.0, 6.0 * out.numel())
-    check(_lib.load().lea_to_c8_bf16(x5.data_ptr(), xbs, out.data_ptr(), out.stride(0), b, c,
-                                     d * h * w, _stream()), "lea_to_c8_bf16")
-    _probe_end(rec)
+    _launch("lea_to_c8_bf16", x5.data_ptr(), xbs, out.data_ptr(), out.stride(0), b, c, d * h * w,
+            probe=lambda: _op_record("to_c8_bf16", 0.0, 6.0 * out.numel()))
     return out
 
 
@@ -1305,8 +1263,7 @@ def from_c8(x: torch.Tensor) -> torch.Tensor:
     b, cb, d, h, w, _ = x.shape
     xbs = _check_c8_view(x, "x")
     out = torch.empty((b, cb * 8, d, h, w), device=x.device, dtype=torch.float32)
-    check(_lib.load().lea_from_c8_bf16(x.data_ptr(), xbs, out.data_ptr(), out.stride(0), b, cb * 8,
-                                       d * h * w, _stream()), "lea_from_c8_bf16")
+    _launch("lea_from_c8_bf16", x.data_ptr(), xbs, out.data_ptr(), out.stride(0), b, cb * 8, d * h * w)
     return out
 
 
@@ -1315,19 +1272,16 @@ def pack_conv_weight_bf16(w: torch.Tensor) -> torch.Tensor:
     _require_cuda(w)
     w = w.detach().contiguous()
     cout, cin, k = w.shape[0], w.shape[1], w.shape[-1]
-    lib = _lib.load()
-    n = lib.lea_conv3d_packed_elems_bf16(cout, cin, k)
+    n = _lib.load().lea_conv3d_packed_elems_bf16(cout, cin, k)
     if n == 0:
         raise ValueError(f"unsupported bf16 conv shape cout={cout} cin={cin} k={k}")
     packed = torch.empty(n, device=w.device, dtype=torch.bfloat16)
-    check(lib.lea_conv3d_pack_weights_bf16(w.data_ptr(), packed.data_ptr(), cout, cin, k, _stream()),
-          "lea_conv3d_pack_weights_bf16")
+    _launch("lea_conv3d_pack_weights_bf16", w.data_ptr(), packed.data_ptr(), cout, cin, k)
     return packed
 
 
 def conv_kernel_name_bf16(b, cout, cin, d, h, w, k, costvolume=False):
-    name = _lib.load().lea_conv3d_kernel_name_bf16(b, cout, cin, d, h, w, k, 1 if costvolume else 0)
-    return name.decode() if name else None
+    return _decode(_lib.load().lea_conv3d_kernel_name_bf16(b, cout, cin, d, h, w, k, 1 if costvolume else 0))
 
 
 def _pair_kernel_name_bf16(cb: int) -> str:
@@ -1355,39 +1309,17 @@ def conv3d_bnrelu_bf16(x: torch.Tensor, packed: torch.Tensor, cout: int, k: int,
         raise ValueError("pair_sum takes two sources and no residual")
     b, cb, d, h, w, _ = x.shape
     xbs = _check_c8_view(x, "x")
-    cin2, x2bs = 0, 0
-    if x2 is not None:
-        if x2.shape[0] != b or tuple(x2.shape[2:5]) != (d, h, w):
-            raise ValueError("x2 must match x in batch and volume")
-        cin2 = x2.shape[1] * 8
-        x2bs = _check_c8_view(x2, "x2")
-    shape = (b, cout // 8, d, h, w, 8)
-    if out is None:
-        if accumulate:
-            raise ValueError("accumulate needs out")
-        out = torch.empty(shape, device=x.device, dtype=torch.bfloat16)
-    if tuple(out.shape) != shape:
-        raise ValueError(f"out shape {tuple(out.shape)} != {shape}")
-    ybs = _check_c8_view(out, "out")
-    if accumulate:
-        rptr, rbs = out.data_ptr(), ybs
-    elif residual is not None:
-        if tuple(residual.shape) != shape:
-            raise ValueError("residual shape mismatch")
-        rptr, rbs = residual.data_ptr(), _check_c8_view(residual, "residual")
-    else:
-        rptr, rbs = None, 0
-    flags = (LEA_RELU if relu else 0) | (LEA_RESIDUAL if rptr is not None else 0) | (LEA_PAIR_SUM if pair_sum else 0)
-    rec = None if _probe is None else _probe_begin(
-        b, cb * 8 + cin2, cout, d, h, w, k, rptr is not None, b * d * h * w, False,
-        name=(_pair_kernel_name_bf16(cb) if pair_sum else
-              conv_kernel_name_bf16(b, cout, cb * 8 + cin2, d, h, w, k)), esz=2)
-    check(_lib.load().lea_conv3d_bnrelu_bf16(
-        x.data_ptr(), xbs, x2.data_ptr() if x2 is not None else None, x2bs, cin2, packed.data_ptr(),
-        scale.data_ptr() if scale is not None else None,
-        shift.data_ptr() if shift is not None else None, rptr, rbs, out.data_ptr(), ybs, b,
-        cb * 8 + cin2, cout, d, h, w, k, flags, _stream()), "lea_conv3d_bnrelu_bf16")
-    _probe_end(rec)
+    x2ptr, x2bs, cin2 = _second_source(x2, b, (d, h, w), c8=True)
+    cin = cb * 8 + cin2
+    out, ybs = _conv_out(b, cout, (d, h, w), out, accumulate, x.device, c8=True)
+    rptr, rbs = _residual(out, accumulate, residual, ybs, c8=True)
+    _launch("lea_conv3d_bnrelu_bf16", x.data_ptr(), xbs, x2ptr, x2bs, cin2, packed.data_ptr(), _ptr(scale),
+            _ptr(shift), rptr, rbs, out.data_ptr(), ybs, b, cin, cout, d, h, w, k,
+            _flags(relu, rptr is not None, pair_sum),
+            probe=lambda: _conv_record(
+                b, cin, cout, d, h, w, k, rptr is not None, b * d * h * w, False,
+                name=(_pair_kernel_name_bf16(cb) if pair_sum else conv_kernel_name_bf16(b, cout, cin, d, h, w, k)),
+                esz=2))
     return out
 
 
@@ -1412,20 +1344,11 @@ def conv1x1_resampled_bf16(x: torch.Tensor, size, packed: torch.Tensor, cout: in
     b, cb, di, hi, wi, _ = x.shape
     d, h, w = (int(t) for t in size)
     xbs = _check_c8_view(x, "x")
-    shape = (b, cout // 8, d, h, w, 8)
-    if out is None:
-        out = torch.empty(shape, device=x.device, dtype=torch.bfloat16)
-    if tuple(out.shape) != shape:
-        raise ValueError(f"out shape {tuple(out.shape)} != {shape}")
-    ybs = _check_c8_view(out, "out")
-    name = "conv1x1_rs_c8_kernel"
-    rec = _probe_begin(b, cb * 8, cout, d, h, w, 1, False, b * di * hi * wi, True, name=name, esz=2)
-    check(_lib.load().lea_conv1x1_resampled_bf16(
-        x.data_ptr(), xbs, di, hi, wi, packed.data_ptr(),
-        scale.data_ptr() if scale is not None else None,
-        shift.data_ptr() if shift is not None else None, out.data_ptr(), ybs, b, cb * 8, cout, d, h,
-        w, LEA_RELU if relu else 0, _stream()), "lea_conv1x1_resampled_bf16")
-    _probe_end(rec)
+    out, ybs = _conv_out(b, cout, (d, h, w), out, False, x.device, c8=True)
+    _launch("lea_conv1x1_resampled_bf16", x.data_ptr(), xbs, di, hi, wi, packed.data_ptr(), _ptr(scale),
+            _ptr(shift), out.data_ptr(), ybs, b, cb * 8, cout, d, h, w, _flags(relu),
+            probe=lambda: _conv_record(b, cb * 8, cout, d, h, w, 1, False, b * di * hi * wi, True,
+                                       name="conv1x1_rs_c8_kernel", esz=2))
     return out
 
 
@@ -1442,15 +1365,10 @@ def conv3d_bnrelu_costvolume_bf16(fl: torch.Tensor, fr: torch.Tensor, maxdisp: i
     b, cb, _, h, w, _ = fl.shape
     d3 = int(maxdisp / 3)
     out = torch.empty((b, cout // 8, d3, h, w, 8), device=fl.device, dtype=torch.bfloat16)
-    rec = None if _probe is None else _probe_begin(
-        b, 2 * cb * 8, cout, d3, h, w, 3, False, 0, False,
-        name=conv_kernel_name_bf16(b, cout, 2 * cb * 8, d3, h, w, 3, True), esz=2)
-    check(_lib.load().lea_conv3d_bnrelu_costvolume_bf16(
-        fl.data_ptr(), fr.data_ptr(), fbs, packed.data_ptr(),
-        scale.data_ptr() if scale is not None else None,
-        shift.data_ptr() if shift is not None else None, out.data_ptr(), out.stride(0), b, cb * 8,
-        cout, d3, h, w, LEA_RELU if relu else 0, _stream()), "lea_conv3d_bnrelu_costvolume_bf16")
-    _probe_end(rec)
+    _launch("lea_conv3d_bnrelu_costvolume_bf16", fl.data_ptr(), fr.data_ptr(), fbs, packed.data_ptr(), _ptr(scale),
+            _ptr(shift), out.data_ptr(), out.stride(0), b, cb * 8, cout, d3, h, w, _flags(relu),
+            probe=lambda: _conv_record(b, 2 * cb * 8, cout, d3, h, w, 3, False, 0, False,
+                                       name=conv_kernel_name_bf16(b, cout, 2 * cb * 8, d3, h, w, 3, True), esz=2))
     return out
 
 
@@ -1462,19 +1380,10 @@ def resample_trilinear_bf16(x: torch.Tensor, size, align_corners: bool = True,
     b, cb, di, hi, wi, _ = x.shape
     do, ho, wo = (int(s) for s in size)
     xbs = _check_c8_view(x, "x")
-    if out is None:
-        out = torch.empty((b, cb, do, ho, wo, 8), device=x.device, dtype=torch.bfloat16)
-    if tuple(out.shape) != (b, cb, do, ho, wo, 8):
-        raise ValueError("out shape mismatch")
-    ybs = _check_c8_view(out, "out")
-    rec = None if _probe is None else _probe_launch(
-        "resample3d_c8", 0.0, 2.0 * b * cb * 8 * (di * hi * wi + do * ho * wo))
-    check(_lib.load().lea_resample3d_trilinear_bf16(
-        x.data_ptr(), xbs, out.data_ptr(), ybs, b, cb * 8, di, hi, wi, do, ho, wo,
-        1 if align_corners else 0, scale.data_ptr() if scale is not None else None,
-        shift.data_ptr() if shift is not None else None, LEA_RELU if relu else 0, _stream()),
-        "lea_resample3d_trilinear_bf16")
-    _probe_end(rec)
+    out, ybs = _out_view(out, (b, cb, do, ho, wo, 8), x.device, c8=True)
+    _launch("lea_resample3d_trilinear_bf16", x.data_ptr(), xbs, out.data_ptr(), ybs, b, cb * 8, di, hi, wi, do, ho,
+            wo, 1 if align_corners else 0, _ptr(scale), _ptr(shift), _flags(relu),
+            probe=lambda: _op_record("resample3d_c8", 0.0, 2.0 * b * cb * 8 * (di * hi * wi + do * ho * wo)))
     return out
 
 
@@ -1485,37 +1394,18 @@ def tapsum_upsample_bf16(q: torch.Tensor, cout: int, size, scale=None, shift=Non
     b, cb, di, hi, wi, _ = q.shape
     if cb * 8 < 27 * cout:
         raise ValueError(f"q has {cb * 8} channels, need 27*{cout}")
-    qbs = _check_c8_view(q, "q")
-    do, ho, wo = (int(s) for s in size)
-    out = torch.empty((b, cout, do, ho, wo), device=q.device, dtype=torch.float32)
-    lib = _lib.load()
-    ws = torch.empty(lib.lea_tapsum_workspace_bytes(b, cout, hi, wi, do) // 4, device=q.device,
-                     dtype=torch.float32)
-    rec = None if _probe is None else _probe_launch(
-        "tapsum_c8", 0.0, 2.0 * q.numel() + 4.0 * out.numel())
-    check(lib.lea_tapsum_upsample(
-        q.data_ptr(), qbs, out.data_ptr(), out.stride(0), b, cout, di, hi, wi, do, ho, wo,
-        scale.data_ptr() if scale is not None else None,
-        shift.data_ptr() if shift is not None else None, LEA_RELU if relu else 0, ws.data_ptr(),
-        _lib.LEA_BF16, _stream()), "lea_tapsum_upsample(bf16)")
-    _probe_end(rec)
-    return out
+    return _tapsum(q, _check_c8_view(q, "q"), cout, (di, hi, wi), size, scale, shift, relu, LEA_BF16,
+                   lambda out: _op_record("tapsum_c8", 0.0, 2.0 * q.numel() + 4.0 * out.numel()))
 
 
 def pack_conv2d_weight_bf16(w: torch.Tensor) -> torch.Tensor:
     """[cout, cin, 3, 3] f32 device weight -> packed bf16 fragments (2D engine)."""
-    _require_cuda(w)
-    w = w.detach().contiguous()
-    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
-        raise ValueError(f"expected a [cout, cin, 3, 3] weight, got {tuple(w.shape)}")
-    cout, cin = w.shape[:2]
-    lib = _lib.load()
-    n = lib.lea_conv2d_packed_elems_bf16(cout, cin)
+    w, cout, cin = _conv2d_weight(w)
+    n = _lib.load().lea_conv2d_packed_elems_bf16(cout, cin)
     if n == 0:
         raise ValueError(f"unsupported bf16 conv2d shape cout={cout} cin={cin}")
     packed = torch.empty(n, device=w.device, dtype=torch.bfloat16)
-    check(lib.lea_conv2d_pack_weights_bf16(w.data_ptr(), packed.data_ptr(), cout, cin, _stream()),
-          "lea_conv2d_pack_weights_bf16")
+    _launch("lea_conv2d_pack_weights_bf16", w.data_ptr(), packed.data_ptr(), cout, cin)
     return packed
 
 
@@ -1529,31 +1419,13 @@ def conv2d_bnrelu_bf16(x: torch.Tensor, packed: torch.Tensor, cout: int, scale, 
     if d != 1:
         raise ValueError("conv2d_bnrelu_bf16 takes D = 1 maps")
     xbs = _check_c8_view(x, "x")
-    shape = (b, cout // 8, 1, h, w, 8)
-    if out is None:
-        if accumulate:
-            raise ValueError("accumulate needs out")
-        out = torch.empty(shape, device=x.device, dtype=torch.bfloat16)
-    if tuple(out.shape) != shape:
-        raise ValueError(f"out shape {tuple(out.shape)} != {shape}")
-    ybs = _check_c8_view(out, "out")
-    if accumulate:
-        rptr, rbs = out.data_ptr(), ybs
-    elif residual is not None:
-        if tuple(residual.shape) != shape:
-            raise ValueError("residual shape mismatch")
-        rptr, rbs = residual.data_ptr(), _check_c8_view(residual, "residual")
-    else:
-        rptr, rbs = None, 0
-    flags = (LEA_RELU if relu else 0) | (LEA_RESIDUAL if rptr is not None else 0)
-    rec = None if _probe is None else _probe_launch(
-        "conv2d_bf16", 2.0 * b * h * w * cout * cb * 8 * 9,
-        2.0 * b * h * w * (cb * 8 + cout * (2 if rptr is not None else 1)) + 18.0 * cout * cb * 8)
-    check(_lib.load().lea_conv2d_bnrelu_bf16(
-        x.data_ptr(), xbs, packed.data_ptr(), scale.data_ptr() if scale is not None else None,
-        shift.data_ptr() if shift is not None else None, rptr, rbs, out.data_ptr(), ybs, b, cb * 8,
-        cout, h, w, flags, _stream()), "lea_conv2d_bnrelu_bf16")
-    _probe_end(rec)
+    out, ybs = _conv_out(b, cout, (1, h, w), out, accumulate, x.device, c8=True)
+    rptr, rbs = _residual(out, accumulate, residual, ybs, c8=True)
+    _launch("lea_conv2d_bnrelu_bf16", x.data_ptr(), xbs, packed.data_ptr(), _ptr(scale), _ptr(shift), rptr, rbs,
+            out.data_ptr(), ybs, b, cb * 8, cout, h, w, _flags(relu, rptr is not None),
+            probe=lambda: _op_record(
+                "conv2d_bf16", 2.0 * b * h * w * cout * cb * 8 * 9,
+                2.0 * b * h * w * (cb * 8 + cout * (2 if rptr is not None else 1)) + 18.0 * cout * cb * 8))
     return out
 
 
@@ -1569,8 +1441,7 @@ def cv_stem_split_weights(w: torch.Tensor):
     cout, c = w.shape[0], w.shape[1] // 2
     wl = torch.empty((9 * cout, c, 3, 3), device=w.device, dtype=torch.float32)
     wr = torch.empty((6 * cout, c, 3, 3), device=w.device, dtype=torch.float32)
-    check(_lib.load().lea_cv_stem_split_weights(w.data_ptr(), wl.data_ptr(), wr.data_ptr(), cout, c,
-                                                _stream()), "lea_cv_stem_split_weights")
+    _launch("lea_cv_stem_split_weights", w.data_ptr(), wl.data_ptr(), wr.data_ptr(), cout, c)
     return wl, wr
 
 
@@ -1580,45 +1451,34 @@ def cv_stem_supported(cout: int, d3: int, w: int, bf16: bool) -> bool:
     return d3 >= 2 and (cout % 8 == 0 if bf16 else w % 4 == 0)
 
 
+def _cv_stem_maps(who, lmaps, rmaps, cout, c8=False):
+    """The 2D maps of the factored stem0 in either layout: (B, H, W, left and right batch stride)."""
+    (_require_c8 if c8 else _require_cuda)(lmaps, rmaps)
+    b, h, w = lmaps.shape[0], lmaps.shape[3], lmaps.shape[4]
+    lbs, rbs = _batch_stride(lmaps, "lmaps", c8), _batch_stride(rmaps, "rmaps", c8)
+    per = 8 if c8 else 1
+    if lmaps.shape[1] * per != 9 * cout or rmaps.shape[1] * per != 6 * cout:
+        raise ValueError(f"{who}: map channels must be 9 / 6 x cout")
+    return b, h, w, lbs, rbs
+
+
 def cv_stem_combine(lmaps: torch.Tensor, rmaps: torch.Tensor, cout: int, d3: int,
                     scale: torch.Tensor | None, shift: torch.Tensor | None, relu: bool = True,
                     name: str = "cv_stem_f32_kernel") -> torch.Tensor:
     """stem0's output from the 2D maps: lmaps [B, 9 cout, 1, H, W] / rmaps [B, 6 cout, 1, H, W]
     f32 -> [B, cout, D3, H, W] f32, or c8 maps -> c8 [B, cout/8, D3, H, W, 8] bf16."""
     c8 = lmaps.dtype == torch.bfloat16
-    if c8:
-        _require_c8(lmaps, rmaps)
-        b, _, _, h, w, _ = lmaps.shape
-        lbs, rbs = _check_c8_view(lmaps, "lmaps"), _check_c8_view(rmaps, "rmaps")
-        if lmaps.shape[1] * 8 != 9 * cout or rmaps.shape[1] * 8 != 6 * cout:
-            raise ValueError("cv_stem_combine: map channels must be 9 / 6 x cout")
-        out = torch.empty((b, cout // 8, d3, h, w, 8), device=lmaps.device, dtype=torch.bfloat16)
-        ybs = out.stride(0)
-    else:
-        _require_cuda(lmaps, rmaps)
-        b, _, _, h, w = lmaps.shape
-        lbs, rbs = _check_volume_view(lmaps, "lmaps"), _check_volume_view(rmaps, "rmaps")
-        if lmaps.shape[1] != 9 * cout or rmaps.shape[1] != 6 * cout:
-            raise ValueError("cv_stem_combine: map channels must be 9 / 6 x cout")
-        out = torch.empty((b, cout, d3, h, w), device=lmaps.device, dtype=torch.float32)
-        ybs = out.stride(0)
+    b, h, w, lbs, rbs = _cv_stem_maps("cv_stem_combine", lmaps, rmaps, cout, c8)
+    out = torch.empty(_act_shape(b, cout, (d3, h, w), c8), device=lmaps.device,
+                      dtype=torch.bfloat16 if c8 else torch.float32)
     _require_cuda(scale, shift)
     if tuple(rmaps.shape[0:1]) != (b,) or tuple(rmaps.shape[3:5]) != (h, w):
         raise ValueError("cv_stem_combine: left/right maps differ in batch or size")
-    rec = None
-    if _probe is not None and (_probe.names is None or name in _probe.names):
-        # algorithmic bytes: the output write (the maps are L2/MALL-resident reads)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        rec = (name, 0.0, float(out.numel() * out.element_size()), e0, e1, 0.0, (b, 0, cout, d3, h, w, 0))
-    check(_lib.load().lea_cv_stem_combine(
-        lmaps.data_ptr(), lbs, rmaps.data_ptr(), rbs,
-        scale.data_ptr() if scale is not None else None,
-        shift.data_ptr() if shift is not None else None, out.data_ptr(), ybs, b, cout, d3, h, w,
-        LEA_RELU if relu else 0, _lib.LEA_BF16 if c8 else LEA_F32, _stream()), "lea_cv_stem_combine")
-    if rec is not None:
-        rec[4].record()
-        _probe.records.append(rec)
+    # algorithmic bytes: the output write (the maps are L2/MALL-resident reads)
+    _launch("lea_cv_stem_combine", lmaps.data_ptr(), lbs, rmaps.data_ptr(), rbs, _ptr(scale), _ptr(shift),
+            out.data_ptr(), out.stride(0), b, cout, d3, h, w, _flags(relu), LEA_BF16 if c8 else LEA_F32,
+            probe=lambda: _op_record(name, 0.0, out.numel() * out.element_size(), 0.0,
+                                     shape=(b, 0, cout, d3, h, w, 0)))
     return out
 
 
@@ -1635,39 +1495,34 @@ def cv_stem_combine_down2(lmaps: torch.Tensor, rmaps: torch.Tensor, cout: int, d
     """``cv_stem_combine`` (f32) with stem0's output also at the next level: returns (y, y2),
     y2 [B, cout, D3/2, H/2, W/2] = resample_trilinear(y, (D3/2, H/2, W/2)) bit for bit, written
     by the same launch from the row pair it holds in registers (no second pass over y)."""
-    _require_cuda(lmaps, rmaps, scale, shift)
-    b, _, _, h, w = lmaps.shape
-    lbs, rbs = _check_volume_view(lmaps, "lmaps"), _check_volume_view(rmaps, "rmaps")
-    if lmaps.shape[1] != 9 * cout or rmaps.shape[1] != 6 * cout:
-        raise ValueError("cv_stem_combine_down2: map channels must be 9 / 6 x cout")
+    _require_cuda(scale, shift)
+    b, h, w, lbs, rbs = _cv_stem_maps("cv_stem_combine_down2", lmaps, rmaps, cout)
     if tuple(rmaps.shape[0:1]) != (b,) or tuple(rmaps.shape[3:5]) != (h, w):
         raise ValueError("cv_stem_combine_down2: left/right maps differ in batch or size")
     out = torch.empty((b, cout, d3, h, w), device=lmaps.device, dtype=torch.float32)
     out2 = torch.empty((b, cout, d3 // 2, h // 2, w // 2), device=lmaps.device, dtype=torch.float32)
     # algorithmic bytes: the maps and both outputs
-    nbytes = 4.0 * (lmaps.numel() + rmaps.numel() + out.numel() + out2.numel())
-    rec = _probe_launch("cv_stem_f32_down2_kernel", 0.0, nbytes)
-    check(_lib.load().lea_cv_stem_combine_down2(
-        lmaps.data_ptr(), lbs, rmaps.data_ptr(), rbs,
-        scale.data_ptr() if scale is not None else None,
-        shift.data_ptr() if shift is not None else None, out.data_ptr(), out.stride(0),
-        out2.data_ptr(), out2.stride(0), b, cout, d3, h, w, LEA_RELU if relu else 0, LEA_F32, _stream()),
-        "lea_cv_stem_combine_down2")
-    _probe_end(rec)
+    _launch("lea_cv_stem_combine_down2", lmaps.data_ptr(), lbs, rmaps.data_ptr(), rbs, _ptr(scale), _ptr(shift),
+            out.data_ptr(), out.stride(0), out2.data_ptr(), out2.stride(0), b, cout, d3, h, w, _flags(relu), LEA_F32,
+            probe=lambda: _op_record("cv_stem_f32_down2_kernel", 0.0,
+                                     4.0 * (lmaps.numel() + rmaps.numel() + out.numel() + out2.numel())))
     return out, out2
 
 
 # ---- host steps either side of forward (SURVEY.md §8f rank 3) ----
+
+def _require_u8_images(who, left, right):
+    for t in (left, right):
+        if not t.is_cuda or t.dtype != torch.uint8:
+            raise _lib.HipKernelError(f"{who} needs uint8 device images, got {t.dtype} on {t.device}")
+
 
 def standardize_crop_u8(left: torch.Tensor, right: torch.Tensor, crop_height: int, crop_width: int):
     """predict.py:162-184 (load_data) fused with :144-159 (test_transform) on the device.
 
     ``left``/``right``: uint8 [B, H, W, 3|4] (or [H, W, 3|4]) decoded images on the
     ROCm device.  Returns (left, right) float32 [B, 3, crop_height, crop_width]."""
-    for t in (left, right):
-        if not t.is_cuda or t.dtype != torch.uint8:
-            raise _lib.HipKernelError(f"standardize_crop_u8 needs uint8 device images, got "
-                                      f"{t.dtype} on {t.device}")
+    _require_u8_images("standardize_crop_u8", left, right)
     if left.dim() == 3:
         left, right = left.unsqueeze(0), right.unsqueeze(0)
     if left.shape != right.shape or left.dim() != 4 or left.shape[-1] not in (3, 4):
@@ -1679,9 +1534,8 @@ def standardize_crop_u8(left: torch.Tensor, right: torch.Tensor, crop_height: in
     ws = torch.empty(lib.lea_standardize_workspace_bytes(b), device=left.device, dtype=torch.uint8)
     out_l = torch.empty((b, 3, crop_height, crop_width), device=left.device, dtype=torch.float32)
     out_r = torch.empty_like(out_l)
-    rc = lib.lea_standardize_crop_u8(left.data_ptr(), right.data_ptr(), b, h, w, ps,
-                                     out_l.data_ptr(), out_r.data_ptr(), crop_height, crop_width,
-                                     ws.data_ptr(), _stream())
+    rc = _call("lea_standardize_crop_u8", left.data_ptr(), right.data_ptr(), b, h, w, ps, out_l.data_ptr(),
+               out_r.data_ptr(), crop_height, crop_width, ws.data_ptr())
     if rc == _lib.LEA_E_INVALID and b"test_transform" in lib.lea_last_error():
         raise ValueError(lib.lea_last_error().decode())
     check(rc, "lea_standardize_crop_u8")
@@ -1699,10 +1553,7 @@ def train_transform_u8(left: torch.Tensor, right: torch.Tensor, disp_left: torch
     [B, 1, ch, cw], n_valid int32 [B]).  Nothing is copied to the host and nothing
     synchronises: the launches read ``params`` from device memory, so the call can be
     captured in a graph and replayed after ``params`` is overwritten."""
-    for t in (left, right):
-        if not t.is_cuda or t.dtype != torch.uint8:
-            raise _lib.HipKernelError(f"train_transform_u8 needs uint8 device images, got "
-                                      f"{t.dtype} on {t.device}")
+    _require_u8_images("train_transform_u8", left, right)
     _require_cuda(disp_left, disp_right)
     if not params.is_cuda or params.dtype != torch.int32:
         raise _lib.HipKernelError(f"train_transform_u8 needs int32 device params, got "
@@ -1717,20 +1568,16 @@ def train_transform_u8(left: torch.Tensor, right: torch.Tensor, disp_left: torch
     if tuple(params.shape) != (b, 5):
         raise ValueError(f"params must be [B, 5] = {(b, 5)}, got {tuple(params.shape)}")
     left, right, disp_left, params = left.contiguous(), right.contiguous(), disp_left.contiguous(), params.contiguous()
-    if disp_right is not None:
-        disp_right = disp_right.contiguous()
-    lib = _lib.load()
+    disp_right = _contiguous(disp_right)
     dev = left.device
-    ws = torch.empty(lib.lea_train_transform_workspace_bytes(b), device=dev, dtype=torch.uint8)
+    ws = torch.empty(_lib.load().lea_train_transform_workspace_bytes(b), device=dev, dtype=torch.uint8)
     out_l = torch.empty((b, 3, crop_height, crop_width), device=dev, dtype=torch.float32)
     out_r = torch.empty_like(out_l)
     out_t = torch.empty((b, 1, crop_height, crop_width), device=dev, dtype=torch.float32)
     n_valid = torch.empty((b,), device=dev, dtype=torch.int32)
-    check(lib.lea_train_transform_u8(left.data_ptr(), right.data_ptr(), b, h, w, ps, disp_left.data_ptr(),
-                                     disp_right.data_ptr() if disp_right is not None else None,
-                                     params.data_ptr(), out_l.data_ptr(), out_r.data_ptr(), out_t.data_ptr(),
-                                     crop_height, crop_width, float(maxdisp), n_valid.data_ptr(),
-                                     ws.data_ptr(), _stream()), "lea_train_transform_u8")
+    _launch("lea_train_transform_u8", left.data_ptr(), right.data_ptr(), b, h, w, ps, disp_left.data_ptr(),
+            _ptr(disp_right), params.data_ptr(), out_l.data_ptr(), out_r.data_ptr(), out_t.data_ptr(), crop_height,
+            crop_width, float(maxdisp), n_valid.data_ptr(), ws.data_ptr())
     return out_l, out_r, out_t, n_valid
 
 
@@ -1743,10 +1590,7 @@ def standardize_tiles_u8(left: torch.Tensor, right: torch.Tensor, origins: torch
     tensor ``origins`` [N, 2] holds, standardised with the whole scene's statistics, 0 outside
     the scene.  Returns (left, right) float32 [N, 3, tile_height, tile_width].  Nothing is
     copied to the host and nothing synchronises; any origins are memory-safe."""
-    for t in (left, right):
-        if not t.is_cuda or t.dtype != torch.uint8:
-            raise _lib.HipKernelError(f"standardize_tiles_u8 needs uint8 device images, got "
-                                      f"{t.dtype} on {t.device}")
+    _require_u8_images("standardize_tiles_u8", left, right)
     if not origins.is_cuda or origins.dtype != torch.int32:
         raise _lib.HipKernelError(f"standardize_tiles_u8 needs int32 device origins, got "
                                   f"{origins.dtype} on {origins.device}")
@@ -1760,13 +1604,11 @@ def standardize_tiles_u8(left: torch.Tensor, right: torch.Tensor, origins: torch
     left, right, origins = left.contiguous(), right.contiguous(), origins.contiguous()
     h, w, ps = left.shape
     n = origins.shape[0]
-    lib = _lib.load()
-    ws = torch.empty(lib.lea_standardize_tiles_workspace_bytes(), device=left.device, dtype=torch.uint8)
+    ws = torch.empty(_lib.load().lea_standardize_tiles_workspace_bytes(), device=left.device, dtype=torch.uint8)
     out_l = torch.empty((n, 3, tile_height, tile_width), device=left.device, dtype=torch.float32)
     out_r = torch.empty_like(out_l)
-    check(lib.lea_standardize_tiles_u8(left.data_ptr(), right.data_ptr(), h, w, ps, origins.data_ptr(), n,
-                                       out_l.data_ptr(), out_r.data_ptr(), tile_height, tile_width,
-                                       ws.data_ptr(), _stream()), "lea_standardize_tiles_u8")
+    _launch("lea_standardize_tiles_u8", left.data_ptr(), right.data_ptr(), h, w, ps, origins.data_ptr(), n,
+            out_l.data_ptr(), out_r.data_ptr(), tile_height, tile_width, ws.data_ptr())
     return out_l, out_r
 
 
@@ -1784,8 +1626,7 @@ def blend_tiles(tiles: torch.Tensor, plan, view: str = "left", check: bool = Fal
     n, th, tw = plan.ny * plan.nx, plan.tile_h, plan.tile_w
     if tiles.dim() != 3 or tuple(tiles.shape) != (n, th, tw):
         raise ValueError(f"tiles must be [N, tile_h, tile_w] = {(n, th, tw)}, got {tuple(tiles.shape)}")
-    if tiles.stride()[1:] != (tw, 1) or (n > 1 and tiles.stride(0) < th * tw):
-        tiles = tiles.contiguous()
+    tiles, tbs = _plane_view(tiles, "tiles")
     (gy0, gy1), (gx0, gx1) = plan.guards(view)
     ys, xs = plan.device_axes(tiles.device)
     if check and count is None:
@@ -1793,10 +1634,8 @@ def blend_tiles(tiles: torch.Tensor, plan, view: str = "left", check: bool = Fal
     if count is not None and (not count.is_cuda or count.dtype != torch.int32 or count.numel() != 1):
         raise ValueError("count must be one int32 element on the device")
     out = torch.empty((plan.height, plan.width), device=tiles.device, dtype=torch.float32)
-    _lib.check(_lib.load().lea_tile_blend_f32(
-        tiles.data_ptr(), tiles.stride(0) if n > 1 else th * tw, ys.data_ptr(), plan.ny, xs.data_ptr(), plan.nx,
-        th, tw, gy0, gy1, gx0, gx1, plan.ramp, out.data_ptr(), plan.height, plan.width,
-        None if count is None else count.data_ptr(), _stream()), "lea_tile_blend_f32")
+    _launch("lea_tile_blend_f32", tiles.data_ptr(), tbs, ys.data_ptr(), plan.ny, xs.data_ptr(), plan.nx, th, tw,
+            gy0, gy1, gx0, gx1, plan.ramp, out.data_ptr(), plan.height, plan.width, _ptr(count))
     if check:
         holes = int(count.item())
         if holes:
@@ -1824,16 +1663,13 @@ def disparity_metrics(pred: torch.Tensor, gt: torch.Tensor, maxdisp: float, roun
         raise ValueError("three bad-pixel thresholds")
     pred, gt = pred.contiguous(), gt.contiguous()
     b, h, w = pred.shape
-    lib = _lib.load()
-    ws = torch.empty(lib.lea_disparity_metrics_workspace_bytes(b, h, w), device=pred.device,
+    ws = torch.empty(_lib.load().lea_disparity_metrics_workspace_bytes(b, h, w), device=pred.device,
                      dtype=torch.uint8)
     out = torch.empty((b, 8), device=pred.device, dtype=torch.float64)
     mask = torch.empty((b, h, w), device=pred.device, dtype=torch.uint8) if correct_mask else None
-    check(lib.lea_disparity_metrics(pred.data_ptr(), h * w, gt.data_ptr(), h * w, b, h, w,
-                                    float(maxdisp), int(bool(round_pred)), int(z_shift),
-                                    *(int(t) for t in thresholds),
-                                    mask.data_ptr() if mask is not None else None, out.data_ptr(),
-                                    ws.data_ptr(), _stream()), "lea_disparity_metrics")
+    _launch("lea_disparity_metrics", pred.data_ptr(), h * w, gt.data_ptr(), h * w, b, h, w, float(maxdisp),
+            int(bool(round_pred)), int(z_shift), *(int(t) for t in thresholds), _ptr(mask), out.data_ptr(),
+            ws.data_ptr())
     return out, mask
 
 
@@ -1908,8 +1744,7 @@ def wino_depth_f2():
 
 
 def wino_kernel_name(b, cout, d, h, w, costvolume=False, cin=0):
-    name = _lib.load().lea_conv3d_wino_kernel_name(b, cin, cout, d, h, w, 1 if costvolume else 0)
-    return name.decode() if name else None
+    return _decode(_lib.load().lea_conv3d_wino_kernel_name(b, cin, cout, d, h, w, 1 if costvolume else 0))
 
 
 def pack_conv_weight_wino(w: torch.Tensor) -> torch.Tensor:
@@ -1924,8 +1759,7 @@ def pack_conv_weight_wino(w: torch.Tensor) -> torch.Tensor:
     if n == 0:
         raise ValueError(f"unsupported Winograd conv shape cout={cout} cin={cin}")
     packed = torch.empty(n, device=w.device, dtype=torch.float32)
-    check(_lib.load().lea_conv3d_wino_pack_weights(w.data_ptr(), packed.data_ptr(), cout, cin,
-                                                   _stream()), "lea_conv3d_wino_pack_weights")
+    _launch("lea_conv3d_wino_pack_weights", w.data_ptr(), packed.data_ptr(), cout, cin)
     return packed
 
 
@@ -1939,6 +1773,13 @@ def pair_sum_supported(x: torch.Tensor, x2: torch.Tensor, out: torch.Tensor) -> 
         ok = ok and t.data_ptr() % al == 0 and t.stride(0) % (al // 4) == 0 and \
             t.stride()[1:] == (d * h * w, h * w, w, 1)
     return bool(ok and 16 * d * h * w * 4 < 0xFFFFFF00)
+
+
+def _wino_record(name, mfma_name, b, cin, cout, d, h, w, accumulate, in_vox, nbytes=None):
+    """``_conv_record`` of a Winograd launch reported as ``name`` that issues the products of
+    kernel ``mfma_name``."""
+    return _conv_record(b, cin, cout, d, h, w, 3, accumulate, in_vox, False, name=name,
+                        mfma_scale=wino_mfma_scale(cout, mfma_name), nbytes=nbytes)
 
 
 def conv3d_bnrelu_wino(x: torch.Tensor, packed: torch.Tensor, cout: int,
@@ -1955,28 +1796,17 @@ def conv3d_bnrelu_wino(x: torch.Tensor, packed: torch.Tensor, cout: int,
         raise ValueError("pair_sum takes two sources and no residual")
     b, cin, d, h, w = x.shape
     xbs = _check_volume_view(x, "x")
-    cin2, x2bs = 0, 0
-    if x2 is not None:
-        if x2.shape[0] != b or tuple(x2.shape[2:]) != (d, h, w):
-            raise ValueError("x2 must match x in batch and volume")
-        cin2 = x2.shape[1]
-        x2bs = _check_volume_view(x2, "x2")
-    out, ybs = _conv_out(x.shape, cout, (d, h, w), out, accumulate, x.device, x.dtype)
+    x2ptr, x2bs, cin2 = _second_source(x2, b, (d, h, w))
+    out, ybs = _conv_out(b, cout, (d, h, w), out, accumulate, x.device)
     rptr, rbs = _residual(out, accumulate, residual, ybs)
-    flags = (LEA_RELU if relu else 0) | (LEA_RESIDUAL if rptr is not None else 0) | (LEA_PAIR_SUM if pair_sum else 0)
-    rec = None
-    if _probe is not None:  # (the kernel-name query only when a probe listens)
+
+    def probe():  # (the kernel-name query only when a probe listens)
         name = "conv3d_wino22_kernel" if pair_sum else wino_kernel_name(b, cout, d, h, w, cin=cin + cin2)
-        rec = _probe_begin(b, cin + cin2, cout, d, h, w, 3, rptr is not None, b * d * h * w, False,
-                           name=name, mfma_scale=wino_mfma_scale(cout, name))
-    check(_lib.load().lea_conv3d_bnrelu_wino(
-        x.data_ptr(), xbs, x2.data_ptr() if x2 is not None else None, x2bs, cin2,
-        packed.data_ptr(),
-        scale.data_ptr() if scale is not None else None,
-        shift.data_ptr() if shift is not None else None,
-        rptr, rbs, out.data_ptr(), ybs, b, cin + cin2, cout, d, h, w, flags, LEA_F32, _stream()),
-        "lea_conv3d_bnrelu_wino")
-    _probe_end(rec)
+        return _wino_record(name, name, b, cin + cin2, cout, d, h, w, rptr is not None, b * d * h * w)
+
+    _launch("lea_conv3d_bnrelu_wino", x.data_ptr(), xbs, x2ptr, x2bs, cin2, packed.data_ptr(), _ptr(scale),
+            _ptr(shift), rptr, rbs, out.data_ptr(), ybs, b, cin + cin2, cout, d, h, w,
+            _flags(relu, rptr is not None, pair_sum), LEA_F32, probe=probe)
     return out
 
 
@@ -1984,11 +1814,8 @@ def wino_down2_kernel_name(b, cin, cout, d, h, w, cin2=0):
     """The instantiation conv3d_bnrelu_wino_down2 launches for this shape (cin2 > 0: the
     two-input form, cin2 of the cin channels from x2), or None."""
     lib = _lib.load()
-    if cin2:
-        name = lib.lea_conv3d_wino_down2_cat_kernel_name(b, cin, cin2, cout, d, h, w)
-    else:
-        name = lib.lea_conv3d_wino_down2_kernel_name(b, cin, cout, d, h, w)
-    return name.decode() if name else None
+    return _decode(lib.lea_conv3d_wino_down2_cat_kernel_name(b, cin, cin2, cout, d, h, w) if cin2
+                   else lib.lea_conv3d_wino_down2_kernel_name(b, cin, cout, d, h, w))
 
 
 def conv3d_wino_down2_supported(x: torch.Tensor, cout: int) -> bool:
@@ -2005,12 +1832,8 @@ def conv3d_wino_down2_cat_supported(x: torch.Tensor, x2: torch.Tensor, cout: int
 
 
 def _wino_down2_supported(x, cout, x2):
-    for t in (x,) if x2 is None else (x, x2):
-        if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 5:
-            return False
-        d, h, w = t.shape[2:]
-        if t.data_ptr() % 16 or t.stride(0) % 4 or t.stride()[1:] != (d * h * w, h * w, w, 1):
-            return False
+    if not all(_f32_volume(t, aligned=True) for t in ((x,) if x2 is None else (x, x2))):
+        return False
     b, cin, d, h, w = x.shape
     if x2 is None:
         return bool(_lib.load().lea_conv3d_wino_down2_supported(b, cin, cout, d, h, w))
@@ -2039,56 +1862,38 @@ def _wino_down2(x, x2, packed, cout, scale, shift, relu):
     _require_cuda(x, x2, packed, scale, shift)
     b, cin, d, h, w = x.shape
     xbs = _check_volume_view(x, "x")
-    cin2, x2bs = 0, 0
-    if x2 is not None:
-        if x2.shape[0] != b or tuple(x2.shape[2:]) != (d, h, w):
-            raise ValueError("x2 must match x in batch and volume")
-        cin2 = x2.shape[1]
-        x2bs = _check_volume_view(x2, "x2")
+    x2ptr, x2bs, cin2 = _second_source(x2, b, (d, h, w))
     cin += cin2
     out = torch.empty((b, cout, d // 2, h // 2, w // 2), device=x.device, dtype=x.dtype)
-    rec = None
-    if _probe is not None:
+
+    def probe():  # the same tile as the plain form; the bytes really moved: input + weights + the L1 output
         name = wino_down2_kernel_name(b, cin, cout, d, h, w, cin2) or (
             "conv3d_wino44_down2_cat_kernel" if cin2 else "conv3d_wino44_down2_kernel")
-        rec = _probe_begin(b, cin, cout, d, h, w, 3, False, b * d * h * w, False, name=name,
-                           mfma_scale=wino_mfma_scale(cout, "conv3d_wino44_kernel"))  # (the same tile)
-        if rec is not None:  # the bytes really moved: input + weights + the L1 output
-            nbytes = 4.0 * (b * cin * d * h * w + out.numel()) + 4.0 * cout * cin * 27
-            rec = rec[:3] + (nbytes,) + rec[4:]
-    lib = _lib.load()
-    sp = scale.data_ptr() if scale is not None else None
-    hp = shift.data_ptr() if shift is not None else None
-    flags = LEA_RELU if relu else 0
+        return _wino_record(name, "conv3d_wino44_kernel", b, cin, cout, d, h, w, False, b * d * h * w,
+                            nbytes=4.0 * (b * cin * d * h * w + out.numel()) + 4.0 * cout * cin * 27)
+
     if x2 is None:
-        check(lib.lea_conv3d_bnrelu_wino_down2(
-            x.data_ptr(), xbs, packed.data_ptr(), sp, hp,
-            out.data_ptr(), out.stride(0), b, cin, cout, d, h, w, flags, LEA_F32, _stream()),
-            "lea_conv3d_bnrelu_wino_down2")
+        _launch("lea_conv3d_bnrelu_wino_down2", x.data_ptr(), xbs, packed.data_ptr(), _ptr(scale), _ptr(shift),
+                out.data_ptr(), out.stride(0), b, cin, cout, d, h, w, _flags(relu), LEA_F32, probe=probe)
     else:
-        check(lib.lea_conv3d_bnrelu_wino_down2_cat(
-            x.data_ptr(), xbs, x2.data_ptr(), x2bs, cin2, packed.data_ptr(), sp, hp,
-            out.data_ptr(), out.stride(0), b, cin, cout, d, h, w, flags, LEA_F32, _stream()),
-            "lea_conv3d_bnrelu_wino_down2_cat")
-    _probe_end(rec)
+        _launch("lea_conv3d_bnrelu_wino_down2_cat", x.data_ptr(), xbs, x2ptr, x2bs, cin2, packed.data_ptr(),
+                _ptr(scale), _ptr(shift), out.data_ptr(), out.stride(0), b, cin, cout, d, h, w, _flags(relu),
+                LEA_F32, probe=probe)
     return out
 
 
 def wino_dp_down2_kernel_name(b, cin, cout, d, h, w, only=False):
     """The instantiation conv3d_bnrelu_wino_dp_down2 launches for this shape, or None."""
-    name = _lib.load().lea_conv3d_wino_dp_down2_kernel_name(b, cin, cout, d, h, w, 1 if only else 0)
-    return name.decode() if name else None
+    return _decode(_lib.load().lea_conv3d_wino_dp_down2_kernel_name(b, cin, cout, d, h, w, 1 if only else 0))
 
 
 def conv3d_wino_dp_down2_supported(x: torch.Tensor, cout: int) -> bool:
     """Whether conv3d_bnrelu_wino_dp_down2 takes this input: an f32 NCDHW device tensor (16-byte
     aligned, whole 16-byte batch strides) of a shape the planner puts on a depth-paired tile
     (lea_conv3d_wino_dp_down2_supported: cout <= 8, even D / H, W % 4 == 0)."""
-    if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 5:
+    if not _f32_volume(x, aligned=True):
         return False
     b, cin, d, h, w = x.shape
-    if x.data_ptr() % 16 or x.stride(0) % 4 or x.stride()[1:] != (d * h * w, h * w, w, 1):
-        return False
     return bool(_lib.load().lea_conv3d_wino_dp_down2_supported(b, cin, cout, d, h, w))
 
 
@@ -2107,37 +1912,21 @@ def conv3d_bnrelu_wino_dp_down2(x: torch.Tensor, packed: torch.Tensor, cout: int
             raise ValueError("no out: the `only` form without accumulate")
         ybs = 0
     else:
-        out, ybs = _conv_out(x.shape, cout, (d, h, w), out, accumulate, x.device, x.dtype)
-    if tuple(down.shape) != (b, cout, d // 2, h // 2, w // 2):
-        raise ValueError(f"down shape {tuple(down.shape)} != {(b, cout, d // 2, h // 2, w // 2)}")
-    dbs = _check_volume_view(down, "down")
-    if accumulate:
-        rptr, rbs = _residual(out, True, residual, ybs)
-    elif residual is not None:
-        _require_cuda(residual)
-        if tuple(residual.shape) != (b, cout, d, h, w):
-            raise ValueError(f"residual shape {tuple(residual.shape)} != {(b, cout, d, h, w)}")
-        rptr, rbs = residual.data_ptr(), _check_volume_view(residual, "residual")
-    else:
-        rptr, rbs = None, 0
-    flags = (LEA_RELU if relu else 0) | (LEA_RESIDUAL if rptr is not None else 0)
-    rec = None
-    if _probe is not None:
+        out, ybs = _conv_out(b, cout, (d, h, w), out, accumulate, x.device)
+    down, dbs = _out_view(down, (b, cout, d // 2, h // 2, w // 2), x.device, name="down")
+    rptr, rbs = _residual(out, accumulate, residual, ybs, shape=(b, cout, d, h, w))
+
+    def probe():  # the bytes really moved: input, weights, residual, L0 output unless `only`, L1
         name = wino_dp_down2_kernel_name(b, cin, cout, d, h, w, only) or "conv3d_wino_dp_down2_kernel"
-        rec = _probe_begin(b, cin, cout, d, h, w, 3, rptr is not None, b * d * h * w, False, name=name,
-                           mfma_scale=wino_mfma_scale(cout, wino_kernel_name(b, cout, d, h, w, cin=cin)))
-        if rec is not None:  # the bytes really moved: input, weights, residual, L0 output unless `only`, L1
-            vox = b * cout * d * h * w
-            nbytes = 4.0 * (x.numel() + (vox if rptr is not None else 0) + (0 if only else vox) + down.numel()) \
-                + 4.0 * cout * cin * 27
-            rec = rec[:3] + (nbytes,) + rec[4:]
-    check(_lib.load().lea_conv3d_bnrelu_wino_dp_down2(
-        x.data_ptr(), xbs, packed.data_ptr(),
-        scale.data_ptr() if scale is not None else None,
-        shift.data_ptr() if shift is not None else None,
-        rptr, rbs, None if only else out.data_ptr(), ybs, down.data_ptr(), dbs, b, cin, cout, d, h, w, flags,
-        LEA_F32, _stream()), "lea_conv3d_bnrelu_wino_dp_down2")
-    _probe_end(rec)
+        vox = b * cout * d * h * w
+        return _wino_record(
+            name, wino_kernel_name(b, cout, d, h, w, cin=cin), b, cin, cout, d, h, w, rptr is not None,
+            b * d * h * w, nbytes=4.0 * (x.numel() + (vox if rptr is not None else 0) + (0 if only else vox) +
+                                         down.numel()) + 4.0 * cout * cin * 27)
+
+    _launch("lea_conv3d_bnrelu_wino_dp_down2", x.data_ptr(), xbs, packed.data_ptr(), _ptr(scale), _ptr(shift),
+            rptr, rbs, None if only else out.data_ptr(), ybs, down.data_ptr(), dbs, b, cin, cout, d, h, w,
+            _flags(relu, rptr is not None), LEA_F32, probe=probe)
     return down
 
 
@@ -2147,22 +1936,15 @@ def conv3d_bnrelu_costvolume_wino(fl: torch.Tensor, fr: torch.Tensor, maxdisp: i
     """``conv3d_bnrelu_costvolume`` on the Winograd engine (the cost volume of
     LEAStereo.py:34-48 read in place, never materialised)."""
     _require_cuda(fl, fr, packed, scale, shift)
-    if fl.shape != fr.shape or fl.dim() != 4:
-        raise ValueError("left/right features must both be [B, C, H, W]")
-    if fl.stride() != fr.stride() or fl.stride()[1:] != (fl.shape[2] * fl.shape[3], fl.shape[3], 1):
-        raise ValueError("left/right features need contiguous C,H,W and equal strides")
-    b, c, h, w = fl.shape
+    b, c, h, w = _feature_pair(fl, fr)
     d3 = int(maxdisp / 3)
     out = torch.empty((b, cout, d3, h, w), device=fl.device, dtype=fl.dtype)
-    rec = None
-    if _probe is not None:
+
+    def probe():
         name = wino_kernel_name(b, cout, d3, h, w, True, cin=2 * c)
-        rec = _probe_begin(b, 2 * c, cout, d3, h, w, 3, False, 0, False,
-                           name=name, mfma_scale=wino_mfma_scale(cout, name))
-    check(_lib.load().lea_conv3d_bnrelu_costvolume_wino(
-        fl.data_ptr(), fr.data_ptr(), fl.stride(0), packed.data_ptr(),
-        scale.data_ptr() if scale is not None else None,
-        shift.data_ptr() if shift is not None else None, out.data_ptr(), out.stride(0), b, c, cout,
-        d3, h, w, LEA_RELU if relu else 0, LEA_F32, _stream()), "lea_conv3d_bnrelu_costvolume_wino")
-    _probe_end(rec)
+        return _wino_record(name, name, b, 2 * c, cout, d3, h, w, False, 0)
+
+    _launch("lea_conv3d_bnrelu_costvolume_wino", fl.data_ptr(), fr.data_ptr(), fl.stride(0), packed.data_ptr(),
+            _ptr(scale), _ptr(shift), out.data_ptr(), out.stride(0), b, c, cout, d3, h, w, _flags(relu), LEA_F32,
+            probe=probe)
     return out

@@ -26,11 +26,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, kernels
-from ._lib import LEA_RELU, check
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
+from .kernels import _flags, _launch, _ptr
 
 
 def flip_weights(w: torch.Tensor) -> torch.Tensor:
@@ -40,8 +36,7 @@ def flip_weights(w: torch.Tensor) -> torch.Tensor:
     w = w.detach().contiguous()
     cout, cin, k = w.shape[0], w.shape[1], w.shape[-1]
     wt = torch.empty((cin, cout, k, k, k), device=w.device, dtype=torch.float32)
-    check(_lib.load().lea_conv3d_flip_weights(w.data_ptr(), wt.data_ptr(), cout, cin, k, _stream()),
-          "lea_conv3d_flip_weights")
+    _launch("lea_conv3d_flip_weights", w.data_ptr(), wt.data_ptr(), cout, cin, k)
     return wt
 
 
@@ -54,24 +49,19 @@ def conv3d_wgrad(x: torch.Tensor, dz: torch.Tensor, k: int) -> torch.Tensor:
     cout = dz.shape[1]
     if dz.shape[0] != b or tuple(dz.shape[2:]) != (d, h, w):
         raise ValueError(f"conv3d_wgrad: dz {tuple(dz.shape)} does not match x {tuple(x.shape)}")
-    lib = _lib.load()
-    nws = lib.lea_conv3d_wgrad_workspace_bytes(b, cin, cout, d, h, w, k)
+    nws = _lib.load().lea_conv3d_wgrad_workspace_bytes(b, cin, cout, d, h, w, k)
     if nws == 0:
         raise ValueError(f"conv3d_wgrad: unsupported shape {tuple(x.shape)} -> {cout}, k={k}")
     ws = torch.empty(nws // 4, device=x.device, dtype=torch.float32)
     dw = torch.empty((cout, cin, k, k, k), device=x.device, dtype=torch.float32)
-    check(lib.lea_conv3d_wgrad(x.data_ptr(), dz.data_ptr(), dw.data_ptr(), ws.data_ptr(), nws, b, cin, cout,
-                               d, h, w, k, _stream()), "lea_conv3d_wgrad")
+    _launch("lea_conv3d_wgrad", x.data_ptr(), dz.data_ptr(), dw.data_ptr(), ws.data_ptr(), nws, b, cin, cout, d, h,
+            w, k)
     return dw
 
 
 def _bn_workspace(c, device):
     n = _lib.load().lea_bn_workspace_bytes(c)
     return torch.empty((n + 7) // 8, device=device, dtype=torch.float64)
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
 
 
 def _conv(x: torch.Tensor, w: torch.Tensor, relu: bool = False) -> torch.Tensor:
@@ -92,14 +82,12 @@ def conv2d_wgrad(x: torch.Tensor, dz: torch.Tensor) -> torch.Tensor:
     x, dz = x.contiguous(), dz.contiguous()
     b, cin, _, h, w = x.shape
     cout = dz.shape[1]
-    lib = _lib.load()
-    nws = lib.lea_conv2d_wgrad_workspace_bytes(b, cin, cout, h, w)
+    nws = _lib.load().lea_conv2d_wgrad_workspace_bytes(b, cin, cout, h, w)
     if nws == 0:
         raise ValueError(f"conv2d_wgrad: unsupported shape {tuple(x.shape)} -> {cout}")
     ws = torch.empty(nws // 4, device=x.device, dtype=torch.float32)
     dw = torch.empty((cout, cin, 3, 3), device=x.device, dtype=torch.float32)
-    check(lib.lea_conv2d_wgrad(x.data_ptr(), dz.data_ptr(), dw.data_ptr(), ws.data_ptr(), nws, b, cin, cout, h, w,
-                               _stream()), "lea_conv2d_wgrad")
+    _launch("lea_conv2d_wgrad", x.data_ptr(), dz.data_ptr(), dw.data_ptr(), ws.data_ptr(), nws, b, cin, cout, h, w)
     return dw
 
 
@@ -110,18 +98,16 @@ def conv2d_s3_backward(x: torch.Tensor, dz: torch.Tensor, w: torch.Tensor, need_
     x, dz, w = x.contiguous(), dz.contiguous(), w.detach().contiguous()
     b, cin, _, hi, wi = x.shape
     cout = w.shape[0]
-    lib = _lib.load()
     dx = dw = None
     if need_dx:
         dx = torch.empty_like(x)
-        check(lib.lea_conv2d_s3_backward_data(dz.data_ptr(), w.data_ptr(), dx.data_ptr(), b, cin, cout, hi, wi,
-                                              _stream()), "lea_conv2d_s3_backward_data")
+        _launch("lea_conv2d_s3_backward_data", dz.data_ptr(), w.data_ptr(), dx.data_ptr(), b, cin, cout, hi, wi)
     if need_dw:
-        nws = lib.lea_conv2d_s3_wgrad_workspace_bytes(b, cin, cout, hi, wi)
+        nws = _lib.load().lea_conv2d_s3_wgrad_workspace_bytes(b, cin, cout, hi, wi)
         ws = torch.empty(nws // 4, device=x.device, dtype=torch.float32)
         dw = torch.empty((cout, cin, 3, 3), device=x.device, dtype=torch.float32)
-        check(lib.lea_conv2d_s3_wgrad(x.data_ptr(), dz.data_ptr(), dw.data_ptr(), ws.data_ptr(), nws, b, cin, cout,
-                                      hi, wi, _stream()), "lea_conv2d_s3_wgrad")
+        _launch("lea_conv2d_s3_wgrad", x.data_ptr(), dz.data_ptr(), dw.data_ptr(), ws.data_ptr(), nws, b, cin, cout,
+                hi, wi)
     return dx, dw
 
 
@@ -165,16 +151,14 @@ class _ConvBRFn(torch.autograd.Function):
             raise ValueError(f"ConvBR: weight {tuple(weight.shape)} does not take {cin} channels")
         z = _conv_forward(kind, x, weight, relu=not use_bn and relu)
         v = z.shape[2] * z.shape[3] * z.shape[4]
-        lib = _lib.load()
         if use_bn:
             y = torch.empty_like(z)
             mean = torch.empty(cout, device=x.device, dtype=torch.float32)
             invstd = torch.empty_like(mean)
             ws = _bn_workspace(cout, x.device)
-            check(lib.lea_bn_forward_f32(z.data_ptr(), y.data_ptr(), b, cout, v, _ptr(gamma), _ptr(beta),
-                                         _ptr(running_mean), _ptr(running_var), float(momentum), float(eps),
-                                         1 if training else 0, LEA_RELU if relu else 0, mean.data_ptr(),
-                                         invstd.data_ptr(), ws.data_ptr(), _stream()), "lea_bn_forward_f32")
+            _launch("lea_bn_forward_f32", z.data_ptr(), y.data_ptr(), b, cout, v, _ptr(gamma), _ptr(beta),
+                    _ptr(running_mean), _ptr(running_var), float(momentum), float(eps), 1 if training else 0,
+                    _flags(relu), mean.data_ptr(), invstd.data_ptr(), ws.data_ptr())
         else:
             y = z
             mean = torch.zeros(cout, device=x.device, dtype=torch.float32)
@@ -195,11 +179,9 @@ class _ConvBRFn(torch.autograd.Function):
         dbeta = torch.empty_like(dgamma) if need_g else None
         dz = torch.empty_like(dy)
         ws = _bn_workspace(cout, dy.device)
-        check(_lib.load().lea_bn_backward_f32(
-            dy.data_ptr(), y.data_ptr(), z.data_ptr(), dz.data_ptr(), b, cout, v,
-            _ptr(gamma) if use_bn else None, mean.data_ptr(), invstd.data_ptr(), 1 if train else 0,
-            LEA_RELU if relu else 0, _ptr(dgamma), _ptr(dbeta), ws.data_ptr(), _stream()),
-            "lea_bn_backward_f32")
+        _launch("lea_bn_backward_f32", dy.data_ptr(), y.data_ptr(), z.data_ptr(), dz.data_ptr(), b, cout, v,
+                _ptr(gamma) if use_bn else None, mean.data_ptr(), invstd.data_ptr(), 1 if train else 0,
+                _flags(relu), _ptr(dgamma), _ptr(dbeta), ws.data_ptr())
         dx, dw = _conv_backward(kind, x, weight, dz, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
         return (dx, dw, dgamma if ctx.needs_input_grad[2] else None,
                 dbeta if ctx.needs_input_grad[3] else None) + (None,) * 8
@@ -215,15 +197,13 @@ def resample3d_backward(dy: torch.Tensor, in_size, align_corners: bool = True) -
     dy = dy.contiguous()
     b, c, do, ho, wo = dy.shape
     di, hi, wi = (int(s) for s in in_size)
-    lib = _lib.load()
-    nws = lib.lea_resample3d_backward_workspace_bytes(b, c, di, hi, wi, do, ho, wo)
+    nws = _lib.load().lea_resample3d_backward_workspace_bytes(b, c, di, hi, wi, do, ho, wo)
     if nws == 0:
         raise ValueError(f"resample3d_backward: bad shape {tuple(dy.shape)} <- {tuple(in_size)}")
     ws = torch.empty(nws // 4, device=dy.device, dtype=torch.float32)
     dx = torch.empty((b, c, di, hi, wi), device=dy.device, dtype=torch.float32)
-    check(lib.lea_resample3d_trilinear_backward(dy.data_ptr(), dx.data_ptr(), ws.data_ptr(), nws, b, c, di, hi,
-                                                wi, do, ho, wo, 1 if align_corners else 0, _stream()),
-          "lea_resample3d_trilinear_backward")
+    _launch("lea_resample3d_trilinear_backward", dy.data_ptr(), dx.data_ptr(), ws.data_ptr(), nws, b, c, di, hi, wi,
+            do, ho, wo, 1 if align_corners else 0)
     return dx
 
 
@@ -259,9 +239,8 @@ class _DisparityFn(torch.autograd.Function):
         b, _, d3, h3, w3 = cost.shape
         # dU transposed along D in the kernel (never materialised over maxdisp planes)
         dv = torch.empty((b, 1, d3, 3 * h3, 3 * w3), device=cost.device, dtype=torch.float32)
-        check(_lib.load().lea_disparity_regression_backward(
-            cost.data_ptr(), disp.data_ptr(), dout.contiguous().data_ptr(), dv.data_ptr(), b, d3, h3, w3,
-            ctx.maxdisp, _stream()), "lea_disparity_regression_backward")
+        _launch("lea_disparity_regression_backward", cost.data_ptr(), disp.data_ptr(),
+                dout.contiguous().data_ptr(), dv.data_ptr(), b, d3, h3, w3, ctx.maxdisp)
         return resample3d_backward(dv, (d3, h3, w3), align_corners=False), None
 
 
@@ -283,9 +262,8 @@ class _CostVolumeFn(torch.autograd.Function):
         dcost = dcost.contiguous()
         dl = torch.empty(ctx.shape, device=dcost.device, dtype=torch.float32)
         dr = torch.empty_like(dl)
-        check(_lib.load().lea_build_cost_volume_backward(dcost.data_ptr(), dl.data_ptr(), dr.data_ptr(), b, c, h,
-                                                         w, dcost.shape[2], _stream()),
-              "lea_build_cost_volume_backward")
+        _launch("lea_build_cost_volume_backward", dcost.data_ptr(), dl.data_ptr(), dr.data_ptr(), b, c, h, w,
+                dcost.shape[2])
         return dl, dr, None
 
 
