@@ -87,6 +87,23 @@ int lea_conv3d_bnrelu(const void* x, int64_t x_bstride,
                       int B, int cin, int cout, int D, int H, int W, int k,
                       unsigned flags, int dtype, void* stream);
 
+/* Two 1x1x1 ConvBR3d of the same input in one pass over it (a matching cell's `preprocess`
+ * and the next cell's `pre_preprocess` read the same tensor, skip_model_3d.py:52-53,75):
+ * w_packed is lea_conv3d_pack_weights (k = 1) of the two weights stacked along cout, head A's
+ * [cout_a, cin] first.  Head A writes y_a [B, cout_a, D, H, W], head B y_b [B, cout_b, D, H, W],
+ * each with its own batch stride, folded BN (both NULL = none) and flags (LEA_RELU only:
+ * neither head takes a residual; LEA_RESIDUAL is LEA_E_INVALID).  x / x2 / cin2 as for
+ * lea_conv3d_bnrelu.  Each head is bit-identical to its own lea_conv3d_bnrelu (k = 1) launch. */
+int lea_conv1x1_heads(const void* x, int64_t x_bstride, const void* x2, int64_t x2_bstride,
+                      int cin2, const float* w_packed,
+                      const float* scale_a, const float* shift_a, void* y_a, int64_t ya_bstride,
+                      int cout_a, unsigned flags_a,
+                      const float* scale_b, const float* shift_b, void* y_b, int64_t yb_bstride,
+                      int cout_b, unsigned flags_b,
+                      int B, int cin, int D, int H, int W, int dtype, void* stream);
+/* Kernel instantiation lea_conv1x1_heads launches (cout = cout_a + cout_b). */
+const char* lea_conv1x1_heads_kernel_name(int B, int cout, int D, int H, int W);
+
 /* ConvBR3d of a trilinearly resampled input: conv(interp(x, [D, H, W],
  * align_corners=True)) with the interpolation done while staging, so the
  * resampled volume never reaches HBM.  Replaces the F.interpolate + ConvBR pairs
@@ -810,12 +827,37 @@ int lea_cv_stem_combine(const void* lmaps, int64_t l_bstride, const void* rmaps,
  * W % 4 == 0 and every plane of a row pair in one workgroup's LDS (D3 <= 224); anything
  * else is LEA_E_UNSUPPORTED (the caller runs lea_cv_stem_combine and resamples).  y needs
  * 16-byte and y2 8-byte alignment (batch strides included) and they must not overlap
- * (LEA_E_INVALID).  flags: LEA_RELU only. */
+ * (LEA_E_INVALID).  flags: LEA_RELU (and LEA_CVS_TMAJOR, below) only. */
 int lea_cv_stem_down2_supported(int cout, int D3, int H, int W, int dtype);
 int lea_cv_stem_combine_down2(const void* lmaps, int64_t l_bstride, const void* rmaps, int64_t r_bstride,
                               const float* scale, const float* shift, void* y, int64_t y_bstride,
                               void* y2, int64_t y2_bstride, int B, int cout, int D3, int H, int W,
                               unsigned flags, int dtype, void* stream);
+
+/* The f32 combine kernels read the masked left maps (t = 1, 2) and the K2 maps on a few
+ * columns only, so those need not be computed elsewhere:
+ *   LEA_CVS_TMAJOR (a flag of lea_cv_stem_combine and lea_cv_stem_combine_down2, LEA_F32):
+ *     lmaps in the order (3 t + kd) cout + o -- the three full-width maps first, the six
+ *     masked ones after them (rmaps are grouped already: Bk, then K2);
+ *   lea_cv_stem_map_windows: the columns read -- left[0..1] = [begin, end) of the masked left
+ *     maps, right[0..3] = the two [begin, end) of the K2 maps (derivation: csrc/cv_stem.hip);
+ *   lea_conv2d_bnrelu_windowed: lea_conv2d_bnrelu (the direct engine's 2D tiles, no residual)
+ *     that computes output channels [0, split) on every column and channels [split, cout) on
+ *     the columns of up to two windows [w1_begin, w1_end), [w2_begin, w2_end) (the second
+ *     empty when w2_begin >= w2_end; w1_end <= w2_begin), rounded outward to the 16-column
+ *     tiles (lea_conv2d_windowed_tiles: tiles[0..3] = the windows in tile columns, as run;
+ *     rounded windows that touch are one).  No workgroup exists for the other columns and
+ *     nothing is written there.  w_packed: lea_conv2d_pack_weights of weight rows [0, split)
+ *     followed by that of rows [split, cout) (only the latter when split = 0).  Where
+ *     computed, a value is bit-identical to lea_conv2d_bnrelu's on the same engine. */
+#define LEA_CVS_TMAJOR 8u
+int lea_cv_stem_map_windows(int D3, int W, int* left, int* right);
+int lea_conv2d_windowed_tiles(int W, int w1_begin, int w1_end, int w2_begin, int w2_end, int* tiles);
+int lea_conv2d_bnrelu_windowed(const void* x, int64_t x_bstride, const float* w_packed,
+                               const float* scale, const float* shift, void* y, int64_t y_bstride,
+                               int B, int cin, int cout, int split, int H, int W, int w1_begin,
+                               int w1_end, int w2_begin, int w2_end, unsigned flags, int dtype,
+                               void* stream);
 
 /* ---- host steps either side of forward ---- */
 

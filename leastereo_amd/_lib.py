@@ -18,6 +18,7 @@ LEA_BF16 = 1
 LEA_RELU = 1
 LEA_RESIDUAL = 2
 LEA_PAIR_SUM = 4
+LEA_CVS_TMAJOR = 8
 LEA_E_INVALID = 1001
 
 _p = ctypes.c_void_p
@@ -35,6 +36,9 @@ SIGNATURES = {
     "lea_conv3d_pack_weights": (_i, [_p, _p, _i, _i, _i, _p]),
     "lea_conv3d_bnrelu": (_i, [_p, _i64, _p, _i64, _i, _p, _p, _p, _p, _i64, _p, _i64,
                                _i, _i, _i, _i, _i, _i, _i, _u, _i, _p]),
+    "lea_conv1x1_heads": (_i, [_p, _i64, _p, _i64, _i, _p, _p, _p, _p, _i64, _i, _u, _p, _p, _p, _i64, _i, _u,
+                               _i, _i, _i, _i, _i, _i, _p]),
+    "lea_conv1x1_heads_kernel_name": (ctypes.c_char_p, [_i, _i, _i, _i, _i]),
     "lea_conv3d_bnrelu_resampled": (_i, [_p, _i64, _i, _i, _i, _p, _p, _p, _p, _i64, _p, _i64,
                                          _i, _i, _i, _i, _i, _i, _i, _u, _i, _p]),
     "lea_conv3d_kernel_name": (ctypes.c_char_p, [_i, _i, _i, _i, _i, _i, _i]),
@@ -166,6 +170,10 @@ SIGNATURES = {
     "lea_cv_stem_split_weights": (_i, [_p, _p, _p, _i, _i, _p]),
     "lea_cv_stem_combine": (_i, [_p, _i64, _p, _i64, _p, _p, _p, _i64, _i, _i, _i, _i, _i, _u, _i,
                                  _p]),
+    "lea_cv_stem_map_windows": (_i, [_i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
+    "lea_conv2d_windowed_tiles": (_i, [_i, _i, _i, _i, _i, ctypes.POINTER(_i)]),
+    "lea_conv2d_bnrelu_windowed": (_i, [_p, _i64, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
+                                        _u, _i, _p]),
     "lea_cv_stem_down2_supported": (_i, [_i, _i, _i, _i, _i]),
     "lea_cv_stem_combine_down2": (_i, [_p, _i64, _p, _i64, _p, _p, _p, _i64, _p, _i64, _i, _i, _i, _i, _i,
                                        _u, _i, _p]),

@@ -231,8 +231,23 @@ __global__ __launch_bounds__(256) void conv1x1_rs_f32_kernel(const ConvArgs a, i
 // NT-float vectors -- 16 lanes cover 64 NT contiguous bytes per instruction instead of 64
 // (host: every base, batch stride and D*H*W a multiple of NT floats).  Each output's k-step
 // sequence is unchanged: bit-identical.
-template <int MT, int NT, bool VEC>
-__global__ __launch_bounds__(kConvThreads) void conv1x1_kernel(const ConvArgs a) {
+//
+// Two heads (TWO, lea_conv1x1_heads): the packed weights are two 1x1 convs of the same input
+// stacked along cout; couts [0, hb.c0) are head A (a.y, a.scale/shift, a.flags), the rest
+// head B with its own output, batch stride, scale/shift (either head's may be null) and
+// ReLU flag, written as channel co - hb.c0.  Neither head takes a residual.  One read of x
+// for both; each output's k-steps are those of its own single launch: bit-identical.
+struct Conv1x1HeadB {
+  float* y;
+  long long ybs;
+  const float* scale;
+  const float* shift;
+  int c0;
+  unsigned flags;
+};
+
+template <int MT, int NT, bool VEC, bool TWO>
+__device__ __forceinline__ void conv1x1_body(const ConvArgs& a, const Conv1x1HeadB& hb) {
   using P = PackCfg<1, MT>;
   constexpr int CIN_B = P::CIN_B;
   constexpr int KS = CIN_B / 4;
@@ -298,16 +313,27 @@ __global__ __launch_bounds__(kConvThreads) void conv1x1_kernel(const ConvArgs a)
     }
   }
 
-  const bool relu = a.flags & LEA_RELU;
-  const bool resid = a.flags & LEA_RESIDUAL;
+  const bool resid = !TWO && (a.flags & LEA_RESIDUAL);
 #pragma unroll
   for (int m = 0; m < MT; ++m) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int co = co0 + m * 16 + kq * 4 + r;
+      int co = co0 + m * 16 + kq * 4 + r;
       if (co >= a.cout) continue;
-      const float sc = a.scale ? a.scale[co] : 1.f;
-      const float sh = a.shift ? a.shift[co] : 0.f;
+      // this output channel's head: destination, folded BN, ReLU, channel inside the head
+      float* y = a.y + (long long)b * a.ybs;
+      const float* scale = a.scale;
+      const float* shift = a.shift;
+      bool relu = a.flags & LEA_RELU;
+      if (TWO && co >= hb.c0) {
+        y = hb.y + (long long)b * hb.ybs;
+        scale = hb.scale;
+        shift = hb.shift;
+        relu = hb.flags & LEA_RELU;
+        co -= hb.c0;
+      }
+      const float sc = scale ? scale[co] : 1.f;
+      const float sh = shift ? shift[co] : 0.f;
       if (VEC && full) {
         const long long o = (long long)co * V + vox(0);
         vecf val;
@@ -321,7 +347,7 @@ __global__ __launch_bounds__(kConvThreads) void conv1x1_kernel(const ConvArgs a)
 #pragma unroll
           for (int j = 0; j < NT; ++j) val[j] += rv[j];
         }
-        *reinterpret_cast<vecf*>(a.y + (long long)b * a.ybs + o) = val;
+        *reinterpret_cast<vecf*>(y + o) = val;
         continue;
       }
 #pragma unroll
@@ -332,10 +358,20 @@ __global__ __launch_bounds__(kConvThreads) void conv1x1_kernel(const ConvArgs a)
         float val = acc[m][j][r] * sc + sh;
         if (relu) val = fmaxf(val, 0.f);
         if (resid) val += a.res[(long long)b * a.rbs + o];
-        a.y[(long long)b * a.ybs + o] = val;
+        y[o] = val;
       }
     }
   }
+}
+
+template <int MT, int NT, bool VEC>
+__global__ __launch_bounds__(kConvThreads) void conv1x1_kernel(const ConvArgs a) {
+  conv1x1_body<MT, NT, VEC, false>(a, Conv1x1HeadB{});
+}
+
+template <int MT, int NT, bool VEC>
+__global__ __launch_bounds__(kConvThreads) void conv1x1_heads_kernel(const ConvArgs a, const Conv1x1HeadB hb) {
+  conv1x1_body<MT, NT, VEC, true>(a, hb);
 }
 
 // ------------------------------------------------- VALU engine for cout <= 2 (k=3)
@@ -655,8 +691,9 @@ int run_rs(const ConvArgs& a, int tw, int B, hipStream_t st) {
 
 int g_1x1_vec = 1;  // lea_conv1x1_set_vector: the NT-float vector form of conv1x1_kernel
 
+// hb: the second head of lea_conv1x1_heads (null: the single-output kernel)
 template <int MT, int NT>
-int launch_1x1(const ConvArgs& a, int B, hipStream_t st) {
+int launch_1x1(const ConvArgs& a, int B, hipStream_t st, const Conv1x1HeadB* hb = nullptr) {
   const long long vox = (long long)a.D * a.H * a.W;
   const long long per = kConvWaves * NT * 16;
   const long long gx = (vox + per - 1) / per;
@@ -664,17 +701,24 @@ int launch_1x1(const ConvArgs& a, int B, hipStream_t st) {
   // the vector form needs every per-channel and per-batch base on an NT-float boundary
   auto al = [](const void* q) { return q == nullptr || ((uintptr_t)q % (NT * 4)) == 0; };
   const bool vec = g_1x1_vec && vox % NT == 0 && al(a.x) && al(a.x2) && al(a.y) && al(a.res) &&
-                   a.xbs % NT == 0 && a.x2bs % NT == 0 && a.ybs % NT == 0 && a.rbs % NT == 0;
-  if (vec) conv1x1_kernel<MT, NT, true><<<dim3((unsigned)gx, B * a.ncob), kConvThreads, 0, st>>>(a);
-  else conv1x1_kernel<MT, NT, false><<<dim3((unsigned)gx, B * a.ncob), kConvThreads, 0, st>>>(a);
+                   a.xbs % NT == 0 && a.x2bs % NT == 0 && a.ybs % NT == 0 && a.rbs % NT == 0 &&
+                   (hb == nullptr || (al(hb->y) && hb->ybs % NT == 0));
+  const dim3 grid((unsigned)gx, B * a.ncob);
+  if (hb != nullptr) {
+    if (vec) conv1x1_heads_kernel<MT, NT, true><<<grid, kConvThreads, 0, st>>>(a, *hb);
+    else conv1x1_heads_kernel<MT, NT, false><<<grid, kConvThreads, 0, st>>>(a, *hb);
+    return launch_status("lea_conv1x1_heads");
+  }
+  if (vec) conv1x1_kernel<MT, NT, true><<<grid, kConvThreads, 0, st>>>(a);
+  else conv1x1_kernel<MT, NT, false><<<grid, kConvThreads, 0, st>>>(a);
   return launch_status("lea_conv3d");
 }
 
-int run_1x1(const Plan& p, const ConvArgs& a, int B, hipStream_t st) {
-  if (p.mt == 1) return p.nt == 4 ? launch_1x1<1, 4>(a, B, st) : launch_1x1<1, 2>(a, B, st);
-  if (p.mt == 2) return p.nt == 4 ? launch_1x1<2, 4>(a, B, st) : launch_1x1<2, 2>(a, B, st);
-  if (p.mt == 3) return p.nt == 4 ? launch_1x1<3, 4>(a, B, st) : launch_1x1<3, 2>(a, B, st);
-  return p.nt == 4 ? launch_1x1<4, 4>(a, B, st) : launch_1x1<4, 2>(a, B, st);
+int run_1x1(const Plan& p, const ConvArgs& a, int B, hipStream_t st, const Conv1x1HeadB* hb = nullptr) {
+  if (p.mt == 1) return p.nt == 4 ? launch_1x1<1, 4>(a, B, st, hb) : launch_1x1<1, 2>(a, B, st, hb);
+  if (p.mt == 2) return p.nt == 4 ? launch_1x1<2, 4>(a, B, st, hb) : launch_1x1<2, 2>(a, B, st, hb);
+  if (p.mt == 3) return p.nt == 4 ? launch_1x1<3, 4>(a, B, st, hb) : launch_1x1<3, 2>(a, B, st, hb);
+  return p.nt == 4 ? launch_1x1<4, 4>(a, B, st, hb) : launch_1x1<4, 2>(a, B, st, hb);
 }
 
 template <int MT>
@@ -904,6 +948,66 @@ extern "C" int lea_conv3d_bnrelu(const void* x, int64_t x_bstride, const void* x
   return lea::conv_common(a, B, k, false, dtype, stream);
 }
 
+extern "C" const char* lea_conv1x1_heads_kernel_name(int B, int cout, int D, int H, int W) {
+  if (B <= 0 || cout <= 0 || D <= 0 || H <= 0 || W <= 0) return nullptr;
+  const lea::Plan p = lea::make_plan(B, cout, D, H, W, 1, false);
+  snprintf(lea::g_name, sizeof(lea::g_name), "conv1x1_heads_kernel<%d, %d>", p.mt, p.nt);
+  return lea::g_name;
+}
+
+extern "C" int lea_conv1x1_heads(const void* x, int64_t x_bstride, const void* x2, int64_t x2_bstride,
+                                 int cin2, const float* w_packed, const float* scale_a,
+                                 const float* shift_a, void* y_a, int64_t ya_bstride, int cout_a,
+                                 unsigned flags_a, const float* scale_b, const float* shift_b, void* y_b,
+                                 int64_t yb_bstride, int cout_b, unsigned flags_b, int B, int cin, int D,
+                                 int H, int W, int dtype, void* stream) {
+  using namespace lea;
+  clear_error();
+  // neither head has a residual (or accumulating) form
+  LEA_CHECK_FLAGS(flags_a, LEA_RELU, "lea_conv1x1_heads");
+  LEA_CHECK_FLAGS(flags_b, LEA_RELU, "lea_conv1x1_heads");
+  LEA_CHECK_ARG(x && w_packed && y_a && y_b, "lea_conv1x1_heads: null pointer");
+  LEA_CHECK_ARG((scale_a == nullptr) == (shift_a == nullptr) && (scale_b == nullptr) == (shift_b == nullptr),
+                "lea_conv1x1_heads: a head's scale/shift must both be set or both NULL");
+  LEA_CHECK_ARG(B > 0 && cin > 0 && cout_a > 0 && cout_b > 0 && D > 0 && H > 0 && W > 0,
+                "lea_conv1x1_heads: bad shape B=%d cin=%d cout=%d+%d D=%d H=%d W=%d", B, cin, cout_a, cout_b,
+                D, H, W);
+  LEA_CHECK_ARG(cin2 >= 0 && cin2 <= cin && (cin2 == 0 || x2), "lea_conv1x1_heads: bad channel split %d/%d",
+                cin - cin2, cin);
+  const long long vox = (long long)D * H * W;
+  LEA_CHECK_ARG(vox * 4 < (1LL << 32) && (long long)(cout_a + cout_b + 63) * vox < (1LL << 31),
+                "lea_conv1x1_heads: volume too large");
+  LEA_CHECK_ARG(x != y_a && x != y_b && (x2 == nullptr || (x2 != y_a && x2 != y_b)),
+                "lea_conv1x1_heads: input aliases an output");
+  LEA_CHECK_ARG(!spans_overlap(y_a, (size_t)cout_a * vox * 4, y_b, (size_t)cout_b * vox * 4),
+                "lea_conv1x1_heads: the heads' outputs overlap");
+  if (dtype != LEA_F32) {
+    set_error("lea_conv1x1_heads: dtype %d unsupported", dtype);
+    return LEA_E_UNSUPPORTED;
+  }
+  ConvArgs a{};
+  a.x = (const float*)x;
+  a.xbs = x_bstride;
+  a.x2 = (const float*)x2;
+  a.x2bs = x2_bstride;
+  a.cin1 = cin - cin2;
+  a.wp = w_packed;
+  a.scale = scale_a;
+  a.shift = shift_a;
+  a.y = (float*)y_a;
+  a.ybs = ya_bstride;
+  a.cin = cin;
+  a.cout = cout_a + cout_b;
+  a.D = D;
+  a.H = H;
+  a.W = W;
+  a.flags = flags_a;
+  const Conv1x1HeadB hb{(float*)y_b, yb_bstride, scale_b, shift_b, cout_a, flags_b};
+  const Plan p = make_plan(B, a.cout, D, H, W, 1, false);
+  a.ncob = (a.cout + p.mt * 16 - 1) / (p.mt * 16);
+  return run_1x1(p, a, B, as_stream(stream), &hb);
+}
+
 extern "C" size_t lea_conv2d_packed_floats(int cout, int cin) {
   if (cout <= 0 || cin <= 0) return 0;
   return lea::packed_floats_2d(cout, cin);
@@ -981,6 +1085,100 @@ extern "C" int lea_conv2d_bnrelu(const void* x, int64_t x_bstride, const float* 
     case 3: return run_dma2d_mt3(p, a, B, st);
     default: return run_dma2d_mt4(p, a, B, st);
   }
+}
+
+namespace lea {
+
+// one channel group of lea_conv2d_bnrelu_windowed on the direct engine's 2D tiles
+int run_dma2d(ConvArgs a, int B, hipStream_t st) {
+  const Plan p = make_plan_2d(B, a.cout, a.H, a.W);
+  a.ncob = (a.cout + p.mt * 16 - 1) / (p.mt * 16);
+  switch (p.mt) {
+    case 1: return run_dma2d_mt1(p, a, B, st);
+    case 2: return run_dma2d_mt2(p, a, B, st);
+    case 3: return run_dma2d_mt3(p, a, B, st);
+    default: return run_dma2d_mt4(p, a, B, st);
+  }
+}
+
+constexpr int kWinTile = 16;  // the 2D tiles' width (make_plan_2d): windows round outward to it
+
+}  // namespace lea
+
+extern "C" int lea_conv2d_windowed_tiles(int W, int w1_begin, int w1_end, int w2_begin, int w2_end,
+                                         int* tiles) {
+  using namespace lea;
+  clear_error();
+  LEA_CHECK_ARG(tiles && W > 0 && 0 <= w1_begin && w1_begin < w1_end && w1_end <= W,
+                "lea_conv2d_windowed: bad first window [%d, %d) of %d columns", w1_begin, w1_end, W);
+  const bool two = w2_begin < w2_end;
+  LEA_CHECK_ARG(!two || (w1_end <= w2_begin && w2_end <= W),
+                "lea_conv2d_windowed: bad second window [%d, %d) after [%d, %d) of %d columns", w2_begin,
+                w2_end, w1_begin, w1_end, W);
+  const int all = (W + kWinTile - 1) / kWinTile;
+  tiles[0] = w1_begin / kWinTile;
+  tiles[1] = (w1_end + kWinTile - 1) / kWinTile;
+  tiles[2] = two ? w2_begin / kWinTile : all;
+  tiles[3] = two ? (w2_end + kWinTile - 1) / kWinTile : all;
+  if (tiles[2] <= tiles[1]) {  // the rounded windows touch: one window
+    tiles[1] = std::max(tiles[1], tiles[3]);
+    tiles[2] = tiles[3] = all;
+  }
+  return LEA_OK;
+}
+
+extern "C" int lea_conv2d_bnrelu_windowed(const void* x, int64_t x_bstride, const float* w_packed,
+                                          const float* scale, const float* shift, void* y,
+                                          int64_t y_bstride, int B, int cin, int cout, int split, int H,
+                                          int W, int w1_begin, int w1_end, int w2_begin, int w2_end,
+                                          unsigned flags, int dtype, void* stream) {
+  using namespace lea;
+  clear_error();
+  LEA_CHECK_FLAGS(flags, LEA_RELU, "lea_conv2d_bnrelu_windowed");
+  LEA_CHECK_ARG(x && w_packed && y && x != y, "lea_conv2d_bnrelu_windowed: null or aliased pointer");
+  LEA_CHECK_ARG((scale == nullptr) == (shift == nullptr),
+                "lea_conv2d_bnrelu_windowed: scale/shift must both be set or both NULL");
+  LEA_CHECK_ARG(B > 0 && cin > 0 && cout > 0 && H > 0 && W > 0 && split >= 0 && split < cout,
+                "lea_conv2d_bnrelu_windowed: bad shape B=%d cin=%d cout=%d split=%d H=%d W=%d", B, cin, cout,
+                split, H, W);
+  LEA_CHECK_ARG((long long)(cout + 63) * H * W < (1LL << 31), "lea_conv2d_bnrelu_windowed: plane too large");
+  int t[4];
+  if (const int rc = lea_conv2d_windowed_tiles(W, w1_begin, w1_end, w2_begin, w2_end, t)) return rc;
+  if (dtype != LEA_F32) {
+    set_error("lea_conv2d_bnrelu_windowed: dtype %d unsupported", dtype);
+    return LEA_E_UNSUPPORTED;
+  }
+  ConvArgs a{};
+  a.x = (const float*)x;
+  a.xbs = x_bstride;
+  a.cin1 = cin;
+  a.cin = cin;
+  a.ybs = y_bstride;
+  a.D = 1;
+  a.H = H;
+  a.W = W;
+  a.flags = flags;
+  hipStream_t st = as_stream(stream);
+  if (split > 0) {  // channels [0, split): every column
+    a.wp = w_packed;
+    a.scale = scale;
+    a.shift = shift;
+    a.y = (float*)y;
+    a.cout = split;
+    if (const int rc = run_dma2d(a, B, st)) return rc;
+  }
+  // channels [split, cout): the windows' tile columns only, as a compact grid
+  a.wp = w_packed + (split > 0 ? packed_floats_2d(split, cin) : 0);
+  a.scale = scale ? scale + split : nullptr;
+  a.shift = shift ? shift + split : nullptr;
+  a.y = (float*)y + (long long)split * H * W;
+  a.cout = cout - split;
+  a.wn1 = t[1] - t[0];
+  a.wt1 = t[0];
+  a.wt2 = t[2];
+  a.wtiles = a.wn1 + (t[3] - t[2]);
+  if (a.wtiles == (W + kWinTile - 1) / kWinTile) a.wtiles = a.wn1 = a.wt1 = a.wt2 = 0;  // every column
+  return run_dma2d(a, B, st);
 }
 
 extern "C" const char* lea_conv3d_costvolume_kernel_name(int B, int cout, int D3, int H, int W) {

@@ -82,6 +82,10 @@ struct ConvArgs {
   int csplit;
   long long uoff;          // F(2,3) x F(2,3) tile (conv3d_wino22.hip): U section of the packed weights
   int grp;                 // F(4,3) x F(4,3) tile: block order (0 = linear; g = groups of g x g tiles)
+  // DMA engine, column windows (lea_conv2d_bnrelu_windowed): the grid holds wtiles tile columns
+  // (0 = all of them) -- the first wn1 are tile columns wt1 .., the rest wt2 ..; no workgroup
+  // exists for the others.  All zero = every column (column c of the grid is tile column c).
+  int wtiles, wn1, wt1, wt2;
 };
 
 // KD = kernel depth: KS for the 3D convs, 1 for the feature net's 2D 3x3 convs
@@ -367,7 +371,8 @@ __global__ __launch_bounds__(kConvThreads, 2) void conv3d_dma_kernel(const ConvA
   const int tile = (lin / a.ndz) % a.ntiles;
   const int bc = lin / (a.ndz * a.ntiles);
   const int h0 = (tile / a.tiles_w) * C::TH;
-  const int w0 = (tile % a.tiles_w) * TW;
+  const int tc = tile % a.tiles_w;  // grid column -> tile column (the windowed launches skip some)
+  const int w0 = (tc < a.wn1 ? a.wt1 + tc : a.wt2 + tc - a.wn1) * TW;
   const int d0 = dz * DSTEP;
   const int b = bc / a.ncob;
   const int co0 = (bc - b * a.ncob) * C::COP;
@@ -491,7 +496,7 @@ struct Plan {
 template <typename K>
 int launch_dma(K kernel, const ConvArgs& a0, int th, int tw, int td, int B, hipStream_t st) {
   ConvArgs a = a0;
-  a.tiles_w = (a.W + tw - 1) / tw;
+  a.tiles_w = a.wtiles > 0 ? a.wtiles : (a.W + tw - 1) / tw;
   a.ntiles = a.tiles_w * ((a.H + th - 1) / th);
   a.ndz = (a.D + td - 1) / td;
   const long long n = (long long)a.ntiles * a.ndz * B * a.ncob;

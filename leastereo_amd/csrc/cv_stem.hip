@@ -77,6 +77,13 @@ __device__ __forceinline__ bool plane_valid(int d, int kd, int D) {
   return d + kd - 1 >= 0 && d + kd - 1 < D;
 }
 
+// channel of left map LK[kd][t], cout o: the public order (3 kd + t) cout + o, or with
+// LEA_CVS_TMAJOR (3 t + kd) cout + o -- the unmasked maps (t = 0, read on every column) first,
+// the masked ones after them (f32 kernels)
+__device__ __forceinline__ int lmap_channel(const Args& a, int kd, int t, int o) {
+  return ((a.flags & LEA_CVS_TMAJOR) ? 3 * t + kd : 3 * kd + t) * a.cout + o;
+}
+
 // left half at (d, u) from the lane's nine LK values
 __device__ __forceinline__ float left_sum(const float lk[3][3], int d, int u, int D) {
   float s = 0.f;
@@ -209,7 +216,7 @@ __global__ __launch_bounds__(kThreads) void cv_stem_f32_kernel(const Args a) {
     for (int t = 0; t < 3; ++t) {
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
       if (t == 0 || band)
-        v = *reinterpret_cast<const float4*>(lk + (long long)((3 * kd + t) * a.cout + o) * HW +
+        v = *reinterpret_cast<const float4*>(lk + (long long)lmap_channel(a, kd, t, o) * HW +
                                              (long long)T.h * W + w);
       lkv[kd][t][0] = v.x;
       lkv[kd][t][1] = v.y;
@@ -338,7 +345,7 @@ __global__ __launch_bounds__(kThreads) void cv_stem_f32_down2_kernel(const Args 
       for (int t = 0; t < 3; ++t) {
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (t == 0 || band)
-          v = *reinterpret_cast<const float4*>(lk + (long long)((3 * kd + t) * a.cout + o) * HW +
+          v = *reinterpret_cast<const float4*>(lk + (long long)lmap_channel(a, kd, t, o) * HW +
                                                (long long)(2 * hp + r) * W + w);
         lkv[kd][t][0] = v.x;
         lkv[kd][t][1] = v.y;
@@ -689,8 +696,9 @@ extern "C" int lea_cv_stem_combine(const void* lmaps, int64_t l_bstride, const v
   a.D = D3;
   a.H = H;
   a.W = W;
-  LEA_CHECK_FLAGS(flags, LEA_RELU | 0x300u, "lea_cv_stem_combine");
-  a.flags = flags & (LEA_RELU | 0x300u);  // 0x100 / 0x200: probe-only variants (tools)
+  LEA_CHECK_FLAGS(flags, LEA_RELU | LEA_CVS_TMAJOR | 0x300u, "lea_cv_stem_combine");
+  LEA_CHECK_ARG(!(flags & LEA_CVS_TMAJOR) || dtype == LEA_F32, "lea_cv_stem_combine: LEA_CVS_TMAJOR is f32 only");
+  a.flags = flags & (LEA_RELU | LEA_CVS_TMAJOR | 0x300u);  // 0x100 / 0x200: probe-only variants (tools)
   a.nseg = (W + cvs::WS - 1) / cvs::WS;
   const int ob = dtype == LEA_F32 ? cvs::OB : cvs::OB8;
   // LDS floats: ob (dchunk + 3 WS - 1) sums + ob dchunk corrections
@@ -705,6 +713,28 @@ extern "C" int lea_cv_stem_combine(const void* lmaps, int64_t l_bstride, const v
   else
     cvs::cv_stem_c8_kernel<<<dim3((unsigned)nblk), cvs::kThreads, lds, as_stream(stream)>>>(a);
   return launch_status("lea_cv_stem_combine");
+}
+
+// The columns of the maps that the f32 combine kernels read, from their own conditions:
+//   masked left maps (t = 1, 2): loaded under `band`, w - (d1 - 1) <= 1 with w the first of a
+//     lane's four columns and d1 <= D3, so on columns [0, D3 + 4) at most;
+//   K2 maps: bz_offset reads column 0 (z = -1 or out of range: the value is then discarded by
+//     bz_valid's select), the last-column correction column clamp(W + 1 - d - kd, 0, W - 1)
+//     with 0 <= d < D3, 0 <= kd <= 2, so columns [W - D3, W) and column 0;
+//   the unmasked left maps (t = 0) and the B maps on every column.
+// No load of a masked or K2 map goes to another column (a branch keeps the masked maps'
+// loads to the band; the K2 addresses are the two forms above), so a map buffer filled only
+// there (lea_conv2d_bnrelu_windowed) gives the same output.
+extern "C" int lea_cv_stem_map_windows(int D3, int W, int* left, int* right) {
+  clear_error();
+  LEA_CHECK_ARG(left && right && D3 >= 2 && W > 0, "lea_cv_stem_map_windows: bad arguments D3=%d W=%d", D3, W);
+  left[0] = 0;
+  left[1] = std::min(W, D3 + 4);
+  right[0] = 0;
+  right[1] = 1;
+  right[2] = std::max(W - D3, 1);
+  right[3] = W;
+  return LEA_OK;
 }
 
 // the down-sampling variant's shapes: f32, even D3 / H, W % 4 == 0, the planes of a row pair
@@ -729,7 +759,7 @@ extern "C" int lea_cv_stem_combine_down2(const void* lmaps, int64_t l_bstride, c
                 "lea_cv_stem_combine_down2: scale/shift must both be set or both NULL");
   LEA_CHECK_ARG(B > 0 && cout > 0 && D3 >= 2 && H > 0 && W > 0,
                 "lea_cv_stem_combine_down2: bad shape B=%d cout=%d D3=%d H=%d W=%d", B, cout, D3, H, W);
-  LEA_CHECK_FLAGS(flags, LEA_RELU, "lea_cv_stem_combine_down2");
+  LEA_CHECK_FLAGS(flags, LEA_RELU | LEA_CVS_TMAJOR, "lea_cv_stem_combine_down2");
   if (!cv_stem_down2_ok(cout, D3, H, W, dtype)) {
     set_error("lea_cv_stem_combine_down2: needs f32, even D3 and H, W %% 4 == 0 and unsplit planes "
               "(D3=%d H=%d W=%d dtype=%d)", D3, H, W, dtype);
@@ -757,7 +787,7 @@ extern "C" int lea_cv_stem_combine_down2(const void* lmaps, int64_t l_bstride, c
   a.D = D3;
   a.H = H;
   a.W = W;
-  a.flags = flags & LEA_RELU;
+  a.flags = flags & (LEA_RELU | LEA_CVS_TMAJOR);
   a.rd = axis_ratio(D3, D3 / 2, 1);
   a.rh = axis_ratio(H, H / 2, 1);
   a.rw = axis_ratio(W, W / 2, 1);

@@ -99,6 +99,10 @@ class CellGraphExecutor:
     # size) feeds one stacked 1x1 conv for both cells (the bf16 executors memoise every
     # resample instead); LEASTEREO_SHARE_DOWNSAMPLE=0 keeps two passes
     SHARE_DOWNSAMPLE = os.environ.get("LEASTEREO_SHARE_DOWNSAMPLE", "1") != "0"
+    # where no cell resamples down: cell i's preprocess and cell i + 1's pre_preprocess, two 1x1
+    # convs at the level of the tensor both read, as one two-head launch (lea_conv1x1_heads);
+    # the f32 matching executor only
+    FANOUT_1X1 = False
     # a three-op sibling group of 16-channel 3D ops (the L1 cells: 16 -> 48) as a 32-cout
     # launch on the pipelined W x D kernel plus a 16-cout one (r03: 66 + 43 us vs 124 us on
     # the 1-D 48-row engine); the f32 Winograd matching executor only.  Split as step 0's op
@@ -219,6 +223,62 @@ class CellGraphExecutor:
                         mods[0], torch.cat([m.conv.weight for m in mods], 0),
                         (torch.cat([f[0] for f in folded]).contiguous(),
                          torch.cat([f[1] for f in folded]).contiguous()))
+            # the same pair of readers where cell i does not resample down (no `share`): cell i's
+            # `preprocess` and cell i + 1's `pre_preprocess` both run a 1x1 at the source's own
+            # level -- plain, or the raw conv of the commuted up-sampling (conv()) -- so one
+            # two-head launch reads the source once (cells.{i}.fanout: [this preprocess ; next
+            # pre_preprocess], each head keeping its own folded BN; which form each head takes
+            # is settled from the sizes at run time, _fanout_forms)
+            for i, (cell, nxt) in enumerate(zip(cells, cells[1:])) if self.FANOUT_1X1 else ():
+                wa, wb = cell.preprocess.conv.weight, nxt.pre_preprocess.conv.weight
+                if (f"cells.{i}.share" in self.p or getattr(cell, "dims", 3) != 3
+                        or wa.dim() != 5 or wa.shape[-1] != 1 or wb.shape[-1] != 1 or wa.shape[1] != wb.shape[1]
+                        or cell.downup_sample < 0 or cell.downup_sample + nxt.downup_sample < 0
+                        or wb.shape[1] == nxt.c_out):  # the next cell skips pre_preprocess
+                    continue
+                p = _conv_params(cell.preprocess, torch.cat([wa, wb], 0), (None, None))
+                p.relu = False  # each head's BN / ReLU are its own ConvBR's
+                self.p[f"cells.{i}.fanout"] = p
+
+    def _fanout_takes(self, x):
+        """The two-head 1x1 (lea_conv1x1_heads) is an f32 device kernel."""
+        return x.is_cuda and x.dtype == torch.float32
+
+    def _fanout_forms(self, i, src, size):
+        """For a planned cells.{i}.fanout on a source of volume ``src``: (next cell's size, this
+        head commuted up-sampling?, next head commuted up-sampling?), or None where a head would
+        not run at the source's own level (sizes that round to a down-sampling)."""
+        nxt = self.m.cells[i + 1]
+        sc = {0: None, -1: 0.5, 1: 2}[nxt.downup_sample]
+        nsize = tuple(size) if sc is None else tuple(scale_dimension(n, sc) for n in size)
+        ups = []
+        for s in (tuple(size), nsize):
+            if s != tuple(src) and not all(o >= n for o, n in zip(s, src)):
+                return None
+            ups.append(s != tuple(src))
+        return nsize, ups[0], ups[1]
+
+    def _fanout(self, i, x, size, forms, out, dn_out):
+        """Cell i's s1 preprocess and cell i + 1's s0 pre_preprocess of the same source ``x`` as
+        one two-head launch.  This cell's head goes where conv() puts it (``out``, or the raw z
+        that the up-sampling reads; ``dn_out``: that up-sampling's level-down side output); the
+        next cell's is left in the share memo, keyed by the source and its size.  Returns s1."""
+        nsize, up_a, up_b = forms
+        pa, pb = self.p[f"cells.{i}.preprocess"], self.p[f"cells.{i + 1}.pre_preprocess"]
+        b, src = x.shape[0], self._volume(x)
+        za = self._empty(b, pa.cout, src, x) if up_a or out is None else out
+        zb = self._empty(b, pb.cout, src, x)
+        fold = lambda p, up: (None, None, False) if up else (p.scale, p.shift, p.relu)
+        kernels.conv1x1_heads(x, self.p[f"cells.{i}.fanout"].packed, pa.cout, *fold(pa, up_a),
+                              pb.cout, *fold(pb, up_b), out_a=za, out_b=zb)
+        if up_b:
+            zb = kernels.resample_trilinear(zb, nsize, True, None, pb.scale, pb.shift, pb.relu)
+        self._share_memo = (x, nsize, zb)
+        if not up_a:
+            return za
+        if dn_out is not None:
+            return kernels.resample_trilinear_down2(za, size, out, dn_out, pa.scale, pa.shift, pa.relu)[0]
+        return kernels.resample_trilinear(za, size, True, out, pa.scale, pa.shift, pa.relu)
 
     def conv(self, name, x, out=None, accumulate=False, x2=None, size=None, residual=None, down=None,
              down_only=False):
@@ -391,8 +451,15 @@ class CellGraphExecutor:
             self._share_memo = (prev_input, size, self._channels(big, 0, c))
             s1 = self._channels(big, c, 2 * c)
         else:
-            s1 = self.conv(f"cells.{i}.preprocess", s1, out=slot.get(1), size=size,
-                           **({} if dn is None else {"down": dslot[1]}))
+            forms = None
+            if (self.FANOUT_1X1 and f"cells.{i}.fanout" in self.p and not s1_down
+                    and not isinstance(self, _C8Layout) and self._fanout_takes(s1)):
+                forms = self._fanout_forms(i, self._volume(s1), size)
+            if forms is not None and (dn is None or forms[1]):
+                s1 = self._fanout(i, s1, size, forms, slot.get(1), None if dn is None else dslot[1])
+            else:
+                s1 = self.conv(f"cells.{i}.preprocess", s1, out=slot.get(1), size=size,
+                               **({} if dn is None else {"down": dslot[1]}))
         states = [s0, s1]
         pairs = self.pair_steps.get(i)
         if pairs is not None:
@@ -476,6 +543,12 @@ class MatchingExecutor(CellGraphExecutor):
     # lea_conv3d_bnrelu_wino_dp_down2) and the last state's full-resolution values never exist;
     # LEASTEREO_FUSED_DOWN_CELLS=0: the resampling 1x1s
     FUSED_DOWN_CELLS = os.environ.get("LEASTEREO_FUSED_DOWN_CELLS", "1") != "0"
+    # stem0's 2D maps that the combine kernels read on a few columns only (the masked left maps,
+    # the K2 maps) computed on those columns alone (lea_conv2d_bnrelu_windowed); f32 device
+    # tensors only; LEASTEREO_WINDOWED_MAPS=0: every map on every column
+    WINDOWED_MAPS = os.environ.get("LEASTEREO_WINDOWED_MAPS", "1") != "0"
+    # LEASTEREO_FANOUT_1X1=0: every 1x1 preprocess as a launch of its own
+    FANOUT_1X1 = os.environ.get("LEASTEREO_FANOUT_1X1", "1") != "0"
 
     def run(self, x):
         """newMatching.forward (skip_model_3d.py:140-174): [B,64,D3,H3,W3] -> [B,1,D3,H3,W3]."""
@@ -503,12 +576,21 @@ class MatchingExecutor(CellGraphExecutor):
         """stem0 = ConvBR3d(cost volume) (LEAStereo.py:34-48, skip_model_3d.py:141) as
         2D maps of each feature map + lea_cv_stem_combine (csrc/cv_stem.hip)."""
         p, (wl, wr) = self.p["stem0"], self.cv
-        lm = kernels.conv2d_bnrelu(fl5, wl, 9 * p.cout, None, None, relu=False)
-        rm = kernels.conv2d_bnrelu(fr5, wr, 6 * p.cout, None, None, relu=False)
+        windowed = (self.WINDOWED_MAPS and self.cv_win is not None and fl5.is_cuda
+                    and fl5.dtype == torch.float32)
+        if windowed:
+            # the masked left maps and the K2 maps only on the columns the combine kernels read
+            # (kernels.cv_stem_map_windows); the left maps t-major, so the full-width ones lead
+            lwin, rwin = kernels.cv_stem_map_windows(d3, fl5.shape[4])
+            lm = kernels.conv2d_bnrelu_windowed(fl5, self.cv_win[0], 9 * p.cout, 3 * p.cout, (lwin,))
+            rm = kernels.conv2d_bnrelu_windowed(fr5, self.cv_win[1], 6 * p.cout, 3 * p.cout, rwin)
+        else:
+            lm = kernels.conv2d_bnrelu(fl5, wl, 9 * p.cout, None, None, relu=False)
+            rm = kernels.conv2d_bnrelu(fr5, wr, 6 * p.cout, None, None, relu=False)
         if self._cell0_takes_down((d3,) + tuple(lm.shape[3:5])) and kernels.cv_stem_down2_supported(lm, p.cout, d3):
             # (stem0, stem0 at cell 0's level): the side output of the same launch
-            return kernels.cv_stem_combine_down2(lm, rm, p.cout, d3, p.scale, p.shift, p.relu)
-        return kernels.cv_stem_combine(lm, rm, p.cout, d3, p.scale, p.shift, p.relu), None
+            return kernels.cv_stem_combine_down2(lm, rm, p.cout, d3, p.scale, p.shift, p.relu, tmajor=windowed)
+        return kernels.cv_stem_combine(lm, rm, p.cout, d3, p.scale, p.shift, p.relu, tmajor=windowed), None
 
     def _cell0_takes_down(self, vol):
         """Cell 0 reads the stems one level down, at exactly half of ``vol`` (an aligned
@@ -663,9 +745,17 @@ class MatchingExecutor(CellGraphExecutor):
             taps = last3.permute(0, 2, 3, 4, 1).reshape(co * 27, ci, 1, 1, 1)
             self.p["last_3.taps"] = ConvParams(kernels.pack_conv_weight(taps), None, None,
                                                ci, co * 27, 1, False)
-            self.cv = None
+            self.cv = self.cv_win = None
             if CV_STEM:
-                self.cv = self._cv_stem_pack(*kernels.cv_stem_split_weights(matching.stem0.conv.weight))
+                wl, wr = kernels.cv_stem_split_weights(matching.stem0.conv.weight)
+                self.cv = self._cv_stem_pack(wl, wr)
+                if self.WINDOWED_MAPS and not isinstance(self, _C8Layout):
+                    # the windowed route's own operands: left rows (3 kd + t) cout + o -> t-major,
+                    # both packed as [full-width rows ; windowed rows]
+                    co = wl.shape[0] // 9
+                    wlt = wl.view(3, 3, co, *wl.shape[1:]).transpose(0, 1).reshape(wl.shape)
+                    self.cv_win = (kernels.pack_conv2d_weight_windowed(wlt, 3 * co),
+                                   kernels.pack_conv2d_weight_windowed(wr, 3 * co))
         self._use_winograd()
 
 
@@ -677,10 +767,11 @@ class MatchingExecutorDirect(MatchingExecutor):
 
     SPLIT_S1_GROUP48 = False
     PAIR_STEPS = False
+    FANOUT_1X1 = False  # the cross-check keeps the single launches
 
     def __init__(self, matching):
         super().__init__(matching)
-        self.cv = None
+        self.cv = self.cv_win = None
 
     def _use_winograd(self):
         """Direct engine only."""
@@ -821,6 +912,7 @@ class MatchingExecutorBF16(_C8Layout, MatchingExecutor):
     is f32 for the disparity regression.  Same graph as MatchingExecutor."""
 
     SPLIT_S1_GROUP48 = False
+    FANOUT_1X1 = False  # (the two-head 1x1 is an f32 kernel)
     # the L0 / L1 cells' steps (8 or 16 channels: one K chunk per conv) as LEA_PAIR_SUM
     # launches of the D-streaming kernel; the L2 cells keep the group + accumulating launches
     PAIR_STEPS = os.environ.get("LEASTEREO_PAIR_STEPS", "1") != "0"

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import collections
 import contextlib
+import ctypes
 import math
 import os
 
@@ -16,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import LEA_BF16, LEA_F32, LEA_PAIR_SUM, LEA_RELU, LEA_RESIDUAL, check
+from ._lib import LEA_BF16, LEA_CVS_TMAJOR, LEA_F32, LEA_PAIR_SUM, LEA_RELU, LEA_RESIDUAL, check
 
 
 def _stream():
@@ -369,6 +370,33 @@ def conv3d_bnrelu(x: torch.Tensor, packed: torch.Tensor, cout: int, k: int,
     return out
 
 
+def conv1x1_heads(x: torch.Tensor, packed: torch.Tensor, cout_a: int, scale_a, shift_a, relu_a: bool,
+                  cout_b: int, scale_b, shift_b, relu_b: bool, out_a: torch.Tensor | None = None,
+                  out_b: torch.Tensor | None = None, x2: torch.Tensor | None = None,
+                  accumulate: bool = False, residual: torch.Tensor | None = None):
+    """Two 1x1 ConvBR3d of ``torch.cat((x, x2), 1)`` over one read of it (lea_conv1x1_heads):
+    ``packed`` is ``pack_conv_weight`` of the two weights stacked along cout, head A's first; each
+    head has its own folded BN (None: none), ReLU and output (a channel slice of a larger buffer
+    qualifies).  Returns (out_a, out_b), each bit-identical to its own ``conv3d_bnrelu(k=1)``.
+    Neither head accumulates or takes a residual."""
+    if accumulate or residual is not None:
+        raise ValueError("conv1x1_heads: neither head accumulates or takes a residual")
+    _require_cuda(x, x2, packed, scale_a, shift_a, scale_b, shift_b, out_a, out_b)
+    b, cin, d, h, w = x.shape
+    xbs = _check_volume_view(x, "x")
+    x2ptr, x2bs, cin2 = _second_source(x2, b, (d, h, w))
+    out_a, abs_ = _out_view(out_a, _act_shape(b, cout_a, (d, h, w)), x.device, name="out_a")
+    out_b, bbs = _out_view(out_b, _act_shape(b, cout_b, (d, h, w)), x.device, name="out_b")
+    cout = cout_a + cout_b
+    _launch("lea_conv1x1_heads", x.data_ptr(), xbs, x2ptr, x2bs, cin2, packed.data_ptr(),
+            _ptr(scale_a), _ptr(shift_a), out_a.data_ptr(), abs_, cout_a, _flags(relu_a),
+            _ptr(scale_b), _ptr(shift_b), out_b.data_ptr(), bbs, cout_b, _flags(relu_b),
+            b, cin + cin2, d, h, w, LEA_F32,
+            probe=lambda: _conv_record(b, cin + cin2, cout, d, h, w, 1, False, b * d * h * w, False,
+                                       name=_decode(_lib.load().lea_conv1x1_heads_kernel_name(b, cout, d, h, w))))
+    return out_a, out_b
+
+
 def costvolume_kernel_name(b, cout, d3, h, w):
     return _decode(_lib.load().lea_conv3d_costvolume_kernel_name(b, cout, d3, h, w))
 
@@ -455,6 +483,50 @@ def conv2d_bnrelu(x: torch.Tensor, packed: torch.Tensor, cout: int,
             probe=lambda: _op_record(
                 conv2d_kernel_name(b, cout, h, w, cin), 2.0 * b * h * w * cout * cin * 9,
                 4.0 * b * h * w * (cin + cout * (2 if rptr is not None else 1)) + 36.0 * cout * cin))
+    return out
+
+
+def pack_conv2d_weight_windowed(w: torch.Tensor, split: int) -> torch.Tensor:
+    """The packed weight of ``conv2d_bnrelu_windowed``: rows [0, split) and rows [split, cout) of a
+    [cout, cin, 3, 3] weight, each packed as ``pack_conv2d_weight`` does, one after the other."""
+    w, cout, _ = _conv2d_weight(w)
+    if not 0 <= split < cout:
+        raise ValueError(f"split {split} must be in [0, {cout})")
+    return torch.cat([pack_conv2d_weight(part) for part in (w[:split], w[split:]) if part.shape[0]])
+
+
+def conv2d_windowed_tiles(w: int, windows):
+    """The windows of ``conv2d_bnrelu_windowed`` as it runs them, in 16-column tiles:
+    [(begin, end), ...] -- rounded outward, merged where they touch."""
+    w1, w2 = (tuple(windows) + ((0, 0),))[:2]
+    t = (ctypes.c_int * 4)()
+    check(_lib.load().lea_conv2d_windowed_tiles(w, w1[0], w1[1], w2[0], w2[1], t), "lea_conv2d_windowed_tiles")
+    return [(t[i], t[i + 1]) for i in (0, 2) if t[i] < t[i + 1]]
+
+
+def conv2d_bnrelu_windowed(x: torch.Tensor, packed: torch.Tensor, cout: int, split: int, windows,
+                           scale: torch.Tensor | None = None, shift: torch.Tensor | None = None,
+                           relu: bool = False, out: torch.Tensor | None = None) -> torch.Tensor:
+    """``conv2d_bnrelu`` on the direct engine with output channels [0, split) computed on every
+    column and channels [split, cout) only on the columns of ``windows`` (one or two (begin, end),
+    rounded outward to 16-column tiles); nothing else of ``out`` is written
+    (lea_conv2d_bnrelu_windowed).  ``packed``: ``pack_conv2d_weight_windowed``."""
+    _require_cuda(x, packed, scale, shift, out)
+    b, cin, d, h, w = x.shape
+    if d != 1:
+        raise ValueError("conv2d_bnrelu_windowed takes [B, C, 1, H, W] views")
+    xbs = _check_volume_view(x, "x")
+    out, ybs = _conv_out(b, cout, (1, h, w), out, False, x.device)
+    w1, w2 = (tuple(windows) + ((0, 0),))[:2]
+    cols = sum(16 * (e - s) for s, e in conv2d_windowed_tiles(w, windows))
+
+    def record():
+        px = b * h * (split * w + (cout - split) * min(cols, w))  # output values computed
+        return _op_record(conv2d_kernel_name(b, cout - split, h, w, None) + " windowed", 2.0 * px * cin * 9,
+                          4.0 * (b * h * w * cin + px) + 36.0 * cout * cin, shape=(b, cin, cout, 1, h, w, 3))
+    _launch("lea_conv2d_bnrelu_windowed", x.data_ptr(), xbs, packed.data_ptr(), _ptr(scale), _ptr(shift),
+            out.data_ptr(), ybs, b, cin, cout, split, h, w, w1[0], w1[1], w2[0], w2[1], _flags(relu), LEA_F32,
+            probe=record)
     return out
 
 
@@ -1445,6 +1517,14 @@ def cv_stem_split_weights(w: torch.Tensor):
     return wl, wr
 
 
+def cv_stem_map_windows(d3: int, w: int):
+    """The columns of the maps that the f32 combine kernels read: (masked left maps' window,
+    K2 maps' two windows), each (begin, end) (lea_cv_stem_map_windows)."""
+    left, right = (ctypes.c_int * 2)(), (ctypes.c_int * 4)()
+    check(_lib.load().lea_cv_stem_map_windows(d3, w, left, right), "lea_cv_stem_map_windows")
+    return (left[0], left[1]), ((right[0], right[1]), (right[2], right[3]))
+
+
 def cv_stem_supported(cout: int, d3: int, w: int, bf16: bool) -> bool:
     """Shapes lea_cv_stem_combine takes (f32 stores float4 rows; one plane has no
     interior to factor around)."""
@@ -1464,9 +1544,10 @@ def _cv_stem_maps(who, lmaps, rmaps, cout, c8=False):
 
 def cv_stem_combine(lmaps: torch.Tensor, rmaps: torch.Tensor, cout: int, d3: int,
                     scale: torch.Tensor | None, shift: torch.Tensor | None, relu: bool = True,
-                    name: str = "cv_stem_f32_kernel") -> torch.Tensor:
+                    name: str = "cv_stem_f32_kernel", tmajor: bool = False) -> torch.Tensor:
     """stem0's output from the 2D maps: lmaps [B, 9 cout, 1, H, W] / rmaps [B, 6 cout, 1, H, W]
-    f32 -> [B, cout, D3, H, W] f32, or c8 maps -> c8 [B, cout/8, D3, H, W, 8] bf16."""
+    f32 -> [B, cout, D3, H, W] f32, or c8 maps -> c8 [B, cout/8, D3, H, W, 8] bf16.  ``tmajor``
+    (f32): lmaps in the order (3 t + kd) cout + o (LEA_CVS_TMAJOR)."""
     c8 = lmaps.dtype == torch.bfloat16
     b, h, w, lbs, rbs = _cv_stem_maps("cv_stem_combine", lmaps, rmaps, cout, c8)
     out = torch.empty(_act_shape(b, cout, (d3, h, w), c8), device=lmaps.device,
@@ -1476,7 +1557,8 @@ def cv_stem_combine(lmaps: torch.Tensor, rmaps: torch.Tensor, cout: int, d3: int
         raise ValueError("cv_stem_combine: left/right maps differ in batch or size")
     # algorithmic bytes: the output write (the maps are L2/MALL-resident reads)
     _launch("lea_cv_stem_combine", lmaps.data_ptr(), lbs, rmaps.data_ptr(), rbs, _ptr(scale), _ptr(shift),
-            out.data_ptr(), out.stride(0), b, cout, d3, h, w, _flags(relu), LEA_BF16 if c8 else LEA_F32,
+            out.data_ptr(), out.stride(0), b, cout, d3, h, w, _flags(relu) | (LEA_CVS_TMAJOR if tmajor else 0),
+            LEA_BF16 if c8 else LEA_F32,
             probe=lambda: _op_record(name, 0.0, out.numel() * out.element_size(), 0.0,
                                      shape=(b, 0, cout, d3, h, w, 0)))
     return out
@@ -1491,7 +1573,8 @@ def cv_stem_down2_supported(lmaps: torch.Tensor, cout: int, d3: int) -> bool:
 
 
 def cv_stem_combine_down2(lmaps: torch.Tensor, rmaps: torch.Tensor, cout: int, d3: int,
-                          scale: torch.Tensor | None, shift: torch.Tensor | None, relu: bool = True):
+                          scale: torch.Tensor | None, shift: torch.Tensor | None, relu: bool = True,
+                          tmajor: bool = False):
     """``cv_stem_combine`` (f32) with stem0's output also at the next level: returns (y, y2),
     y2 [B, cout, D3/2, H/2, W/2] = resample_trilinear(y, (D3/2, H/2, W/2)) bit for bit, written
     by the same launch from the row pair it holds in registers (no second pass over y)."""
@@ -1503,7 +1586,8 @@ def cv_stem_combine_down2(lmaps: torch.Tensor, rmaps: torch.Tensor, cout: int, d
     out2 = torch.empty((b, cout, d3 // 2, h // 2, w // 2), device=lmaps.device, dtype=torch.float32)
     # algorithmic bytes: the maps and both outputs
     _launch("lea_cv_stem_combine_down2", lmaps.data_ptr(), lbs, rmaps.data_ptr(), rbs, _ptr(scale), _ptr(shift),
-            out.data_ptr(), out.stride(0), out2.data_ptr(), out2.stride(0), b, cout, d3, h, w, _flags(relu), LEA_F32,
+            out.data_ptr(), out.stride(0), out2.data_ptr(), out2.stride(0), b, cout, d3, h, w,
+            _flags(relu) | (LEA_CVS_TMAJOR if tmajor else 0), LEA_F32,
             probe=lambda: _op_record("cv_stem_f32_down2_kernel", 0.0,
                                      4.0 * (lmaps.numel() + rmaps.numel() + out.numel() + out2.numel())))
     return out, out2
