@@ -8,19 +8,37 @@ and its BN folded into fp32 scale/shift.  ``run`` then issues only C-ABI launche
 on the current stream (no host syncs), so a whole forward can be captured in a
 HIP graph.
 
-Memory plan per cell (skip_model_3d.py:41-75, new_model_2d.py:41-75): the cell
-output ``cat([s1, s2, s3, s4])`` is allocated once and every producer writes its
-channel slice directly (preprocess -> s1 slot, first DAG op -> s_k slot, second
-DAG op accumulates into the same slot through the conv epilogue; a skip_connect
-term enters as the epilogue's residual), so neither the ``cat`` nor the ``sum``
-moves data.  Feature-net activations are [B, C, 1, H, W] views: a 2D map is the
-one-plane case of the 3D kernels (1x1 convs, bilinear = trilinear on one plane),
-and the 3x3 convs run on the 2D entry of the same MFMA engine.
+An executor is put together in three steps ("How an executor is put together"):
+
+* plan: ``_plan`` makes one ``ConvParams`` entry per ConvBR, then one planning method per route
+  (``_plan_s1_group``, ``_plan_s0_pair``, ``_plan_pair_steps``, ``_plan_share``, ``_plan_fanout``,
+  each behind its class switch) adds the stacked entries.  An entry records the ConvBRs whose
+  weights it stacks and along which axis (``_plan_entry``), so nothing later reads that out of its
+  name;
+* pack once: ``_pack`` gives every planned entry the weight of the format that runs, from
+  ``_source_weights`` of its record -- f32 executors ``packed`` (+ ``wino``), bf16 executors their
+  bf16 fragments only;
+* run with the carry: ``cell`` allocates the cell output ``cat([s1, s2, s3, s4])`` once and every
+  producer writes its channel slice directly (preprocess -> s1 slot, first DAG op -> s_k slot, the
+  second accumulates through the conv epilogue, a skip_connect term enters as the epilogue's
+  residual: neither the ``cat`` nor the ``sum`` moves data).  What the next cell needs beyond the
+  two states -- a level-down copy of the output, its own s0 already computed -- is returned in
+  ``CellOut`` and handed to the next ``cell`` call; nothing of a forward stays on the executor.
+
+A new route adds: a planning method and its call in ``_plan``, its launch in the part of ``cell``
+it replaces (``_preprocess_s0``, ``_preprocess_s1``, ``_paired_steps``, ``_steps``), and, where it
+hands something to the next cell, a field of ``CellOut``.  The packers need no edit.
+
+Feature-net activations are [B, C, 1, H, W] views: a 2D map is the one-plane case of the 3D
+kernels (1x1 convs, bilinear = trilinear on one plane), and the 3x3 convs run on the 2D entry of
+the same MFMA engine.
 """
 from __future__ import annotations
 
+import functools
 import os
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import torch
 
@@ -44,15 +62,29 @@ def _stacked(fl: torch.Tensor, fr: torch.Tensor) -> torch.Tensor:
 
 @dataclass
 class ConvParams:
-    packed: torch.Tensor      # packed weights ("s3": the raw [cout, cin, 3, 3] weight)
+    packed: torch.Tensor | None  # packed weights ("s3": the raw [cout, cin, 3, 3] weight); None until _pack
     scale: torch.Tensor | None
     shift: torch.Tensor | None
     cin: int
     cout: int
     k: int
     relu: bool
-    kind: str = "3d"          # "3d" (k 1/3), "2d" (3x3 s1), "s3" (3x3 stride 3)
+    kind: str = "3d"          # "3d" (k 1/3), "2d" (3x3 s1), "s3" (3x3 stride 3); bf16 packs: "bf16", "bf16_2d"
     wino: torch.Tensor | None = None  # Winograd-packed weight (f32 3D k=3 layers)
+    # the record of what the entry holds: the ConvBR modules whose weights it stacks, in order, along
+    # ``axis`` (0: cout -- sibling groups, share, fanout, s0_pair; 1: cin -- the pair steps); ``taps``:
+    # the one source's 27 taps as the output channels of a 1x1 (last_3.taps)
+    sources: tuple = ()
+    axis: int = 0
+    taps: bool = False
+
+
+class CellOut(NamedTuple):
+    """What cell() returns and the next cell() takes."""
+    s0: torch.Tensor                  # the next cell's s0 (this cell's s1 input)
+    out: torch.Tensor                 # this cell's output
+    down: torch.Tensor | None = None  # the output one level down too, where its producers wrote it
+    memo: tuple | None = None         # the next cell's s0 already computed: (source tensor, size, value)
 
 
 # f32 3x3x3 layers run on the Winograd F(2,3)-along-W engine (2/3 of the direct
@@ -63,21 +95,45 @@ WINOGRAD = os.environ.get("LEASTEREO_WINOGRAD", "1") != "0"
 CV_STEM = os.environ.get("LEASTEREO_CV_STEM", "1") != "0"
 
 
-def _conv_params(mod, w=None, folded=None):
-    """ConvParams of a ConvBR (weights/BN may be overridden by stacked ones)."""
-    w = mod.conv.weight if w is None else w
-    scale, shift = mod.folded_bn() if folded is None else folded
-    cout, cin, k = w.shape[0], w.shape[1], w.shape[-1]
-    if w.dim() == 5:
-        return ConvParams(kernels.pack_conv_weight(w), scale, shift, cin, cout, k, mod.relu)
-    if k == 1:  # 1x1 Conv2d = 1x1x1 Conv3d on one plane
-        return ConvParams(kernels.pack_conv_weight(w.reshape(cout, cin, 1, 1, 1)), scale, shift,
-                          cin, cout, 1, mod.relu)
-    if mod.stride == 3:
-        return ConvParams(w.detach().contiguous(), scale, shift, cin, cout, 3, mod.relu, "s3")
-    if mod.stride != 1 or mod.padding != 1:
+def _cat(ts, axis=0):
+    return ts[0] if len(ts) == 1 else torch.cat(ts, axis)
+
+
+def _plan_entry(convs, sources, axis=0, bn=True):
+    """The (not yet packed) ConvParams of the ConvBR ``sources[0]``, or of several stacked along
+    ``axis`` with their folded BN concatenated in the same order; ReLU and kind are the first's.
+    ``bn=False``: the bare conv (no BN, no ReLU).  ``convs``: the net's ConvBR modules by name."""
+    mods = [convs[s] for s in sources]
+    mod, ws = mods[0], [m.conv.weight for m in mods]
+    cout, cin, k = ws[0].shape[0], ws[0].shape[1], ws[0].shape[-1]
+    if axis == 0:
+        cout = sum(w.shape[0] for w in ws)
+    else:
+        cin = sum(w.shape[1] for w in ws)
+    folded = [m.folded_bn() if bn else (None, None) for m in mods]
+    scale, shift = folded[0] if len(mods) == 1 or not bn else (
+        torch.cat([f[j] for f in folded]).contiguous() for j in (0, 1))
+    if ws[0].dim() == 5 or k == 1:  # (1x1 Conv2d = 1x1x1 Conv3d on one plane)
+        kind = "3d"
+    elif mod.stride == 3:
+        kind = "s3"
+    elif mod.stride != 1 or mod.padding != 1:
         raise ValueError(f"unsupported Conv2d stride={mod.stride} padding={mod.padding}")
-    return ConvParams(kernels.pack_conv2d_weight(w), scale, shift, cin, cout, 3, mod.relu, "2d")
+    else:
+        kind = "2d"
+    return ConvParams(None, scale, shift, cin, cout, k, bn and mod.relu, kind, sources=tuple(sources), axis=axis)
+
+
+def _source_weights(convs, p):
+    """The f32 weights that entry ``p`` stacks, in its record's order: what every packer reads.  A 2D
+    1x1 comes in its one-plane 3D form.  ``taps``: the 3x3x3 weight's taps as rows co * 27 + tap of a
+    1x1 weight, with zero rows up to the entry's cout (c8: channels in blocks of 8)."""
+    ws = [convs[s].conv.weight for s in p.sources]
+    if p.taps:
+        taps = ws[0].permute(0, 2, 3, 4, 1).reshape(-1, ws[0].shape[1], 1, 1, 1)
+        pad = p.cout - taps.shape[0]
+        return [torch.cat([taps, taps.new_zeros((pad,) + tuple(taps.shape[1:]))], 0) if pad else taps]
+    return [w.reshape(*w.shape[:2], 1, 1, 1) if w.dim() == 4 and w.shape[-1] == 1 else w for w in ws]
 
 
 class CellGraphExecutor:
@@ -123,122 +179,150 @@ class CellGraphExecutor:
     # the cells' channel counts that take the pair launches (A/B: LEASTEREO_PAIR_C=16,32 ...)
     PAIR_C = tuple(int(c) for c in os.environ.get("LEASTEREO_PAIR_C", "8,16,32").split(",") if c)
 
+    # activations in the c8 layout ([B, C/8, D, H, W, 8] bfloat16; _C8Layout sets it): the f32-only
+    # routes and operands stay out
+    C8 = False
+
     def __init__(self, net):
-        from .model import ConvBR
         self.m = net
-        self.p = {}
         with torch.no_grad():
-            for name, mod in net.named_modules():
-                if isinstance(mod, ConvBR):
-                    self.p[name] = _conv_params(mod)
-            # Sibling ops: the DAG ops that read s1 (one per step: ops 1, 2, 4 of the
-            # matching genotype) write consecutive cat slots, so they run as ONE conv
-            # with cout = n*C over channels [.., ..) of the cell output (their weights
-            # and folded BN stacked along cout).  The remaining ops accumulate.
-            self.s1_group = {}
-            self.s1_split = set()
-            for i, cell in enumerate(net.cells):
-                group = []
-                for k, terms in enumerate(cell.plan):
-                    for op, j in terms:
-                        if j == 1 and cell.op_kinds[op] == "conv":
-                            group.append((k, op))
-                            break
-                first_cat_state = 2 + cell.steps - cell.block_multiplier
-                steps = [k for k, _ in group]
-                if (len(group) < 2 or steps != list(range(steps[0], steps[0] + len(steps)))
-                        or 2 + steps[0] < first_cat_state):
-                    continue
-                mods = [cell._ops[op] for _, op in group]
-                split = (self.SPLIT_S1_GROUP48 and WINOGRAD and len(mods) == 3 and cell.c_out == 16
-                         and mods[0].conv.weight.dim() == 5 and mods[0].conv.weight.shape[2] == 3)
-                for key, part in ((("s1_group_head", mods[:1]), ("s1_group", mods[1:])) if split
-                                  else (("s1_group", mods),)):
-                    w = torch.cat([m.conv.weight for m in part], 0)
-                    folded = [m.folded_bn() for m in part]
-                    scale = torch.cat([f[0] for f in folded]).contiguous()
-                    shift = torch.cat([f[1] for f in folded]).contiguous()
-                    self.p[f"cells.{i}.{key}"] = _conv_params(part[0], w, (scale, shift))
-                self.s1_group[i] = group
-                if split:
-                    self.s1_split.add(i)
-            self.s0_pair = {}
-            for i, cell in enumerate(net.cells) if self.PAIR_S0 else ():
-                pair = [(k, op) for k, terms in enumerate(cell.plan) for op, j in terms
-                        if j == 0 and cell.op_kinds[op] == "conv"]
-                first_cat_state = 2 + cell.steps - cell.block_multiplier
-                if (len(pair) != 2 or getattr(cell, "dims", 3) != 2 or 2 + pair[0][0] < first_cat_state
-                        or cell.c_out % 8 or 2 * cell.c_out > 32):
-                    continue
-                (k0, op0), (k1, op1) = pair
-                m0, m1 = cell._ops[op0], cell._ops[op1]
-                other = [(o, j) for o, j in cell.plan[k1] if o != op1]
-                # the s1 sibling group writes its steps' slots without accumulating, after
-                # the pair: a step both of them write would lose the pair's term
-                if {k for k, _ in self.s1_group.get(i, [])} & {k0, k1}:
-                    continue
-                # op1 writes its step first (the other term a conv that accumulates after it)
-                if (m0.relu != m1.relu or m0.conv.weight.dim() != 4 or m0.conv.weight.shape[-1] != 3
-                        or m0.stride != 1 or m1.stride != 1 or cell.plan[k1][0][0] != op1
-                        or not other or cell.op_kinds[other[0][0]] != "conv"):
-                    continue
-                w = torch.cat([m0.conv.weight, m1.conv.weight], 0)
-                folded = [m0.folded_bn(), m1.folded_bn()]
-                self.p[f"cells.{i}.s0_pair"] = _conv_params(
-                    m0, w, (torch.cat([f[0] for f in folded]).contiguous(),
-                            torch.cat([f[1] for f in folded]).contiguous()))
-                self.s0_pair[i] = pair
-            self.pair_steps = {}
-            for i, cell in enumerate(net.cells) if self.PAIR_STEPS else ():
-                terms = [[(op, j) for op, j in t] for t in cell.plan]
-                if (getattr(cell, "dims", 3) != 3 or not terms or cell.c_out not in self.PAIR_C
-                        or any(len(t) != 2 or any(cell.op_kinds[op] != "conv" for op, _ in t) for t in terms)):
-                    continue
-                mods = [[cell._ops[op] for op, _ in t] for t in terms]
-                if any(m.conv.weight.shape[-1] != 3 or not m.relu for ms in mods for m in ms):
-                    continue
-                for k, (ma, mb) in enumerate(mods):
-                    folded = [ma.folded_bn(), mb.folded_bn()]
-                    self.p[f"cells.{i}.pair{k}"] = self._pair_params(
-                        ma, torch.cat([ma.conv.weight, mb.conv.weight], 1),
-                        (torch.cat([f[0] for f in folded]).contiguous(),
-                         torch.cat([f[1] for f in folded]).contiguous()))
-                self.pair_steps[i] = terms
-            # a cell that resamples s1, followed by a same-level cell: the next cell's s0
-            # is this s1 (Cell.forward returns prev_input, skip_model_3d.py:75) at the same
-            # size, so both 1x1 convs run as one stacked conv over one read of it (down:
-            # interpolation in the conv's staging; up: one low-resolution conv and one
-            # up-sampling with the stacked BN)
-            cells = list(net.cells)
-            for i, (cell, nxt) in enumerate(zip(cells, cells[1:])):
-                if (self.SHARE_DOWNSAMPLE and cell.downup_sample != 0 and nxt.downup_sample == 0
-                        and nxt.c_out == cell.c_out and 2 + cell.steps - cell.block_multiplier == 1
-                        and cell.preprocess.conv.weight.shape[1] == nxt.pre_preprocess.conv.weight.shape[1]
-                        # the next cell applies pre_preprocess only when s0's channels differ
-                        # from its C_out (skip_model_3d.py:52); the memo path assumes it does
-                        and cell.preprocess.conv.weight.shape[1] != nxt.c_out):
-                    mods = [nxt.pre_preprocess, cell.preprocess]
-                    folded = [m.folded_bn() for m in mods]
-                    self.p[f"cells.{i}.share"] = _conv_params(
-                        mods[0], torch.cat([m.conv.weight for m in mods], 0),
-                        (torch.cat([f[0] for f in folded]).contiguous(),
-                         torch.cat([f[1] for f in folded]).contiguous()))
-            # the same pair of readers where cell i does not resample down (no `share`): cell i's
-            # `preprocess` and cell i + 1's `pre_preprocess` both run a 1x1 at the source's own
-            # level -- plain, or the raw conv of the commuted up-sampling (conv()) -- so one
-            # two-head launch reads the source once (cells.{i}.fanout: [this preprocess ; next
-            # pre_preprocess], each head keeping its own folded BN; which form each head takes
-            # is settled from the sizes at run time, _fanout_forms)
-            for i, (cell, nxt) in enumerate(zip(cells, cells[1:])) if self.FANOUT_1X1 else ():
-                wa, wb = cell.preprocess.conv.weight, nxt.pre_preprocess.conv.weight
-                if (f"cells.{i}.share" in self.p or getattr(cell, "dims", 3) != 3
-                        or wa.dim() != 5 or wa.shape[-1] != 1 or wb.shape[-1] != 1 or wa.shape[1] != wb.shape[1]
-                        or cell.downup_sample < 0 or cell.downup_sample + nxt.downup_sample < 0
-                        or wb.shape[1] == nxt.c_out):  # the next cell skips pre_preprocess
-                    continue
-                p = _conv_params(cell.preprocess, torch.cat([wa, wb], 0), (None, None))
-                p.relu = False  # each head's BN / ReLU are its own ConvBR's
-                self.p[f"cells.{i}.fanout"] = p
+            self._plan()
+            for name, p in self.p.items():
+                self._pack(name, p)
+
+    def _plan(self):
+        """``p``: one entry per ConvBR, then each route's stacked entries (and ``s1_group``,
+        ``s1_split``, ``s0_pair``, ``pair_steps``: what cell() runs from)."""
+        from .model import ConvBR
+        self._convs = {name: mod for name, mod in self.m.named_modules() if isinstance(mod, ConvBR)}
+        self.p = {name: _plan_entry(self._convs, (name,)) for name in self._convs}
+        self.s1_group, self.s1_split, self.s0_pair, self.pair_steps = {}, set(), {}, {}
+        cells = list(self.m.cells)
+        for i, cell in enumerate(cells):
+            self._plan_s1_group(i, cell)
+        for i, cell in enumerate(cells) if self.PAIR_S0 else ():
+            self._plan_s0_pair(i, cell)
+        for i, cell in enumerate(cells) if self.PAIR_STEPS else ():
+            self._plan_pair_steps(i, cell)
+        for i, (cell, nxt) in enumerate(zip(cells, cells[1:])) if self.SHARE_DOWNSAMPLE else ():
+            self._plan_share(i, cell, nxt)
+        for i, (cell, nxt) in enumerate(zip(cells, cells[1:])) if self.FANOUT_1X1 else ():
+            self._plan_fanout(i, cell, nxt)
+
+    @staticmethod
+    def _first_cat_state(cell):
+        """The first state that is part of the cell's output (states: s0, s1, then one per step)."""
+        return 2 + cell.steps - cell.block_multiplier
+
+    def _plan_s1_group(self, i, cell):
+        """Sibling ops: the DAG ops that read s1 (one per step: ops 1, 2, 4 of the matching
+        genotype) write consecutive cat slots, so they run as ONE conv with cout = n*C over
+        channels [.., ..) of the cell output (their weights and folded BN stacked along cout).
+        The remaining ops accumulate."""
+        group = []
+        for k, terms in enumerate(cell.plan):
+            for op, j in terms:
+                if j == 1 and cell.op_kinds[op] == "conv":
+                    group.append((k, op))
+                    break
+        steps = [k for k, _ in group]
+        if (len(group) < 2 or steps != list(range(steps[0], steps[0] + len(steps)))
+                or 2 + steps[0] < self._first_cat_state(cell)):
+            return
+        names = [f"cells.{i}._ops.{op}" for _, op in group]
+        w0 = cell._ops[group[0][1]].conv.weight
+        split = (self.SPLIT_S1_GROUP48 and WINOGRAD and len(names) == 3 and cell.c_out == 16
+                 and w0.dim() == 5 and w0.shape[2] == 3)
+        for key, part in ((("s1_group_head", names[:1]), ("s1_group", names[1:])) if split
+                          else (("s1_group", names),)):
+            self.p[f"cells.{i}.{key}"] = _plan_entry(self._convs, part)
+        self.s1_group[i] = group
+        if split:
+            self.s1_split.add(i)
+
+    def _plan_s0_pair(self, i, cell):
+        """A 2D cell's two conv ops on s0 as one launch writing two slots (PAIR_S0)."""
+        pair = [(k, op) for k, terms in enumerate(cell.plan) for op, j in terms
+                if j == 0 and cell.op_kinds[op] == "conv"]
+        if (len(pair) != 2 or cell.dims != 2 or 2 + pair[0][0] < self._first_cat_state(cell)
+                or cell.c_out % 8 or 2 * cell.c_out > 32):
+            return
+        (k0, op0), (k1, op1) = pair
+        m0, m1 = cell._ops[op0], cell._ops[op1]
+        other = [(o, j) for o, j in cell.plan[k1] if o != op1]
+        # the s1 sibling group writes its steps' slots without accumulating, after
+        # the pair: a step both of them write would lose the pair's term
+        if {k for k, _ in self.s1_group.get(i, [])} & {k0, k1}:
+            return
+        # op1 writes its step first (the other term a conv that accumulates after it)
+        if (m0.relu != m1.relu or m0.conv.weight.dim() != 4 or m0.conv.weight.shape[-1] != 3
+                or m0.stride != 1 or m1.stride != 1 or cell.plan[k1][0][0] != op1
+                or not other or cell.op_kinds[other[0][0]] != "conv"):
+            return
+        self.p[f"cells.{i}.s0_pair"] = _plan_entry(self._convs, [f"cells.{i}._ops.{op0}", f"cells.{i}._ops.{op1}"])
+        self.s0_pair[i] = pair
+
+    def _plan_pair_steps(self, i, cell):
+        """A 3D cell whose every step sums two 3x3x3 conv ops: one entry per step (PAIR_STEPS)."""
+        terms = [[(op, j) for op, j in t] for t in cell.plan]
+        if (cell.dims != 3 or not terms or cell.c_out not in self.PAIR_C
+                or any(len(t) != 2 or any(cell.op_kinds[op] != "conv" for op, _ in t) for t in terms)):
+            return
+        if any(cell._ops[op].conv.weight.shape[-1] != 3 or not cell._ops[op].relu for t in terms for op, _ in t):
+            return
+        for k, t in enumerate(terms):
+            # a LEA_PAIR_SUM step: [W_a | W_b] along cin, BN (a's, then b's)
+            self.p[f"cells.{i}.pair{k}"] = _plan_entry(self._convs, [f"cells.{i}._ops.{op}" for op, _ in t], axis=1)
+        self.pair_steps[i] = terms
+
+    def _plan_share(self, i, cell, nxt):
+        """A cell that resamples s1, followed by a same-level cell: the next cell's s0 is this s1
+        (Cell.forward returns prev_input, skip_model_3d.py:75) at the same size, so both 1x1 convs
+        run as one stacked conv over one read of it (down: interpolation in the conv's staging;
+        up: one low-resolution conv and one up-sampling with the stacked BN)."""
+        if (cell.downup_sample != 0 and nxt.downup_sample == 0
+                and nxt.c_out == cell.c_out and self._first_cat_state(cell) == 1
+                and cell.preprocess.conv.weight.shape[1] == nxt.pre_preprocess.conv.weight.shape[1]
+                # the next cell applies pre_preprocess only when s0's channels differ
+                # from its C_out (skip_model_3d.py:52); the memo path assumes it does
+                and cell.preprocess.conv.weight.shape[1] != nxt.c_out):
+            self.p[f"cells.{i}.share"] = _plan_entry(
+                self._convs, [f"cells.{i + 1}.pre_preprocess", f"cells.{i}.preprocess"])
+
+    def _plan_fanout(self, i, cell, nxt):
+        """The same pair of readers where cell i does not resample down (no `share`): cell i's
+        `preprocess` and cell i + 1's `pre_preprocess` both run a 1x1 at the source's own level --
+        plain, or the raw conv of the commuted up-sampling (conv()) -- so one two-head launch reads
+        the source once (cells.{i}.fanout: [this preprocess ; next pre_preprocess], each head
+        keeping its own folded BN; which form each head takes is settled from the sizes at run
+        time, _fanout_forms)."""
+        wa, wb = cell.preprocess.conv.weight, nxt.pre_preprocess.conv.weight
+        if (f"cells.{i}.share" in self.p or cell.dims != 3
+                or wa.dim() != 5 or wa.shape[-1] != 1 or wb.shape[-1] != 1 or wa.shape[1] != wb.shape[1]
+                or cell.downup_sample < 0 or cell.downup_sample + nxt.downup_sample < 0
+                or wb.shape[1] == nxt.c_out):  # the next cell skips pre_preprocess
+            return
+        # (each head's BN / ReLU are its own ConvBR's)
+        self.p[f"cells.{i}.fanout"] = _plan_entry(
+            self._convs, [f"cells.{i}.preprocess", f"cells.{i + 1}.pre_preprocess"], bn=False)
+
+    def _takes_winograd(self, p):
+        """f32 3x3x3 layers the Winograd engine takes get its packed weight as well."""
+        return WINOGRAD and p.kind == "3d" and kernels.wino_eligible(p.cout, p.cin, p.k)
+
+    def _pack(self, name, p):
+        """The f32 engines' operands of a planned entry: ``packed`` (the pair steps' weight
+        concatenated along cin), and ``wino`` of the same weight where _takes_winograd."""
+        w = _cat(_source_weights(self._convs, p), p.axis)
+        if p.kind == "s3":
+            p.packed = w.detach().contiguous()
+        elif p.kind == "2d":
+            p.packed = kernels.pack_conv2d_weight(w)
+        else:
+            p.packed = kernels.pack_conv_weight(w)
+        if self._takes_winograd(p):
+            p.wino = kernels.pack_conv_weight_wino(w)
+
 
     def _fanout_takes(self, x):
         """The two-head 1x1 (lea_conv1x1_heads) is an f32 device kernel."""
@@ -262,7 +346,8 @@ class CellGraphExecutor:
         """Cell i's s1 preprocess and cell i + 1's s0 pre_preprocess of the same source ``x`` as
         one two-head launch.  This cell's head goes where conv() puts it (``out``, or the raw z
         that the up-sampling reads; ``dn_out``: that up-sampling's level-down side output); the
-        next cell's is left in the share memo, keyed by the source and its size.  Returns s1."""
+        next cell's is handed on as the memo, keyed by the source and its size.  Returns
+        (s1, memo)."""
         nsize, up_a, up_b = forms
         pa, pb = self.p[f"cells.{i}.preprocess"], self.p[f"cells.{i + 1}.pre_preprocess"]
         b, src = x.shape[0], self._volume(x)
@@ -273,12 +358,12 @@ class CellGraphExecutor:
                               pb.cout, *fold(pb, up_b), out_a=za, out_b=zb)
         if up_b:
             zb = kernels.resample_trilinear(zb, nsize, True, None, pb.scale, pb.shift, pb.relu)
-        self._share_memo = (x, nsize, zb)
+        memo = (x, nsize, zb)
         if not up_a:
-            return za
+            return za, memo
         if dn_out is not None:
-            return kernels.resample_trilinear_down2(za, size, out, dn_out, pa.scale, pa.shift, pa.relu)[0]
-        return kernels.resample_trilinear(za, size, True, out, pa.scale, pa.shift, pa.relu)
+            return kernels.resample_trilinear_down2(za, size, out, dn_out, pa.scale, pa.shift, pa.relu)[0], memo
+        return kernels.resample_trilinear(za, size, True, out, pa.scale, pa.shift, pa.relu), memo
 
     def conv(self, name, x, out=None, accumulate=False, x2=None, size=None, residual=None, down=None,
              down_only=False):
@@ -328,12 +413,6 @@ class CellGraphExecutor:
         return kernels.conv3d_bnrelu(x, p.packed, p.cout, p.k, p.scale, p.shift, p.relu, out,
                                      accumulate, x2, residual)
 
-    def _pair_params(self, mod, w, folded):
-        """ConvParams of a LEA_PAIR_SUM step: [W_a | W_b] along cin, BN (a's, then b's)."""
-        p = _conv_params(mod, w, folded)
-        p.cout = w.shape[0]
-        return p
-
     def _pair_ok(self, x, x2, out):
         """The f32 pair launch's shape / alignment rule (lea_conv3d_bnrelu_wino, LEA_PAIR_SUM:
         the F(2,3) x F(2,3) tile, conv3d_wino22.hip)."""
@@ -342,28 +421,6 @@ class CellGraphExecutor:
     def pair_conv(self, name, x, x2, out):
         p = self.p[name]
         return kernels.conv3d_bnrelu_wino(x, p.wino, p.cout, p.scale, p.shift, True, out, x2=x2, pair_sum=True)
-
-    def _use_winograd(self):
-        """Pack the eligible 3x3x3 layers for the Winograd engine (f32 executors)."""
-        if not WINOGRAD:
-            return
-        with torch.no_grad():
-            for name, p in self.p.items():
-                if p.kind != "3d" or not kernels.wino_eligible(p.cout, p.cin, p.k):
-                    continue
-                if ".pair" in name:
-                    i, k = int(name.split(".")[1]), int(name.rsplit("pair", 1)[1])
-                    cell = self.m.cells[i]
-                    w = torch.cat([cell._ops[op].conv.weight for op, _ in self.pair_steps[i][k]], 1)
-                elif name.endswith("s1_group") or name.endswith("s1_group_head"):
-                    i = int(name.split(".")[1])
-                    mods = [self.m.cells[i]._ops[op] for _, op in self.s1_group[i]]
-                    if i in self.s1_split:
-                        mods = mods[:1] if name.endswith("_head") else mods[1:]
-                    w = torch.cat([m.conv.weight for m in mods], 0)
-                else:
-                    w = self.m.get_submodule(name).conv.weight
-                p.wino = kernels.pack_conv_weight_wino(w)
 
     # activation layout hooks (f32 NCDHW here; the bf16 executor overrides them)
     def _empty(self, b, c, size, like):
@@ -385,39 +442,36 @@ class CellGraphExecutor:
     def _resample(x, size):
         return kernels.resample_trilinear(x, size)
 
+    @staticmethod
+    def _maps(t):
+        """A one-plane result as the 2D maps its reader takes."""
+        return t.squeeze(2)
+
     def _cell_output_takes_down(self, i, size):
         """Whether cell i's producers also write its output (at ``size``) one level down
         (MatchingExecutor)."""
         return False
 
-    def cell(self, i, s0, s1, down=None):
+    def cell(self, i, s0, s1, down=None, memo=None):
         """Cell.forward (skip_model_3d.py:41-75 / new_model_2d.py:41-75).  The level
         change of s1 (:44-48) and the size match of s0 (:49-51) are fused into the
         1x1 preprocess convs (:52-53) that consume them.  ``down`` = (s0, s1) already at
         this cell's size (either may be None), written by their producers' down-sampling
-        epilogues: the preprocess convs then run at this level on them.  Where this cell's own
-        output is read only one level down (_cell_output_takes_down) that copy is left in
-        ``self._cell_down`` (None otherwise) for the caller to hand to the next cell."""
+        epilogues: the preprocess convs then run at this level on them.  ``memo``: the previous
+        cell's CellOut.memo.  Where this cell's own output is read only one level down
+        (_cell_output_takes_down) that copy is the result's ``down`` (None otherwise)."""
         cell = self.m.cells[i]
-        c = cell.c_out
-        if down is not None and down[0] is not None:
-            s0 = down[0]
-        s1_down = down is not None and down[1] is not None
-        if s1_down:
-            s1 = down[1]
+        c, bm = cell.c_out, cell.block_multiplier
+        s0_down, s1_down = down or (None, None)
+        if s0_down is not None:
+            s0 = s0_down
+        if s1_down is not None:
+            s1 = s1_down
         prev_input = s1
-        size = self._volume(s1)
-        if cell.downup_sample != 0 and not s1_down:
-            sc = 0.5 if cell.downup_sample < 0 else 2
-            # the D axis of a 2D map stays 1 (bilinear on H, W only)
-            size = tuple(n if (cell.dims == 2 and ax == 0) else scale_dimension(n, sc)
-                         for ax, n in enumerate(size))
+        size = self._cell_size(cell, s1, s1_down is not None)
         b = s1.shape[0]
-        bm = cell.block_multiplier
-        n_states = 2 + cell.steps
-        memo, self._share_memo = getattr(self, "_share_memo", None), None
-        share = f"cells.{i}.share" in self.p
-        if share:
+        big = None
+        if f"cells.{i}.share" in self.p:
             # this cell's s1 preprocess and the next cell's s0 pre_preprocess read the
             # same down-sampled tensor: one stacked 1x1 conv writes [next s0 | this s1]
             # into the channels just before and at the start of this cell's output
@@ -425,53 +479,87 @@ class CellGraphExecutor:
             out = self._channels(big, c, c + bm * c)
         else:
             out = self._empty(b, bm * c, size, s1)
-        slot = {idx: self._channels(out, k * c, (k + 1) * c)
-                for k, idx in enumerate(range(n_states - bm, n_states))}
+        first = self._first_cat_state(cell)
+        slot = {first + k: self._channels(out, k * c, (k + 1) * c) for k in range(bm)}
         # the output's only reader is the next cell's down-sampling preprocess: its producers write
         # that level too (dslot, the same channel order), the last state nothing else
         dn = None
         if self._cell_output_takes_down(i, size) and self._down_kernels_take(s1, c, self._volume(s1), size):
             dn = self._empty(b, bm * c, tuple(n // 2 for n in size), s1)
-        self._cell_down = dn
         dslot = {} if dn is None else {idx: self._channels(dn, k * c, (k + 1) * c) for k, idx in enumerate(slot)}
-        group = self.s1_group.get(i, [])
+        s0 = self._preprocess_s0(i, s0, size, slot.get(0), memo)
+        s1, memo = self._preprocess_s1(i, s1, size, big, slot.get(1), dslot.get(1), s1_down is not None)
+        if not self._paired_steps(i, s0, s1, slot):
+            self._steps(i, s0, s1, size, out, slot, dslot)
+        return CellOut(prev_input, out, dn, memo)
+
+    def _cell_size(self, cell, s1, s1_down):
+        """The cell's volume: s1's after its level change (unless its producer made it already)."""
+        size = self._volume(s1)
+        if cell.downup_sample != 0 and not s1_down:
+            sc = 0.5 if cell.downup_sample < 0 else 2
+            # the D axis of a 2D map stays 1 (bilinear on H, W only)
+            size = tuple(n if (cell.dims == 2 and ax == 0) else scale_dimension(n, sc)
+                         for ax, n in enumerate(size))
+        return size
+
+    def _preprocess_s0(self, i, s0, size, out, memo):
+        """s0 at this cell's channels and size, copied or written into ``out`` (its slot) if it is
+        part of the output."""
         if memo is not None and memo[0] is s0 and memo[1] == size:
             s0 = memo[2]  # computed by the previous cell's stacked conv
-            if 0 in slot:
-                slot[0].copy_(s0)
-        elif self._nchannels(s0) != c:
-            s0 = self.conv(f"cells.{i}.pre_preprocess", s0, out=slot.get(0), size=size)
-        else:
-            if self._volume(s0) != size:
-                s0 = self._resample(s0, size)
-            if 0 in slot:
-                slot[0].copy_(s0)
-        if share:
+        elif self._nchannels(s0) != self.m.cells[i].c_out:
+            return self.conv(f"cells.{i}.pre_preprocess", s0, out=out, size=size)
+        elif self._volume(s0) != size:
+            s0 = self._resample(s0, size)
+        if out is not None:
+            out.copy_(s0)
+        return s0
+
+    def _preprocess_s1(self, i, s1, size, big, out, dn_out, s1_down):
+        """s1's preprocess into ``out`` (its slot): stacked with the next cell's pre_preprocess into
+        ``big`` (share), as the two-head launch, or plain; ``dn_out``: its level-down side output.
+        Returns (s1, the next cell's memo or None)."""
+        c = self.m.cells[i].c_out
+        if big is not None:
             self.conv(f"cells.{i}.share", s1, out=self._channels(big, 0, 2 * c), size=size)
-            self._share_memo = (prev_input, size, self._channels(big, 0, c))
-            s1 = self._channels(big, c, 2 * c)
-        else:
-            forms = None
-            if (self.FANOUT_1X1 and f"cells.{i}.fanout" in self.p and not s1_down
-                    and not isinstance(self, _C8Layout) and self._fanout_takes(s1)):
-                forms = self._fanout_forms(i, self._volume(s1), size)
-            if forms is not None and (dn is None or forms[1]):
-                s1 = self._fanout(i, s1, size, forms, slot.get(1), None if dn is None else dslot[1])
-            else:
-                s1 = self.conv(f"cells.{i}.preprocess", s1, out=slot.get(1), size=size,
-                               **({} if dn is None else {"down": dslot[1]}))
-        states = [s0, s1]
+            return self._channels(big, c, 2 * c), (s1, size, self._channels(big, 0, c))
+        forms = None
+        if (self.FANOUT_1X1 and f"cells.{i}.fanout" in self.p and not s1_down
+                and not self.C8 and self._fanout_takes(s1)):
+            forms = self._fanout_forms(i, self._volume(s1), size)
+        if forms is not None and (dn_out is None or forms[1]):
+            return self._fanout(i, s1, size, forms, out, dn_out)
+        return self.conv(f"cells.{i}.preprocess", s1, out=out, size=size,
+                         **({} if dn_out is None else {"down": dn_out})), None
+
+    def _paired_steps(self, i, s0, s1, slot):
+        """Every step as one LEA_PAIR_SUM launch, where the cell is planned so and the engine takes
+        the operands; False where the generic steps have to run."""
         pairs = self.pair_steps.get(i)
-        if pairs is not None:
-            dsts = [slot.get(2 + k) for k in range(len(pairs))]
-            if all(d is not None for d in dsts) and all(
-                    self._pair_ok(states[t[0][1]] if t[0][1] < 2 else dsts[t[0][1] - 2],
-                                  states[t[1][1]] if t[1][1] < 2 else dsts[t[1][1] - 2], dsts[k])
-                    for k, t in enumerate(pairs)):
-                for k, ((_, ja), (_, jb)) in enumerate(pairs):
-                    self.pair_conv(f"cells.{i}.pair{k}", states[ja], states[jb], dsts[k])
-                    states.append(dsts[k])
-                return prev_input, out
+        if pairs is None:
+            return False
+        states = [s0, s1]
+        dsts = [slot.get(2 + k) for k in range(len(pairs))]
+        if not (all(d is not None for d in dsts) and all(
+                self._pair_ok(states[t[0][1]] if t[0][1] < 2 else dsts[t[0][1] - 2],
+                              states[t[1][1]] if t[1][1] < 2 else dsts[t[1][1] - 2], dsts[k])
+                for k, t in enumerate(pairs))):
+            return False
+        for k, ((_, ja), (_, jb)) in enumerate(pairs):
+            self.pair_conv(f"cells.{i}.pair{k}", states[ja], states[jb], dsts[k])
+            states.append(dsts[k])
+        return True
+
+    def _steps(self, i, s0, s1, size, out, slot, dslot):
+        """The steps of the DAG: the s0 pair and the s1 sibling group first (one launch each, straight
+        into their slots), then per step the remaining conv ops (a skip term as the first one's
+        residual, accumulating once the slot is written) and the skip terms left.  ``dslot``: the
+        launch that finishes a state writes it one level down there too."""
+        cell = self.m.cells[i]
+        c, b, n_states = cell.c_out, s1.shape[0], 2 + cell.steps
+        states = [s0, s1]
+        group = self.s1_group.get(i, [])
         written = set()
         done = set(group)
         consumed = set()  # steps whose skip term went in as an epilogue residual already
@@ -487,7 +575,7 @@ class CellGraphExecutor:
             if skips0:
                 consumed.add(k0)
         if group:  # ops on s1 of every step, one launch, straight into their slots
-            k0 = 2 + group[0][0] - (n_states - bm)
+            k0 = 2 + group[0][0] - self._first_cat_state(cell)
             if i in self.s1_split:
                 self.conv(f"cells.{i}.s1_group", s1, out=self._channels(out, (k0 + 1) * c, (k0 + 3) * c))
                 self.conv(f"cells.{i}.s1_group_head", s1, out=self._channels(out, k0 * c, (k0 + 1) * c))
@@ -509,7 +597,7 @@ class CellGraphExecutor:
                 if step not in written and skips:  # skip_connect term -> epilogue residual
                     residual = skips.pop()
                 kw = {}
-                if dn is not None and k == todo[-1]:  # the launch that finishes this state
+                if dslot and k == todo[-1]:  # the launch that finishes this state
                     kw = {"down": dslot[len(states)], "down_only": len(states) == n_states - 1}
                 self.conv(f"cells.{i}._ops.{k}", states[j], out=dst, accumulate=step in written,
                           residual=residual, **kw)
@@ -521,7 +609,7 @@ class CellGraphExecutor:
                     dst.copy_(t)
                 written.add(step)
             states.append(dst)
-        return prev_input, out
+
 
 
 class MatchingExecutor(CellGraphExecutor):
@@ -592,25 +680,30 @@ class MatchingExecutor(CellGraphExecutor):
             return kernels.cv_stem_combine_down2(lm, rm, p.cout, d3, p.scale, p.shift, p.relu, tmajor=windowed)
         return kernels.cv_stem_combine(lm, rm, p.cout, d3, p.scale, p.shift, p.relu, tmajor=windowed), None
 
+    def _down_route(self, switch):
+        """The part every *_takes_down predicate starts with: its switch on, no tap installed (the
+        per-stage checks see today's launches), not the c8 layout."""
+        return switch and self.tap is None and not self.C8
+
+    @staticmethod
+    def _halves(vol):
+        """One level down is exactly half of ``vol``, an aligned 2 x 2 x 2 reduction."""
+        return all(n % 2 == 0 and scale_dimension(n, 0.5) == n // 2 for n in vol)
+
     def _cell0_takes_down(self, vol):
-        """Cell 0 reads the stems one level down, at exactly half of ``vol`` (an aligned
-        2 x 2 x 2 reduction): their producers may write that level themselves.  Never with a
-        tap installed (the per-stage checks see today's launches) nor in the c8 layout."""
+        """Cell 0 reads the stems one level down, at exactly half of ``vol``: their producers may
+        write that level themselves."""
         cells = self.m.cells
-        return (self.FUSED_DOWN and self.tap is None and not isinstance(self, _C8Layout) and len(cells) > 0
-                and cells[0].downup_sample < 0 and cells[0].dims == 3
-                and all(n % 2 == 0 and scale_dimension(n, 0.5) == n // 2 for n in vol))
+        return (self._down_route(self.FUSED_DOWN) and len(cells) > 0
+                and cells[0].downup_sample < 0 and cells[0].dims == 3 and self._halves(vol))
 
     def _conv1_takes_down(self, vol):
         """conv1 (cat(outs[1], outs[4]) -> cell 5's s1) has one reader, cell 5's stacked 1x1
         (cells.5.share: cell 5's s1 and, through the share memo, cell 6's s0), which reads it at
-        exactly half of ``vol``: conv1 may write that level itself.  Never with a tap installed
-        nor in the c8 layout (as _cell0_takes_down)."""
+        exactly half of ``vol``: conv1 may write that level itself."""
         cells = self.m.cells
-        return (self.FUSED_DOWN_CELLS and self.tap is None and not isinstance(self, _C8Layout)
-                and len(cells) == 12 and "cells.5.share" in self.p
-                and cells[5].downup_sample < 0 and cells[5].dims == 3
-                and all(n % 2 == 0 and scale_dimension(n, 0.5) == n // 2 for n in vol))
+        return (self._down_route(self.FUSED_DOWN_CELLS) and len(cells) == 12 and "cells.5.share" in self.p
+                and cells[5].downup_sample < 0 and cells[5].dims == 3 and self._halves(vol))
 
     def _cell_output_takes_down(self, i, size):
         """Cell i's output (at ``size``) has one reader, the down-sampling ``preprocess`` of the
@@ -618,11 +711,11 @@ class MatchingExecutor(CellGraphExecutor):
         reads the output as its s0), takes its s1 alone (no ``share``), and neither conv1 nor conv2
         reads cell i.  The producers that have a down-sampling form must be the ones that run: s1
         from the commuted up-sampling 1x1, every step finished by a conv launch (no skip term left
-        to add), the step launches not paired.  Never with a tap installed nor in the c8 layout."""
+        to add), the step launches not paired."""
         cells = self.m.cells
         n = len(cells)
-        if not (self.FUSED_DOWN_CELLS and self.tap is None and not isinstance(self, _C8Layout)
-                and 0 <= i and i + 2 == n and not (n == 12 and i in (1, 4, 8))):
+        if not (self._down_route(self.FUSED_DOWN_CELLS) and 0 <= i and i + 2 == n
+                and not (n == 12 and i in (1, 4, 8))):
             return False
         cell, nxt = cells[i], cells[i + 1]
         pre = self.p.get(f"cells.{i}.preprocess")
@@ -630,11 +723,11 @@ class MatchingExecutor(CellGraphExecutor):
                 and nxt.downup_sample < 0 and f"cells.{i + 1}.share" not in self.p
                 and cell.downup_sample > 0 and f"cells.{i}.share" not in self.p
                 and pre is not None and pre.k == 1
-                and 2 + cell.steps - cell.block_multiplier == 1
+                and self._first_cat_state(cell) == 1
                 and self.pair_steps.get(i) is None and self.s0_pair.get(i) is None
                 and all(cell.op_kinds[op] == "conv" for terms in cell.plan for op, _ in terms)
                 and all(self._finishing_op(i, step) is not None for step in range(len(cell.plan)))
-                and all(m % 2 == 0 and scale_dimension(m, 0.5) == m // 2 for m in size) and size[2] % 4 == 0)
+                and self._halves(size) and size[2] % 4 == 0)
 
     def _finishing_op(self, i, step):
         """The op whose launch writes step ``step``'s state last (the s1 sibling group runs first),
@@ -679,35 +772,30 @@ class MatchingExecutor(CellGraphExecutor):
             stem1 = self.conv("stem1", stem0)
             self._emit("stem1", stem1)
         outs = []
-        prev = (stem0, stem1)
-        cell_down = None
+        # the carry: the next cell's (s0, s1), either of them already at its level (down), its memo
+        s0, s1, down, memo = stem0, stem1, (stem0_down, stem1_down), None
         n = len(self.m.cells)
         for i in range(n):
-            down = (stem0_down, stem1_down) if i == 0 else None
-            if cell_down is not None:  # cell i - 1 wrote its output at this cell's level as well
-                down = (None, cell_down)
             if i == 5 and n == 12:   # :150-151, cat read in place by the conv
-                pc, xa, xb = self.p["conv1"], outs[1][1], outs[4][1]
+                pc, xa, xb = self.p["conv1"], outs[1].out, outs[4].out
                 if (self._conv1_takes_down(self._volume(xa)) and pc.wino is not None
                         and kernels.wino_preferred(xa.shape[0], pc.cout, pc.cin, *xa.shape[2:5])
                         and kernels.conv3d_wino_down2_cat_supported(xa, xb, pc.cout)):
                     down = (None, kernels.conv3d_bnrelu_wino_down2_cat(xa, xb, pc.wino, pc.cout, pc.scale,
                                                                        pc.shift, pc.relu))
-                    prev = (outs[4][0], None)
+                    s0, s1 = outs[4].s0, None
                 else:
-                    fused = self.conv("conv1", xa, x2=xb)
-                    self._emit("conv1", fused)
-                    prev = (outs[4][0], fused)
+                    s0, s1 = outs[4].s0, self.conv("conv1", xa, x2=xb)
+                    self._emit("conv1", s1)
             elif i == 9 and n == 12:  # :155-156
-                fused = self.conv("conv2", outs[4][1], x2=outs[8][1])
-                self._emit("conv2", fused)
-                prev = (outs[8][0], fused)
-            o = self.cell(i, prev[0], prev[1], down=down)
-            cell_down, self._cell_down = self._cell_down, None
-            self._emit(f"cell{i}", o[1])
+                s0, s1 = outs[8].s0, self.conv("conv2", outs[4].out, x2=outs[8].out)
+                self._emit("conv2", s1)
+            o = self.cell(i, s0, s1, down=down, memo=memo)
+            self._emit(f"cell{i}", o.out)
             outs.append(o)
-            prev = o
-        last = outs[-1][1]
+            # (down: where cell i wrote its output at the next cell's level as well)
+            s0, s1, down, memo = o.s0, o.out, (None, o.down), o.memo
+        last = outs[-1].out
         lh = self._volume(last)[1]
         full, half, quarter = (d, h, w), (d // 2, h // 2, w // 2), (d // 4, h // 4, w // 4)
         # head (:161-173): the 1x1 Upsample pairs run commuted (see conv()); the final
@@ -737,26 +825,32 @@ class MatchingExecutor(CellGraphExecutor):
 
     def __init__(self, matching):
         super().__init__(matching)
-        with torch.no_grad():
-            # Head: last_3(Upsample(y)) = sum over taps of upsampled per-tap partial
-            # sums (lea_tapsum_upsample); the taps run as a 1x1 conv with 27*cout outputs.
-            last3 = matching.last_3.conv.weight
-            co, ci = last3.shape[:2]
-            taps = last3.permute(0, 2, 3, 4, 1).reshape(co * 27, ci, 1, 1, 1)
-            self.p["last_3.taps"] = ConvParams(kernels.pack_conv_weight(taps), None, None,
-                                               ci, co * 27, 1, False)
-            self.cv = self.cv_win = None
-            if CV_STEM:
-                wl, wr = kernels.cv_stem_split_weights(matching.stem0.conv.weight)
-                self.cv = self._cv_stem_pack(wl, wr)
-                if self.WINDOWED_MAPS and not isinstance(self, _C8Layout):
-                    # the windowed route's own operands: left rows (3 kd + t) cout + o -> t-major,
-                    # both packed as [full-width rows ; windowed rows]
-                    co = wl.shape[0] // 9
-                    wlt = wl.view(3, 3, co, *wl.shape[1:]).transpose(0, 1).reshape(wl.shape)
-                    self.cv_win = (kernels.pack_conv2d_weight_windowed(wlt, 3 * co),
-                                   kernels.pack_conv2d_weight_windowed(wr, 3 * co))
-        self._use_winograd()
+        self.cv = self.cv_win = None
+        if CV_STEM:
+            with torch.no_grad():
+                self._factor_stem0()
+
+    def _plan(self):
+        super()._plan()
+        # Head: last_3(Upsample(y)) = sum over taps of upsampled per-tap partial
+        # sums (lea_tapsum_upsample); the taps run as a 1x1 conv with 27*cout outputs
+        # (c8: 27*cout channels padded to a block)
+        co, ci = self.m.last_3.conv.weight.shape[:2]
+        cout = co * 27 + ((-co * 27) % 8 if self.C8 else 0)
+        self.p["last_3.taps"] = ConvParams(None, None, None, ci, cout, 1, False, sources=("last_3",), taps=True)
+
+    def _factor_stem0(self):
+        """The factored stem0's operands: ``cv``, the 2D map weights of each feature map, and
+        ``cv_win``, the windowed route's own (f32 only)."""
+        wl, wr = kernels.cv_stem_split_weights(self.m.stem0.conv.weight)
+        self.cv = self._cv_stem_pack(wl, wr)
+        if self.WINDOWED_MAPS and not self.C8:
+            # the windowed route's own operands: left rows (3 kd + t) cout + o -> t-major,
+            # both packed as [full-width rows ; windowed rows]
+            co = wl.shape[0] // 9
+            wlt = wl.view(3, 3, co, *wl.shape[1:]).transpose(0, 1).reshape(wl.shape)
+            self.cv_win = (kernels.pack_conv2d_weight_windowed(wlt, 3 * co),
+                           kernels.pack_conv2d_weight_windowed(wr, 3 * co))
 
 
 class MatchingExecutorDirect(MatchingExecutor):
@@ -769,12 +863,12 @@ class MatchingExecutorDirect(MatchingExecutor):
     PAIR_STEPS = False
     FANOUT_1X1 = False  # the cross-check keeps the single launches
 
-    def __init__(self, matching):
-        super().__init__(matching)
-        self.cv = self.cv_win = None
+    def _factor_stem0(self):
+        """No factored stem."""
 
-    def _use_winograd(self):
+    def _takes_winograd(self, p):
         """Direct engine only."""
+        return False
 
 
 class FeatureExecutor(CellGraphExecutor):
@@ -799,37 +893,55 @@ class FeatureExecutor(CellGraphExecutor):
 
     def run(self, x, x2=None):
         """newFeature.forward (new_model_2d.py:140-165): [N,3,H,W] -> [N,32,H/3,W/3]
-        (with x2: the stacked features of x then x2)."""
-        stem1 = self._stems(x, x2=x2)
+        (with x2: the stacked features of x then x2).  One graph for both layouts, through the
+        layout hooks (bf16: c8 maps [N, 32/8, 1, H/3, W/3, 8])."""
+        stem1 = self._stems(x, c8=self.C8, x2=x2)
         stem2 = self.conv("stem2", stem1)
-        out = (stem1, stem2)
+        o = CellOut(stem1, stem2)
         for i in range(len(self.m.cells)):
-            out = self.cell(i, out[0], out[1])
-        last = out[-1]
-        h, w = stem2.shape[3:]
-        lh = last.shape[3]
+            o = self.cell(i, o.s0, o.out, memo=o.memo)
+        last = o.out
+        h, w = self._volume(stem2)[1:]
+        lh = self._volume(last)[1]
         full, half, quarter = (1, h, w), (1, h // 2, w // 2), (1, h // 4, w // 4)
         # head (:156-163): ConvBR at the low level, then nn.Upsample; a ConvBR after an
         # Upsample reads it through conv(size=...) (interpolation fused/commuted)
         if lh == h:
             y = last
         elif lh == h // 2:
-            y = kernels.resample_trilinear(self.conv("last_6", last), full)
+            y = self._resample(self.conv("last_6", last), full)
         elif lh == h // 4:
             y = self.conv("last_6", self.conv("last_12", last), size=half)
-            y = kernels.resample_trilinear(y, full)
+            y = self._resample(y, full)
         elif lh == h // 8:
+            # new_model_2d.py:163: last_12(up_24(last_24(x))), then last_6(up_12(.)), up_6
             y = self.conv("last_12", self.conv("last_24", last), size=quarter)
-            y = kernels.resample_trilinear(self.conv("last_6", y, size=half), full)
+            y = self._resample(self.conv("last_6", y, size=half), full)
         else:
             # the reference raises UnboundLocalError here (new_model_2d.py:156-165)
             raise ValueError(f"feature size {tuple(x.shape[2:])} is not legal for the feature net")
-        return self.conv("last_3", y).squeeze(2)
+        return self._maps(self.conv("last_3", y))
+
+
+def _fresh_memo(run):
+    """A forward of a bf16 executor: the resample memo (_C8Layout._downsampled) empty before it and
+    dropped after it, however it ends."""
+    @functools.wraps(run)
+    def forward(self, *args, **kw):
+        self._rs_memo = None
+        try:
+            return run(self, *args, **kw)
+        finally:
+            self._rs_memo = None
+    return forward
 
 
 class _C8Layout:
     """Activation-layout hooks of the bf16 executors: c8 tensors
     ([B, C/8, D, H, W, 8] bfloat16), channel slices on block boundaries."""
+
+    C8 = True
+    _rs_memo = None
 
     # down-sampling 1x1 convs read their input through the interpolating gather-GEMM
     # (lea_conv1x1_resampled_bf16), so the shared-preprocess stacking applies as in fp32
@@ -857,27 +969,32 @@ class _C8Layout:
         return kernels.resample_trilinear_bf16(x, size)
 
     @staticmethod
-    def _share_weight(net, name):
-        """The stacked 1x1 weight of cells.{i}.share: [next cell's pre_preprocess ; this
-        cell's preprocess] (CellGraphExecutor.__init__)."""
-        i = int(name.split(".")[1])
-        return torch.cat([net.cells[i + 1].pre_preprocess.conv.weight, net.cells[i].preprocess.conv.weight], 0)
+    def _maps(t):
+        return t
+
+    def _pack(self, name, p):
+        """The bf16 engines' fragments of a planned entry, and nothing else (same scale/shift).  A
+        pair step: each half packed, the packs one after the other."""
+        ws = _source_weights(self._convs, p)
+        if p.kind == "2d":
+            p.packed, p.kind = kernels.pack_conv2d_weight_bf16(_cat(ws)), "bf16_2d"
+        elif p.axis == 1:
+            p.packed, p.kind = torch.cat([kernels.pack_conv_weight_bf16(w) for w in ws]), "bf16"
+        else:
+            p.packed, p.kind = kernels.pack_conv_weight_bf16(_cat(ws)), "bf16"
 
     def _downsampled(self, x, size):
         """Materialised trilinear resample of a c8 tensor, memoised for one reuse: cell i
         resizes its s1 (skip_model_3d.py:44-48) and cell i+1 resizes the same raw tensor
         as its s0 to the same size (:49-51) -- stem1 L0->L1, cell1's output and conv1's
         L1->L2.  The memo holds the source itself (no address reuse while cached) and
-        is dropped at the end of every forward (_fresh)."""
-        memo = getattr(self, "_rs_memo", None)
+        is dropped at the end of every forward (_fresh_memo)."""
+        memo = self._rs_memo
         if memo is not None and memo[0] is x and memo[1] == tuple(size):
             return memo[2]
         y = kernels.resample_trilinear_bf16(x, size)
         self._rs_memo = (x, tuple(size), y)
         return y
-
-    def _fresh(self):
-        self._rs_memo = None
 
     def _conv_c8(self, name, x, out=None, accumulate=False, x2=None, size=None, residual=None):
         p = self.p[name]
@@ -917,44 +1034,9 @@ class MatchingExecutorBF16(_C8Layout, MatchingExecutor):
     # launches of the D-streaming kernel; the L2 cells keep the group + accumulating launches
     PAIR_STEPS = os.environ.get("LEASTEREO_PAIR_STEPS", "1") != "0"
 
-    def __init__(self, matching):
-        from .model import ConvBR
-        super().__init__(matching)
-        with torch.no_grad():
-            # re-pack every f32 ConvParams into bf16 fragments (same scale/shift)
-            for name, p in list(self.p.items()):
-                if name == "last_3":
-                    continue  # runs through last_3.taps + tap-sum
-                if name == "last_3.taps":
-                    w = matching.last_3.conv.weight
-                    co, ci = w.shape[:2]
-                    taps = w.permute(0, 2, 3, 4, 1).reshape(co * 27, ci, 1, 1, 1)
-                    pad = (-taps.shape[0]) % 8  # c8: 27*cout channels padded to a block
-                    taps = torch.cat([taps, taps.new_zeros((pad,) + tuple(taps.shape[1:]))], 0)
-                    self.p[name] = ConvParams(kernels.pack_conv_weight_bf16(taps), None, None, ci,
-                                              taps.shape[0], 1, False, "bf16")
-                    continue
-                if ".pair" in name:
-                    i, k = int(name.split(".")[1]), int(name.rsplit("pair", 1)[1])
-                    wa, wb = (matching.cells[i]._ops[op].conv.weight for op, _ in self.pair_steps[i][k])
-                    packed = torch.cat([kernels.pack_conv_weight_bf16(wa), kernels.pack_conv_weight_bf16(wb)])
-                    self.p[name] = ConvParams(packed, p.scale, p.shift, p.cin, p.cout, p.k, p.relu, "bf16")
-                    continue
-                if name.endswith(".s1_group"):
-                    i = int(name.split(".")[1])
-                    mods = [matching.cells[i]._ops[op] for _, op in self.s1_group[i]]
-                    w = torch.cat([m.conv.weight for m in mods], 0)
-                elif name.endswith(".share"):
-                    w = self._share_weight(matching, name)
-                else:
-                    mod = matching.get_submodule(name)
-                    assert isinstance(mod, ConvBR)
-                    w = mod.conv.weight
-                self.p[name] = ConvParams(kernels.pack_conv_weight_bf16(w), p.scale, p.shift, p.cin,
-                                          p.cout, p.k, p.relu, "bf16")
-
-    def _use_winograd(self):
-        """bf16 layers stay on the bf16 engine."""
+    def _pack(self, name, p):
+        if name != "last_3":  # runs through last_3.taps + tap-sum: only its cout and BN are read
+            super()._pack(name, p)
 
     def _pair_ok(self, x, x2, out):
         return kernels.pair_sum_supported_bf16(x, x2, out)
@@ -985,22 +1067,13 @@ class MatchingExecutorBF16(_C8Layout, MatchingExecutor):
     def conv(self, *args, **kw):
         return self._conv_c8(*args, **kw)
 
+    @_fresh_memo
     def run(self, x):
         """x: f32 cost volume [B, 64, D3, H3, W3] -> f32 matching cost [B, 1, D3, H3, W3]."""
-        self._fresh()
-        try:
-            return self._from_stem0(self.conv("stem0", kernels.to_c8(x)))
-        finally:
-            self._fresh()
+        return self._from_stem0(self.conv("stem0", kernels.to_c8(x)))
 
+    @_fresh_memo
     def run_features(self, fl, fr, maxdisp):
-        self._fresh()
-        try:
-            return self._run_features(fl, fr, maxdisp)
-        finally:
-            self._fresh()
-
-    def _run_features(self, fl, fr, maxdisp):
         p = self.p["stem0"]
         cf = fl.shape[1] * (8 if fl.dtype == torch.bfloat16 else 1)
         if cf * 2 != p.cin:
@@ -1025,59 +1098,15 @@ class FeatureExecutorBF16(_C8Layout, FeatureExecutor):
     which the bf16 matching net reads directly."""
     PAIR_S0 = False  # (the pair launch is the f32 few-channel tile's)
 
-    def __init__(self, feature):
-        super().__init__(feature)
-        with torch.no_grad():
-            for name, p in list(self.p.items()):
-                if name in ("stem0", "stem1"):
-                    continue
-                if name.endswith(".s1_group"):
-                    i = int(name.split(".")[1])
-                    w = torch.cat([feature.cells[i]._ops[op].conv.weight for _, op in self.s1_group[i]], 0)
-                elif name.endswith(".share"):
-                    w = self._share_weight(feature, name)
-                else:
-                    w = feature.get_submodule(name).conv.weight
-                if p.kind == "2d":
-                    self.p[name] = ConvParams(kernels.pack_conv2d_weight_bf16(w), p.scale, p.shift,
-                                              p.cin, p.cout, 3, p.relu, "bf16_2d")
-                else:  # 1x1
-                    self.p[name] = ConvParams(
-                        kernels.pack_conv_weight_bf16(w.reshape(p.cout, p.cin, 1, 1, 1)), p.scale,
-                        p.shift, p.cin, p.cout, 1, p.relu, "bf16")
+    def _pack(self, name, p):
+        if name in ("stem0", "stem1"):
+            CellGraphExecutor._pack(self, name, p)
+        else:
+            super()._pack(name, p)
 
     def conv(self, name, x, *args, **kw):
         if name in ("stem0", "stem1"):
             return CellGraphExecutor.conv(self, name, x, *args, **kw)
         return self._conv_c8(name, x, *args, **kw)
 
-    def run(self, x, x2=None):
-        self._fresh()
-        try:
-            return self._run(x, x2)
-        finally:
-            self._fresh()
-
-    def _run(self, x, x2=None):
-        stem1 = self._stems(x, c8=True, x2=x2)
-        stem2 = self.conv("stem2", stem1)
-        out = (stem1, stem2)
-        for i in range(len(self.m.cells)):
-            out = self.cell(i, out[0], out[1])
-        last = out[-1]
-        h, w = self._volume(stem2)[1:]
-        lh = self._volume(last)[1]
-        full, half, quarter = (1, h, w), (1, h // 2, w // 2), (1, h // 4, w // 4)
-        if lh == h:
-            y = last
-        elif lh == h // 2:
-            y = self._resample(self.conv("last_6", last), full)
-        elif lh == h // 4:
-            y = self._resample(self.conv("last_6", self.conv("last_12", last), size=half), full)
-        elif lh == h // 8:
-            # new_model_2d.py:163: last_12(up_24(last_24(x))), then last_6(up_12(.)), up_6
-            y = self.conv("last_12", self.conv("last_24", last), size=quarter)
-            y = self._resample(self.conv("last_6", y, size=half), full)
-        else:
-            raise ValueError(f"feature size {tuple(x.shape[2:])} is not legal for the feature net")
-        return self.conv("last_3", y)
+    run = _fresh_memo(FeatureExecutor.run)

@@ -16,9 +16,9 @@ from leastereo_amd.config import LEAStereoArgs, default_arch_args
 from leastereo_amd.model import LEAStereo
 from leastereo_amd.weights import synthetic_state_dict
 from oracle import torch_ref as ref
+from tests.executor_stands import Stand, _act
 from tests.golden_util import arch, normal
 from tests.test_capi import declared_symbols
-from tests.test_executor_plan_cpu import FakeKernels, _act
 
 INVALID, UNSUPPORTED = 1001, 1002
 
@@ -138,7 +138,7 @@ def test_supported_helpers_are_false_off_the_device():
 
 
 # ------------------------------------------------------------ the executor's fused route
-class FakeDown(FakeKernels):
+class FakeDown(Stand):
     """+ stand-ins for the two down-sampling launches: the plain launch, then F.interpolate."""
 
     @staticmethod
@@ -153,11 +153,7 @@ class FakeDown(FakeKernels):
 @pytest.mark.parametrize("stem0_down", [True, False])
 @pytest.mark.parametrize("fused", [True, False])
 def test_matching_executor_fused_route_matches_oracle(monkeypatch, fused, stem0_down):
-    fk = FakeDown()
-    for name in ("pack_conv2d_weight", "pack_conv_weight", "conv3d_bnrelu", "conv3d_bnrelu_resampled",
-                 "resample_trilinear", "pack_conv_weight_wino", "conv3d_bnrelu_wino", "tapsum_upsample",
-                 "conv3d_bnrelu_wino_down2"):
-        monkeypatch.setattr(kernels, name, getattr(fk, name))
+    fk = FakeDown().install(monkeypatch, extra=("conv3d_bnrelu_wino_down2",))
     monkeypatch.setattr(kernels, "conv3d_wino_down2_supported", lambda x, cout: True)
     monkeypatch.setattr(ex, "CV_STEM", False)
     monkeypatch.setattr(ex.MatchingExecutor, "FUSED_DOWN", fused)
@@ -193,11 +189,7 @@ def test_matching_executor_fused_route_matches_oracle(monkeypatch, fused, stem0_
 
 def test_fused_route_is_off_with_a_tap(monkeypatch):
     """A stage tap sees stem1 at full resolution: the executor keeps today's launches."""
-    fk = FakeDown()
-    for name in ("pack_conv2d_weight", "pack_conv_weight", "conv3d_bnrelu", "conv3d_bnrelu_resampled",
-                 "resample_trilinear", "pack_conv_weight_wino", "conv3d_bnrelu_wino", "tapsum_upsample",
-                 "conv3d_bnrelu_wino_down2"):
-        monkeypatch.setattr(kernels, name, getattr(fk, name))
+    fk = FakeDown().install(monkeypatch, extra=("conv3d_bnrelu_wino_down2",))
     monkeypatch.setattr(kernels, "conv3d_wino_down2_supported", lambda x, cout: True)
     monkeypatch.setattr(ex, "CV_STEM", False)
     m = LEAStereo(default_arch_args(LEAStereoArgs(maxdisp=48)), "cpu")

@@ -9,8 +9,8 @@ right for the shipped genotype can be wrong for another (a genotype 
 s1 group covers a step of the s0 pair).
 
 These tests replace the library's launches by plain torch ops with the same contract
-(packed weights = the raw weights; ``out``/``accumulate``/``residual`` semantics of
-kernels.py) and run the executor in float64 on CPU against the oracle
+(tests/executor_stands.py: packed weights = the raw weights; ``out``/``accumulate``/``residual``
+semantics of kernels.py) and run the executor in float64 on CPU against the oracle
 (oracle/torch_ref.feature_forward, itself pinned to the reference's fixtures): the
 executor's graph logic is then the only thing under test.  The HIP arithmetic is
 covered by the -m gpu tests.
@@ -18,115 +18,19 @@ covered by the -m gpu tests.
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 from leastereo_amd import executor as ex
-from leastereo_amd import kernels
 from leastereo_amd.config import LEAStereoArgs, default_arch_args
 from leastereo_amd.model import LEAStereo
 from leastereo_amd.weights import synthetic_state_dict
 from oracle import torch_ref as ref
+from tests.executor_stands import Stand
 from tests.golden_util import arch, normal
-
-
-def _act(z, scale, shift, relu):
-    if scale is not None:
-        z = z * scale.view(1, -1, 1, 1, 1).to(z.dtype) + shift.view(1, -1, 1, 1, 1).to(z.dtype)
-    return z.clamp_min(0) if relu else z
-
-
-def _emit(y, out, accumulate, residual):
-    if residual is not None:
-        y = y + residual
-    if out is None:
-        return y
-    if accumulate:
-        out.add_(y)
-    else:
-        out.copy_(y)
-    return out
-
-
-class FakeKernels:
-    """torch stand-ins for the launches the f32 feature executor issues."""
-
-    def __init__(self):
-        self.log = []
-
-    @staticmethod
-    def pack_conv2d_weight(w):
-        return w.detach().clone()
-
-    @staticmethod
-    def pack_conv_weight(w):
-        return w.detach().clone()
-
-    def conv2d_bnrelu(self, x, packed, cout, scale, shift, relu=True, out=None, accumulate=False,
-                      residual=None):
-        self.log.append(("conv2d", out.data_ptr() if out is not None else None, accumulate))
-        z = F.conv2d(x[:, :, 0], packed.to(x.dtype), padding=1).unsqueeze(2)
-        return _emit(_act(z, scale, shift, relu), out, accumulate, residual)
-
-    def conv2d_bnrelu_pair(self, x, packed, c1, cout, scale, shift, relu, out1, out2, residual=None):
-        self.log.append(("pair", out1.data_ptr(), out2.data_ptr()))
-        y = _act(F.conv2d(x[:, :, 0], packed.to(x.dtype), padding=1).unsqueeze(2), scale, shift, relu)
-        _emit(y[:, :c1], out1, False, residual)
-        _emit(y[:, c1:], out2, False, None)
-
-    def conv2d_s3_bnrelu(self, x, w, scale, shift, relu=True):
-        z = F.conv2d(x[:, :, 0], w.to(x.dtype), stride=3, padding=1).unsqueeze(2)
-        return _act(z, scale, shift, relu)
-
-    def conv3d_bnrelu(self, x, packed, cout, k, scale, shift, relu=True, out=None, accumulate=False,
-                      x2=None, residual=None):
-        if x2 is not None:
-            x = torch.cat((x, x2), 1)
-        z = F.conv3d(x, packed.to(x.dtype), padding=k // 2)
-        return _emit(_act(z, scale, shift, relu), out, accumulate, residual)
-
-    def conv3d_bnrelu_resampled(self, x, size, packed, cout, k, scale, shift, relu=True, out=None,
-                                accumulate=False):
-        x = F.interpolate(x, size=tuple(size), mode="trilinear", align_corners=True)
-        return self.conv3d_bnrelu(x, packed, cout, k, scale, shift, relu, out, accumulate)
-
-    @staticmethod
-    def pack_conv_weight_wino(w):
-        return w.detach().clone()
-
-    def conv3d_bnrelu_wino(self, x, packed, cout, scale, shift, relu=True, out=None, accumulate=False,
-                           x2=None, residual=None, pair_sum=False):
-        self.log.append(("wino", out.data_ptr() if out is not None else None, accumulate, pair_sum))
-        if not pair_sum:
-            return self.conv3d_bnrelu(x, packed, cout, 3, scale, shift, relu, out, accumulate, x2, residual)
-        ca = x.shape[1]
-        ya = _act(F.conv3d(x, packed[:, :ca].to(x.dtype), padding=1), scale[:cout], shift[:cout], relu)
-        yb = _act(F.conv3d(x2, packed[:, ca:].to(x.dtype), padding=1), scale[cout:], shift[cout:], relu)
-        return _emit(ya + yb, out, False, None)
-
-    def tapsum_upsample(self, q, cout, size, scale=None, shift=None, relu=False):
-        """sum over the 27 taps of the up-sampled per-tap partial sums, shifted by the tap
-        (channel co * 27 + tap): conv3x3x3(upsample(y)) by linearity."""
-        d, h, w = (int(v) for v in size)
-        up = F.pad(F.interpolate(q, size=(d, h, w), mode="trilinear", align_corners=True), (1, 1, 1, 1, 1, 1))
-        y = sum(up[:, co * 27 + (kd * 3 + kh) * 3 + kw::27 * cout][:, :1, kd:kd + d, kh:kh + h, kw:kw + w]
-                for co in range(cout) for kd in range(3) for kh in range(3) for kw in range(3)) \
-            if cout == 1 else None
-        return _act(y, scale, shift, relu)
-
-    def resample_trilinear(self, x, size, align_corners=True, out=None, scale=None, shift=None,
-                           relu=False):
-        y = _act(F.interpolate(x, size=tuple(size), mode="trilinear", align_corners=align_corners),
-                 scale, shift, relu)
-        return _emit(y, out, False, None)
 
 
 @pytest.fixture
 def fake(monkeypatch):
-    fk = FakeKernels()
-    for name in ("pack_conv2d_weight", "pack_conv_weight", "conv2d_bnrelu", "conv2d_bnrelu_pair",
-                 "conv2d_s3_bnrelu", "conv3d_bnrelu", "conv3d_bnrelu_resampled", "resample_trilinear",
-                 "pack_conv_weight_wino", "conv3d_bnrelu_wino", "tapsum_upsample"):
-        monkeypatch.setattr(kernels, name, getattr(fk, name))
+    fk = Stand().install(monkeypatch)
     # the stems as two convs (the fused stem kernel has no stand-in here)
     monkeypatch.setattr(ex.FeatureExecutor, "FUSED_STEM", False)
     return fk

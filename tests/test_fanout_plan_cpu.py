@@ -15,62 +15,24 @@ import torch
 import torch.nn.functional as F
 
 from leastereo_amd import executor as ex
-from leastereo_amd import kernels
 from leastereo_amd.config import LEAStereoArgs, default_arch_args
 from leastereo_amd.model import LEAStereo
 from leastereo_amd.weights import synthetic_state_dict
 from oracle import torch_ref as ref
+from tests.executor_stands import Stand, _act, _emit
 from tests.golden_util import arch, normal
 
 
-def _act(z, scale, shift, relu):
-    if scale is not None:
-        z = z * scale.view(1, -1, 1, 1, 1).to(z.dtype) + shift.view(1, -1, 1, 1, 1).to(z.dtype)
-    return z.clamp_min(0) if relu else z
-
-
-def _emit(y, out, accumulate=False, residual=None):
-    if residual is not None:
-        y = y + residual
-    if out is None:
-        return y
-    if accumulate:
-        out.add_(y)
-    else:
-        out.copy_(y)
-    return out
-
-
-class Stand:
-    """torch stand-ins for the launches the f32 matching executor issues on this path."""
+class HeadsStand(Stand):
+    """+ the two-head 1x1 (lea_conv1x1_heads)."""
 
     def __init__(self):
+        super().__init__()
         self.heads = []   # (source data_ptr, cout_a, head A has BN, cout_b, head B has BN)
-        self.single = []  # (source data_ptr, cout) of every single 1x1 launch
 
-    @staticmethod
-    def pack(w):
-        return w.detach().clone()
-
-    def conv3d_bnrelu(self, x, packed, cout, k, scale, shift, relu=True, out=None, accumulate=False,
-                      x2=None, residual=None):
-        if k == 1:
-            self.single.append((x.data_ptr(), cout))
-        if x2 is not None:
-            x = torch.cat((x, x2), 1)
-        z = F.conv3d(x, packed.to(x.dtype), padding=k // 2)
-        return _emit(_act(z, scale, shift, relu), out, accumulate, residual)
-
-    def conv3d_bnrelu_resampled(self, x, size, packed, cout, k, scale, shift, relu=True, out=None,
-                                accumulate=False):
-        x = F.interpolate(x, size=tuple(size), mode="trilinear", align_corners=True)
-        z = F.conv3d(x, packed.to(x.dtype), padding=k // 2)
-        return _emit(_act(z, scale, shift, relu), out, accumulate)
-
-    def conv3d_bnrelu_wino(self, x, packed, cout, scale, shift, relu=True, out=None, accumulate=False,
-                           x2=None, residual=None, pair_sum=False):
-        assert not pair_sum
-        return self.conv3d_bnrelu(x, packed, cout, 3, scale, shift, relu, out, accumulate, x2, residual)
+    def conv3d_bnrelu_wino(self, *args, pair_sum=False, **kw):
+        assert not pair_sum  # (PAIR_STEPS is off on this path)
+        return super().conv3d_bnrelu_wino(*args, **kw)
 
     def conv1x1_heads(self, x, packed, cout_a, scale_a, shift_a, relu_a, cout_b, scale_b, shift_b, relu_b,
                       out_a=None, out_b=None, x2=None):
@@ -80,27 +42,10 @@ class Stand:
         return (_emit(_act(z[:, :cout_a], scale_a, shift_a, relu_a), out_a),
                 _emit(_act(z[:, cout_a:], scale_b, shift_b, relu_b), out_b))
 
-    def resample_trilinear(self, x, size, align_corners=True, out=None, scale=None, shift=None, relu=False):
-        y = F.interpolate(x, size=tuple(size), mode="trilinear", align_corners=align_corners)
-        return _emit(_act(y, scale, shift, relu), out)
-
-    def tapsum_upsample(self, q, cout, size, scale=None, shift=None, relu=False):
-        assert cout == 1
-        d, h, w = (int(v) for v in size)
-        up = F.pad(F.interpolate(q, size=(d, h, w), mode="trilinear", align_corners=True), (1, 1, 1, 1, 1, 1))
-        y = sum(up[:, (kd * 3 + kh) * 3 + kw::27][:, :1, kd:kd + d, kh:kh + h, kw:kw + w]
-                for kd in range(3) for kh in range(3) for kw in range(3))
-        return _act(y, scale, shift, relu)
-
 
 @pytest.fixture
 def stand(monkeypatch):
-    st = Stand()
-    for name in ("conv3d_bnrelu", "conv3d_bnrelu_resampled", "conv3d_bnrelu_wino", "conv1x1_heads",
-                 "resample_trilinear", "tapsum_upsample"):
-        monkeypatch.setattr(kernels, name, getattr(st, name))
-    for name in ("pack_conv_weight", "pack_conv2d_weight", "pack_conv_weight_wino"):
-        monkeypatch.setattr(kernels, name, st.pack)
+    st = HeadsStand().install(monkeypatch, extra=("conv1x1_heads",))
     monkeypatch.setattr(ex, "CV_STEM", False)
     monkeypatch.setattr(ex.MatchingExecutor, "PAIR_STEPS", False)
     return st
