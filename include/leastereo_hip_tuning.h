@@ -181,6 +181,22 @@ int lea_conv3d_wino44_set_sched(int s);
  * workgroups, else 0.  Bit-identical. */
 int lea_conv3d_wino44_set_group(int g);
 
+/* The F(4,3) x F(4,3) tile's geometry: 32 = 32 (W) x 2 (H) x 4 (D) voxels per workgroup, 16 =
+ * 16 x 4 x 4 (the same 64 voxels per plane and 16 MFMA columns per wave: 4 W groups x 4 rows
+ * instead of 8 x 2), -1 (default) = by the layer's shape: the narrow tile where it pads fewer
+ * columns (ceil(W / 16) 16 < ceil(W / 32) 32; C2's quarter-resolution volumes, W = 80).  Any other
+ * value is LEA_E_INVALID and leaves the setting alone.  Bit-identical outputs: the same transforms
+ * in the same order per voxel.  The narrow geometry exists in the default form only: with
+ * lea_conv3d_wino44_set_upre(1) or a non-zero lea_conv3d_wino44_set_sched the wide tile runs,
+ * and the down-sampling entries (lea_conv3d_bnrelu_wino_down2[_cat]) always launch the wide tile.
+ * lea_conv3d_wino_kernel_name answers "conv3d_wino44_kernel" for both. */
+int lea_conv3d_wino44_set_tile(int t);
+
+/* The geometry a launch of this shape takes under the current settings: 32 or 16 for a layer the
+ * planner puts on the F(4,3) x F(4,3) tile (lea_conv3d_wino_kernel_name ==
+ * "conv3d_wino44_kernel", aligned operands assumed), 0 for any other. */
+int lea_conv3d_wino44_tile(int B, int cin, int cout, int D, int H, int W);
+
 /* 1 (default) = the Winograd engines' buffer-addressed epilogue where the shape allows
  * it (W % 4 == 0, 16-B aligned output / residual; residual loads issued together, the
  * next chunk's DMA waited for without the stores), 0 = the per-group epilogue. */

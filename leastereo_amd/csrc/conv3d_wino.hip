@@ -42,6 +42,8 @@
 // Within a chunk the 9 (kd, kh) steps are software-pipelined: LDS reads two steps
 // ahead, the V / U transforms one step ahead, so a step's VALU issues under the
 // previous step's MFMAs.
+#include <cstring>
+
 #include "wino_common.h"
 
 namespace lea {
@@ -1148,6 +1150,20 @@ extern "C" int lea_conv3d_wino44_set_group(int g) {
   LEA_CHECK_ARG(g >= -1 && g <= 16, "lea_conv3d_wino44_set_group: %d", g);
   wino::g_w44g = g;
   return 0;
+}
+
+extern "C" int lea_conv3d_wino44_set_tile(int t) {
+  clear_error();
+  LEA_CHECK_ARG(t == -1 || t == 16 || t == 32, "lea_conv3d_wino44_set_tile: %d", t);
+  wino::g_w44t = t;
+  return 0;
+}
+
+extern "C" int lea_conv3d_wino44_tile(int B, int cin, int cout, int D, int H, int W) {
+  if (cin <= 0 || cin % wino::CIN_B != 0) return 0;
+  const char* name = lea_conv3d_wino_kernel_name(B, cin, cout, D, H, W, 0);
+  if (!name || strcmp(name, "conv3d_wino44_kernel") != 0) return 0;
+  return wino::tile44(B, cin, cout, D, H, W);
 }
 
 extern "C" int lea_conv3d_wino44_set_sched(int s) {

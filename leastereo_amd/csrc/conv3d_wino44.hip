@@ -15,7 +15,8 @@
 // two waves per SIMD, so the W points are split between two waves: wave (xh, wc) owns the W
 // points 3 xh .. 3 xh + 2 of cout tile wc (16 couts) -- 18 points, 72 accumulator VGPRs.  The
 // workgroup = 2 x-halves x 2 cout tiles = 4 waves over one 32 (W) x 2 (H) x 4 (D) x 32 (cout)
-// output tile; two workgroups per CU (74 KB of LDS each).
+// output tile; two workgroups per CU (74 KB of LDS each).  A second geometry, 16 (W) x 4 (H) x
+// 4 (D), covers the same 64 voxels per plane (w44::Geo<4>; the host's tile44 picks per shape).
 //
 // Item i = (depth quad, 4-channel chunk), the one-barrier pipeline of conv3d_wino2p_kernel:
 //   top      this wave's halo(i + 1) pieces and weights g(i) have landed (vmcnt), barrier
@@ -30,7 +31,8 @@
 // four couts its lanes carry, then A_W^T and A_D^T (with G's factors), BN, ReLU, residual,
 // buffer-addressed float4 stores.
 //
-// LDS maps (exhaustive checks in the comments below, tools/w44_banks.py):
+// LDS maps of the 32 x 2 geometry (the 16 x 4 one's: at w44::Geo; exhaustive checks of both in
+// tools/w44_banks.py):
 //   halo: channel c at CB(c) == {1, 3, 33, 35}[c] mod 64, rows of RWA = 40 floats from w0 - 4
 //         (whole 16-byte blocks), planes PLANEA = 160 apart; the V-pass's b64 reads
 //         (32 lanes = 8 groups x 4 channels) hit 64 distinct banks
@@ -45,22 +47,50 @@ namespace lea {
 namespace wino {
 
 namespace w44 {
-constexpr int Q = 8, F = 4, TW = 32, TH = 2, TD = 4, PLANES = 6, RH = TH + 2, RWA = TW + 8;
-constexpr int PLANEA = RH * RWA;               // 160 floats per staged plane
-constexpr int BLK16 = PLANES * PLANEA / 4;     // 240 16-byte blocks per channel
+constexpr int F = 4, TD = 4, PLANES = 6;
 constexpr int CB0 = 1, CB1 = CB0 + 1024 + 2, CB2 = CB1 + 1024 + 30, CB3 = CB2 + 1024 + 2;
 constexpr int XS = (CB3 + 1024 + 3) / 4 * 4;   // floats per halo buffer
-constexpr int GS = 40, XHS = 20, TRS = 320, TCS = 1284, TS = 4 * TCS;
+constexpr int GS = 40, XHS = 20;
 constexpr int KGL = 28;                        // per-lane weights per (cout, channel): [kh][kd][x 3] + pad
 constexpr int KGU = 56;                        // UPRE: U = G_D' G_W' g, [kh][x 3][e 6] + pad
 constexpr int NST = 8;                         // buffer stores per epilogue and lane
 constexpr int NSTD = 2;                        // ... of the down-sampling epilogue (DOWN)
 static_assert(CB1 % 64 == 3 && CB2 % 64 == 33 && CB3 % 64 == 35, "V-pass bank map");
-static_assert(BLK16 <= 4 * 64 && 4 * 256 <= CB1 - CB0, "whole pieces per channel region");
-static_assert(TRS % 64 == 0 && TCS % 8 == 4 && GS % 8 == 0 && XHS % 4 == 0 && TRS >= Q * GS && TCS >= RH * TRS,
-              "V bank map");
-static_assert(4 * 64 * 20 <= TS && 4 * 64 * 16 <= XS, "epilogue exchange fits a V and a halo buffer");
-static_assert((2 * XS + 2 * TS) * 4 * 2 <= 160 * 1024, "two workgroups per CU");
+static_assert(GS % 8 == 0 && XHS % 4 == 0, "V bank map");
+
+// The tile's geometry: a wave's 16 MFMA columns are Q_ W groups x 16 / Q_ rows.  Geo<8> is the
+// 32 (W) x 2 (H) tile, Geo<4> the 16 x 4 one (the same 64 voxels per plane; taken where it pads
+// fewer columns of W: tile44 below).  Channel bases, XS, GS and XHS are common to both.
+//   halo: rows of RWA floats in RSLOTS row slots per plane.  Geo<4> leaves the slot before its last
+//         halo row empty: a 32-lane ds_read_b64 group of the V-pass is 4 groups x 4 channels x 2
+//         rows, and with rows 24 floats apart the rows of a pair must be 16 or 48 (mod 64) apart to
+//         hit disjoint banks -- pairs (0, 2), (1, 3) and, past the empty slot, (4, 5): 48 each.
+//         The compiler pairs two of the three reads into a ds_read2_b64 (16-lane groups, 32 banks,
+//         where channels c and c + 2 coincide): a 16-lane group is 4 groups x 2 channels {0, 1} or
+//         {2, 3} x both rows of the pair (48 == 16 mod 32), 32 distinct banks as well
+//   V:    [ci: TCS][row: TRS = Q GS][group: GS][x-half: XHS][x 3][e 6].  Geo<4>: TRS = 160 == 32 and
+//         TCS = 964 == 4 (mod 64): a step's ds_read_b128 lane group holds rows {0, 3} of one channel
+//         and {1, 2} of the next, 16-byte slots {0, 8} and {9, 1} + 10 pq (mod 16), all distinct
+template <int Q_>
+struct Geo {
+  static constexpr int Q = Q_, TW = F * Q, TH = 16 / Q, RH = TH + 2, RWA = TW + 8;
+  static constexpr int RSLOTS = Q == 8 ? RH : RH + 1;
+  static constexpr int PLANEA = RSLOTS * RWA;            // 160 / 168 floats per staged plane
+  static constexpr int BLK16 = PLANES * PLANEA / 4;      // 240 / 252 16-byte blocks per channel
+  static constexpr int TRS = Q * GS, TCS = Q == 8 ? 1284 : 964;
+  static constexpr int TS = 4 * TCS > 4 * 64 * 20 ? 4 * TCS : 4 * 64 * 20;  // (the exchange's 20 floats per lane)
+  static constexpr int row_slot(int r) { return RSLOTS == RH || r < RH - 1 ? r : r + 1; }
+  static_assert(Q == 8 || Q == 4, "the instantiated geometries");
+  static_assert(BLK16 <= 4 * 64 && 4 * 256 <= CB1 - CB0, "whole pieces per channel region");
+  static_assert(Q == 8 ? TRS % 64 == 0 && TCS % 8 == 4 : TRS % 64 == 32 && TCS % 64 == 4, "V bank map");
+  static_assert(TCS >= RH * TRS, "V rows per channel");
+  static_assert(4 * 64 * 20 <= TS && 4 * 64 * 16 <= XS, "epilogue exchange fits a V and a halo buffer");
+  static_assert((2 * XS + 2 * TS) * 4 * 2 <= 160 * 1024, "two workgroups per CU");
+};
+static_assert((Geo<4>::row_slot(2) - Geo<4>::row_slot(0)) * Geo<4>::RWA % 64 == 48 &&
+                  (Geo<4>::row_slot(3) - Geo<4>::row_slot(1)) * Geo<4>::RWA % 64 == 48 &&
+                  (Geo<4>::row_slot(5) - Geo<4>::row_slot(4)) * Geo<4>::RWA % 64 == 48,
+              "halo row pairs of a V-pass half-wave");
 }  // namespace w44
 
 // per-lane weights of one (cout block of 32, chunk, cout tile wc, x-half xh): 7 slices of 64
@@ -177,9 +207,12 @@ __device__ __forceinline__ void buf_store2(__amdgpu_buffer_rsrc_t rs, unsigned o
   __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_t, v), rs, off, 0, 0);
 }
 
-template <bool UPRE, int SCHED, bool DOWN>
+template <class Geom, bool UPRE, int SCHED, bool DOWN>
 __device__ __forceinline__ void conv3d_wino44_body(const ConvArgs& a) {
   using namespace w44;
+  static_assert(!DOWN || Geom::Q == 8, "the down-sampling epilogue's H partner is lane ^ 8 of the 32 x 2 tile");
+  constexpr int Q = Geom::Q, TW = Geom::TW, TH = Geom::TH, RH = Geom::RH, RWA = Geom::RWA;
+  constexpr int PLANEA = Geom::PLANEA, BLK16 = Geom::BLK16, TRS = Geom::TRS, TCS = Geom::TCS, TS = Geom::TS;
   constexpr int NX = 3, NE = 6;  // this wave's W points x the D points
   __shared__ __attribute__((aligned(16))) float smem[2 * XS + 2 * TS];
   const unsigned lds0 = lds_addr(smem);
@@ -253,10 +286,12 @@ __device__ __forceinline__ void conv3d_wino44_body(const ConvArgs& a) {
   unsigned hwo16 = 0xFFFFFFF0u;
   int pln16 = -1000;
   {
-    const int p = e16 / (RH * (RWA / 4)), r = e16 - p * (RH * (RWA / 4));
-    const int rr = r / (RWA / 4), blk = r - rr * (RWA / 4);
+    const int p = e16 / (PLANEA / 4), r = e16 - p * (PLANEA / 4);
+    const int rs = r / (RWA / 4), blk = r - rs * (RWA / 4);
+    const int rr = Geom::RSLOTS == RH || rs < RH - 1 ? rs : rs - 1;  // (Geom::row_slot's inverse)
+    const bool live = Geom::RSLOTS == RH || rs != RH - 1;            // not the empty row slot
     const int h = h0 + rr - 1, w = w0 - 4 + 4 * blk;
-    if (e16 < BLK16 && (unsigned)h < (unsigned)a.H && (unsigned)w < (unsigned)a.W) {
+    if (live && e16 < BLK16 && (unsigned)h < (unsigned)a.H && (unsigned)w < (unsigned)a.W) {
       hwo16 = (unsigned)(h * a.W + w) * 4u;
       pln16 = p - 1;
     }
@@ -286,11 +321,25 @@ __device__ __forceinline__ void conv3d_wino44_body(const ConvArgs& a) {
     for (int k = 0; k < GL / 4; ++k) gw[k] = src[64 * k];
   };
   // V-pass unit of thread t: W group vg, channel vc, halo row vr, x-half vxh (wave-uniform)
-  const int vg = (tid & 3) | (((tid >> 3) & 1) << 2);
-  const int vc = ((tid >> 2) & 1) | (((tid >> 4) & 1) << 1);
-  const int vr = (tid >> 5) & 3;
+  int vg, vc, vr;
+  if constexpr (Q == 8) {
+    vg = (tid & 3) | (((tid >> 3) & 1) << 2);
+    vc = ((tid >> 2) & 1) | (((tid >> 4) & 1) << 1);
+    vr = (tid >> 5) & 3;
+  } else {
+    // 96 units per x-half on 128 threads: half-wave hw = 4 groups x 4 channels x the row pair
+    // (0, 2), (1, 3) or (4, 5); the fourth half-wave repeats the first one's units (the same
+    // values to the same words: no branch, no masked lanes).  Lanes as in the wide map, the row
+    // of the pair (bit 3) where that has the group's high bit: 16 lanes = 4 groups x channels
+    // {0, 1} or {2, 3} x both rows, so the ds_read2_b64 that a0 / a1 compile to (16-lane groups,
+    // 32 banks, where channels c and c + 2 share banks) is conflict-free as well
+    const int hw = (tid >> 5) & 3, ub = hw == 3 ? 0 : hw, rb = (tid >> 3) & 1;
+    vg = tid & 3;
+    vc = ((tid >> 2) & 1) | (((tid >> 4) & 1) << 1);
+    vr = ub < 2 ? ub + 2 * rb : 4 + rb;
+  }
   const int vxh = __builtin_amdgcn_readfirstlane(tid >> 7);
-  const int vxo = (vc == 0 ? CB0 : vc == 1 ? CB1 : vc == 2 ? CB2 : CB3) + vr * RWA + 3 + F * vg;
+  const int vxo = (vc == 0 ? CB0 : vc == 1 ? CB1 : vc == 2 ? CB2 : CB3) + Geom::row_slot(vr) * RWA + 3 + F * vg;
   const int vto = vc * TCS + vr * TRS + GS * vg + XHS * vxh;
   auto vpass = [&](auto XHC, int buf) {
     constexpr int VXH = decltype(XHC)::value;  // == vxh (wave-uniform): a compile-time branch
@@ -624,15 +673,19 @@ __device__ __forceinline__ void conv3d_wino44_body(const ConvArgs& a) {
 
 template <bool UPRE, int SCHED>
 __global__ __launch_bounds__(256, 2) void conv3d_wino44_kernel(const ConvArgs a) {
-  conv3d_wino44_body<UPRE, SCHED, false>(a);
+  conv3d_wino44_body<w44::Geo<8>, UPRE, SCHED, false>(a);
+}
+// the 16 x 4 geometry, in the default form only (lea_conv3d_wino44_set_tile, tile44 below)
+__global__ __launch_bounds__(256, 2) void conv3d_wino44_kernel_16x4(const ConvArgs a) {
+  conv3d_wino44_body<w44::Geo<4>, false, 0, false>(a);
 }
 __global__ __launch_bounds__(256, 2) void conv3d_wino44_down2_kernel(const ConvArgs a) {
-  conv3d_wino44_body<false, 0, true>(a);
+  conv3d_wino44_body<w44::Geo<8>, false, 0, true>(a);
 }
 // the same body on cat(x, x2) read in place (lea_conv3d_bnrelu_wino_down2_cat: issue_halo takes a
 // chunk's channels from the source that holds them), under a name of its own in traces
 __global__ __launch_bounds__(256, 2) void conv3d_wino44_down2_cat_kernel(const ConvArgs a) {
-  conv3d_wino44_body<false, 0, true>(a);
+  conv3d_wino44_body<w44::Geo<8>, false, 0, true>(a);
 }
 
 // lea_conv3d_wino44_set (r06 default 1: -9.5 % on its layers, profiles/r06_w44_ab.txt; 2 since v45,
@@ -641,11 +694,29 @@ int g_w44 = 2;
 int g_w44u = 0;  // lea_conv3d_wino44_set_upre
 int g_w44s = 0;  // lea_conv3d_wino44_set_sched
 int g_w44g = -1;  // lea_conv3d_wino44_set_group (-1: auto)
+int g_w44t = -1;  // lea_conv3d_wino44_set_tile (-1: auto)
+
+// The tile geometry of a layer on this kernel, by its shape alone: 32 (the 32 x 2 tile) or 16
+// (16 x 4).  Auto takes the narrow tile where it pads fewer columns (C2's quarter-resolution
+// volumes: W = 80 is 2.5 wide tiles, and 288 / 864 workgroups against 256 CUs x 2 become 240 /
+// 720).  The rule also takes the narrow tile for every W <= 16 and every W % 32 in 1 .. 16; of
+// those only W = 80 was measured (profiles/w44_narrow_layers_ab.txt), the others follow from the
+// padding argument alone.  The narrow geometry is built for the default form only (upre 0,
+// sched 0); the down-sampling entries always launch the wide one.
+int tile44(int B, int cin, int cout, int D, int H, int W) {
+  (void)B, (void)cin, (void)cout, (void)D, (void)H;
+  if (g_w44u || g_w44s != 0) return 32;
+  if (g_w44t > 0) return g_w44t;
+  auto padded = [&](int tw) { return (W + tw - 1) / tw * tw; };
+  return padded(w44::Geo<4>::TW) < padded(w44::Geo<8>::TW) ? 16 : 32;
+}
 
 int run44(ConvArgs a, int B, int spw, hipStream_t st, bool down) {
+  const bool narrow = !down && tile44(B, a.cin, a.cout, a.D, a.H, a.W) == 16;
+  const int tw = narrow ? w44::Geo<4>::TW : w44::Geo<8>::TW, th = narrow ? w44::Geo<4>::TH : w44::Geo<8>::TH;
   a.ncob = (a.cout + 31) / 32;
-  a.tiles_w = (a.W + w44::TW - 1) / w44::TW;
-  a.ntiles = a.tiles_w * ((a.H + w44::TH - 1) / w44::TH);
+  a.tiles_w = (a.W + tw - 1) / tw;
+  a.ntiles = a.tiles_w * ((a.H + th - 1) / th);
   a.ndz = (a.D + w44::TD - 1) / w44::TD;
   a.spw = std::max(1, std::min(spw > 0 ? spw : auto_walk(a, B, 2), a.ndz));
   const long long n_ = (long long)a.ntiles * ((a.ndz + a.spw - 1) / a.spw) * B * a.ncob;
@@ -664,7 +735,9 @@ int run44(ConvArgs a, int B, int spw, hipStream_t st, bool down) {
       conv3d_wino44_down2_kernel<<<grid, 256, 0, st>>>(a);
     return launch_status("lea_conv3d(wino44 down2)");
   }
-  if (g_w44u)
+  if (narrow)
+    conv3d_wino44_kernel_16x4<<<grid, 256, 0, st>>>(a);
+  else if (g_w44u)
     conv3d_wino44_kernel<true, 0><<<grid, 256, 0, st>>>(a);
   else if (g_w44s == 1)
     conv3d_wino44_kernel<false, 1><<<grid, 256, 0, st>>>(a);

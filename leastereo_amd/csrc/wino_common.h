@@ -152,6 +152,8 @@ extern int g_w44;
 extern int g_w44u;  // lea_conv3d_wino44_set_upre
 extern int g_w44s;  // lea_conv3d_wino44_set_sched
 extern int g_w44g;  // lea_conv3d_wino44_set_group
+extern int g_w44t;  // lea_conv3d_wino44_set_tile
+int tile44(int B, int cin, int cout, int D, int H, int W);  // 32 (the 32 x 2 tile) or 16 (16 x 4)
 long long lane44_floats(int cout, int cin);
 long long lane44_g_floats(int cout, int cin);  // the G_W' g part (the U copy follows)
 __global__ void pack_wino44_lane_kernel(const float* __restrict__ w, float* __restrict__ out, int cout, int cin,

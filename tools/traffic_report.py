@@ -30,6 +30,8 @@ def load(d, counter):
 
 # kernels the library names without their (code-variant) template arguments
 PLAIN = {"conv3d_wino44_kernel", "conv3d_wino2p_kernel"}
+# kernels the library reports under another kernel's name (the F(4,3) x F(4,3) tile's 16 x 4 geometry)
+ALIAS = {"conv3d_wino44_kernel_16x4": "conv3d_wino44_kernel"}
 
 
 def short(n):
@@ -42,7 +44,7 @@ def short(n):
             return m.group(1)
         return f"{m.group(1)}<{m.group(2)}>"
     m = re.search(r"lea::(?:\w+::)*(\w+)\(", n)
-    return m.group(1) if m else None
+    return ALIAS.get(m.group(1), m.group(1)) if m else None
 
 
 fetch, names = load(sys.argv[1], "FETCH_SIZE")
