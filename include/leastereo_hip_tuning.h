@@ -4,10 +4,17 @@
  *
  * Each hook overrides a planner choice of one engine for A/B measurements and the
  * sweep tools under tools/ (conv_sweep.py, wino_sweep.py, wino2_sweep.py,
- * resample_probe.py, gpu_ab.sh via the LEASTEREO_* variables of _lib.py).  The
- * settings are process-wide (every host thread sees them) and take effect on the
- * next launch; callers of the hot path never need them.  Each returns 0, or
- * LEA_E_INVALID for an out-of-range value (nothing changed).
+ * resample_probe.py, gpu_ab.sh via the LEASTEREO_* variables of _lib.py); callers of
+ * the hot path never need them.
+ *
+ * How the state is organised: every hook is one plain variable of the library (three for
+ * the tile overrides), process-wide -- every host thread sees it -- and read by the next
+ * launch or host query.  Nothing locks them: set hooks only while no other thread launches
+ * or queries (a launch that overlaps a set may plan with either value; lea_rectify_set_tile
+ * alone is atomic).  Each setter returns 0, or LEA_E_INVALID for an out-of-range value
+ * (nothing changed).  There is no reset call and a default may change between releases, so
+ * code that flips a hook reads it first and puts that value back: lea_tuning_get /
+ * lea_tuning_name below are the way to read and restore them (_lib.tuning() in Python).
  */
 #ifndef LEASTEREO_HIP_TUNING_H
 #define LEASTEREO_HIP_TUNING_H
@@ -15,6 +22,16 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
+
+/* The current arguments of the hook whose setter is named `setter` (e.g.
+ * "lea_conv3d_wino44_set"), written to values[0 .. n): calling the setter with them changes
+ * nothing.  Returns n (1, or 3 for the *_set_tile_override hooks), or -1 (lea_last_error set)
+ * for an unknown name, values == NULL or capacity < n. */
+int lea_tuning_get(const char* setter, int* values, int capacity);
+
+/* The name of the i-th hook's setter, i = 0, 1, ..: every setter declared below, in no
+ * particular order; NULL past the end. */
+const char* lea_tuning_name(int i);
 
 /* Direct k = 3 engine: force the (NT, TW, TD) tile (nt <= 0 restores the planner).
  * A tile not instantiated for the conv's cout block makes the conv return

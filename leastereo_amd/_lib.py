@@ -4,6 +4,7 @@ Loading fails loudly: there is no CPU or eager fallback for the hot path.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 import threading
@@ -168,6 +169,8 @@ SIGNATURES = {
     "lea_conv3d_bf16_set_stream1x1": (_i, [_i]),
     "lea_conv3d_wino_set_small_cout": (_i, [_i]),
     "lea_conv3d_wino_set_block48": (_i, [_i]),
+    "lea_tuning_get": (_i, [ctypes.c_char_p, ctypes.POINTER(_i), _i]),
+    "lea_tuning_name": (ctypes.c_char_p, [_i]),
     # stem0 over the cost volume, factored through 2D maps
     "lea_cv_stem_split_weights": (_i, [_p, _p, _p, _i, _i, _p]),
     "lea_cv_stem_combine": (_i, [_p, _i64, _p, _i64, _p, _p, _p, _i64, _i, _i, _i, _i, _i, _u, _i,
@@ -278,3 +281,39 @@ def check(rc: int, what: str):
     if rc != 0:
         msg = load().lea_last_error().decode(errors="replace")
         raise HipKernelError(f"{what} failed (rc={rc}): {msg}")
+
+
+def tuning_get(setter: str) -> tuple:
+    """The current arguments of the tuning hook `setter` (lea_tuning_get)."""
+    vals = (_i * 3)()
+    n = load().lea_tuning_get(setter.encode(), vals, 3)
+    if n < 0:
+        raise HipKernelError(load().lea_last_error().decode(errors="replace"))
+    return tuple(vals[:n])
+
+
+def tuning_names() -> list:
+    """Every tuning hook's setter (lea_tuning_name)."""
+    lib, names = load(), []
+    while (name := lib.lea_tuning_name(len(names))) is not None:
+        names.append(name.decode())
+    return names
+
+
+@contextlib.contextmanager
+def tuning(**settings):
+    """Set tuning hooks (setter name = an int, or a tuple for the tile overrides; None = leave it,
+    for a block that calls the setter itself) for the block and put back what they held before, in
+    reverse order, also when the block or a later setting raises.  The hooks are process-wide: not
+    for use beside launches from other threads."""
+    lib, before = load(), []
+    try:
+        for setter, value in settings.items():
+            before.append((setter, tuning_get(setter)))
+            if value is not None:
+                args = tuple(value) if isinstance(value, (tuple, list)) else (value,)
+                check(getattr(lib, setter)(*args), f"{setter}{args}")
+        yield
+    finally:
+        for setter, args in reversed(before):
+            check(getattr(lib, setter)(*args), f"{setter}{args}")

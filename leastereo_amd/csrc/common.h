@@ -28,6 +28,32 @@ namespace lea {
 void set_error(const char* fmt, ...);
 void clear_error();
 
+// The tuning hooks (leastereo_hip_tuning.h) are plain process-wide variables beside the planner
+// that reads them; this table (storage in capi.hip) lists every setter with a way to read its
+// current arguments, for lea_tuning_get / lea_tuning_name.  Launch paths never go through it.
+struct TuningHook {
+  const char* setter;  // exported name
+  int nargs;           // 1, or 3 for the tile overrides
+  void (*get)(int* v);
+};
+struct TuningRegistrar {
+  TuningRegistrar(const char* setter, int nargs, void (*get)(int*));
+};
+// registers `setter`; the trailing statements write its current arguments to int* v
+#define LEA_TUNING_HOOK(setter, nargs, ...) \
+  static ::lea::TuningRegistrar lea_tuning_reg_##setter(#setter, nargs, [](int* v) { __VA_ARGS__; });
+// int variable `var` (default dflt) with its setter for lo <= value <= hi, registered;
+// `text` is the printf tail of the error message after "setter: " (one %d)
+#define LEA_TUNING_INT(setter, var, dflt, lo, hi, text)    \
+  int var = dflt;                                          \
+  extern "C" int setter(int value) {                       \
+    ::lea::clear_error();                                  \
+    LEA_CHECK_ARG(value >= (lo) && value <= (hi), #setter ": " text, value); \
+    var = value;                                           \
+    return 0;                                              \
+  }                                                        \
+  LEA_TUNING_HOOK(setter, 1, v[0] = var)
+
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 // Map a launch result to the ABI return code, recording the HIP error string.

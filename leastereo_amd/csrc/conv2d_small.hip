@@ -131,7 +131,7 @@ __global__ __launch_bounds__(256) void conv2d_small_kernel(const ConvArgs a) {
   }
 }
 
-int g_conv2d_small = 1;  // lea_conv2d_set_small
+LEA_TUNING_INT(lea_conv2d_set_small, g_conv2d_small, 1, 0, 1, "on=%d")
 
 bool conv2d_small_ok(int cin, int cout) { return g_conv2d_small && cin <= 16 && cout <= 32; }
 
@@ -162,16 +162,6 @@ int run_conv2d_small(const ConvArgs& a, int B, hipStream_t st) {
 }
 
 }  // namespace lea
-
-extern "C" int lea_conv2d_set_small(int on) {
-  lea::clear_error();
-  if (on != 0 && on != 1) {
-    lea::set_error("lea_conv2d_set_small: on=%d", on);
-    return LEA_E_INVALID;
-  }
-  lea::g_conv2d_small = on;
-  return 0;
-}
 
 extern "C" int lea_conv2d_bnrelu_pair(const void* x, int64_t x_bstride, const float* w_packed,
                                       const float* scale, const float* shift, const void* residual,

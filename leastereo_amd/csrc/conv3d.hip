@@ -597,7 +597,7 @@ inline bool prefer_tw64(int W) {
 
 // lea_conv3d_set_rs_gather: 1 (default) = the resampled 1x1 convs on the gather-GEMM
 // (conv1x1_rs_f32_kernel), 0 = the register-staged engine
-int g_rs_gather = 1;
+LEA_TUNING_INT(lea_conv3d_set_rs_gather, g_rs_gather, 1, 0, 1, "on=%d")
 
 inline Plan make_plan(int B, int cout, int D, int H, int W, int k, bool resample) {
   Plan p;
@@ -689,7 +689,8 @@ int run_rs(const ConvArgs& a, int tw, int B, hipStream_t st) {
   return launch(conv3d_reg_kernel<KS, MT, NT, 32, true>, a, LEA_TILE_TH(KS, MT, NT, 32), 32, B, st);
 }
 
-int g_1x1_vec = 1;  // lea_conv1x1_set_vector: the NT-float vector form of conv1x1_kernel
+// the NT-float vector form of conv1x1_kernel
+LEA_TUNING_INT(lea_conv1x1_set_vector, g_1x1_vec, 1, 0, 1, "on=%d")
 
 // hb: the second head of lea_conv1x1_heads (null: the single-output kernel)
 template <int MT, int NT>
@@ -858,20 +859,6 @@ extern "C" const char* lea_conv3d_kernel_name(int B, int cout, int D, int H, int
   return lea::plan_name(lea::make_plan(B, cout, D, H, W, k, resample != 0), k);
 }
 
-extern "C" int lea_conv3d_set_rs_gather(int on) {
-  lea::clear_error();
-  LEA_CHECK_ARG(on == 0 || on == 1, "lea_conv3d_set_rs_gather: on=%d", on);
-  lea::g_rs_gather = on;
-  return 0;
-}
-
-extern "C" int lea_conv1x1_set_vector(int on) {
-  lea::clear_error();
-  LEA_CHECK_ARG(on == 0 || on == 1, "lea_conv1x1_set_vector: on=%d", on);
-  lea::g_1x1_vec = on;
-  return 0;
-}
-
 extern "C" int lea_conv3d_set_tile_override(int nt, int tw, int td) {
   lea::clear_error();
   if (nt <= 0) {
@@ -886,6 +873,7 @@ extern "C" int lea_conv3d_set_tile_override(int nt, int tw, int td) {
   lea::g_tile_override[2] = td;
   return 0;
 }
+LEA_TUNING_HOOK(lea_conv3d_set_tile_override, 3, for (int i = 0; i < 3; ++i) v[i] = lea::g_tile_override[0] > 0 ? lea::g_tile_override[i] : 0)
 
 extern "C" size_t lea_conv3d_packed_floats(int cout, int cin, int k) {
   if (cout <= 0 || cin <= 0 || (k != 1 && k != 3)) return 0;

@@ -1218,11 +1218,12 @@ struct Plan {
 };
 
 int g_override[3] = {0, 0, 0};  // th, td, mt (lea_conv3d_bf16_set_tile_override)
-int g_variant = 0;              // lea_conv3d_bf16_set_variant: 0 planner, 1 tile kernel only
-int g_stream1x1 = 1;            // lea_conv3d_bf16_set_stream1x1
-int g_pair_split = 3;           // lea_conv3d_bf16_set_pair_split: LEA_PAIR_SUM on the split-wave kernel
-                                // (2: the plane-paired tile for the 8 -> 8 steps; 3: that, and the
-                                // 16-channel steps on the two-source D-streaming kernel)
+// 0 planner, 1 tile kernel only
+LEA_TUNING_INT(lea_conv3d_bf16_set_variant, g_variant, 0, 0, 1, "bad variant %d")
+LEA_TUNING_INT(lea_conv3d_bf16_set_stream1x1, g_stream1x1, 1, 0, 1, "on=%d")
+// LEA_PAIR_SUM on the split-wave kernel (2: the plane-paired tile for the 8 -> 8 steps; 3: that,
+// and the 16-channel steps on the two-source D-streaming kernel)
+LEA_TUNING_INT(lea_conv3d_bf16_set_pair_split, g_pair_split, 3, 0, 3, "%d")
 // conv1x1_rs_c8_kernel: tiles per wave (r05 probe at the C4 shapes, tools/rs_probe.py: two tiles'
 // corner loads in flight together 4-5 % faster than one; more tiles per wave slower)
 constexpr int g_rs_tpw = 2;
@@ -1429,27 +1430,7 @@ extern "C" int lea_conv3d_bf16_set_tile_override(int th, int td, int mt) {
   bf::g_override[2] = mt;
   return 0;
 }
-
-extern "C" int lea_conv3d_bf16_set_stream1x1(int on) {
-  clear_error();
-  LEA_CHECK_ARG(on == 0 || on == 1, "lea_conv3d_bf16_set_stream1x1: on=%d", on);
-  bf::g_stream1x1 = on;
-  return 0;
-}
-
-extern "C" int lea_conv3d_bf16_set_pair_split(int on) {
-  clear_error();
-  LEA_CHECK_ARG(on >= 0 && on <= 3, "lea_conv3d_bf16_set_pair_split: %d", on);
-  bf::g_pair_split = on;
-  return 0;
-}
-
-extern "C" int lea_conv3d_bf16_set_variant(int variant) {
-  clear_error();
-  LEA_CHECK_ARG(variant == 0 || variant == 1, "lea_conv3d_bf16_set_variant: bad variant %d", variant);
-  bf::g_variant = variant;
-  return 0;
-}
+LEA_TUNING_HOOK(lea_conv3d_bf16_set_tile_override, 3, for (int i = 0; i < 3; ++i) v[i] = bf::g_override[0] > 0 ? bf::g_override[i] : 0)
 
 extern "C" size_t lea_conv3d_packed_elems_bf16(int cout, int cin, int k) {
   if (cout <= 0 || cin <= 0 || cin % 8 != 0 || (k != 1 && k != 3)) return 0;
@@ -1623,15 +1604,8 @@ extern "C" int lea_from_c8_bf16(const void* x, int64_t x_bstride, float* y, int6
 // resample words per thread (lea_resample_bf16_set_batch; 0 = up-sampling 4, else 1)
 static int g_resample_k = 0;
 
-// 1 (default) = up-samplings on the column-walking kernel (lea_resample_bf16_set_cols)
-static int g_resample_cols = 1;
-
-extern "C" int lea_resample_bf16_set_cols(int on) {
-  clear_error();
-  LEA_CHECK_ARG(on >= 0 && on <= 2, "lea_resample_bf16_set_cols: %d", on);
-  g_resample_cols = on;
-  return 0;
-}
+// 1 (default) = up-samplings on the column-walking kernel
+static LEA_TUNING_INT(lea_resample_bf16_set_cols, g_resample_cols, 1, 0, 2, "%d")
 
 extern "C" int lea_resample_bf16_set_batch(int k) {
   clear_error();
@@ -1639,6 +1613,7 @@ extern "C" int lea_resample_bf16_set_batch(int k) {
   g_resample_k = k;
   return 0;
 }
+LEA_TUNING_HOOK(lea_resample_bf16_set_batch, 1, v[0] = g_resample_k)
 
 extern "C" int lea_resample3d_trilinear_bf16(const void* x, int64_t x_bstride, void* y,
                                              int64_t y_bstride, int B, int C, int Di, int Hi,

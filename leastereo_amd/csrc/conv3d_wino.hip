@@ -768,37 +768,44 @@ __global__ void pack_wino_dp_kernel(const float* __restrict__ w, float* __restri
   }
 }
 
-struct Plan {
-  int f, q, mt, np, td;
-  bool d2;   // two-dimensional engine (conv3d_wino2.hip) with tile p2
-  Plan2 p2;
-  bool h16;  // 1-D engine: halo staged as 16-byte pieces (plan_halo16)
-};
-
+// ---- the tuning hooks of the Winograd entries (leastereo_hip_tuning.h): route() below is the
+// only reader of the routing ones; host_mt (the packed layout) reads small_cout and block48 ----
 int g_override[3] = {0, 0, 0};  // np, td, f (lea_conv3d_wino_set_tile_override)
-// lea_conv3d_wino_set_variant: 0 = the planner's choice (5), 1 = F(4,3)-along-W engine only,
+// 0 = the planner's choice (5), 1 = F(4,3)-along-W engine only,
 // 2..4 = the W x D engine's tiles where it applies (2: four waves, one cout tile each;
 // 3: eight waves; 4: two cout tiles per wave at one wave per SIMD), 5..7 = the same
 // with the inputs transformed once per chunk into LDS (32-cout blocks; 16-cout blocks
 // keep 2)
-int g_variant = 0;
-int g_spw = 0;  // lea_conv3d_wino2_set_walk: depth pairs per workgroup (0 = planner)
-// lea_conv3d_wino_set_small_cout: couts <= 8 packed / planned as 16-row blocks for the
-// W x D engine (1) or depth-paired for the 1-D engine (0, the default: r02 sweep, L0 8->8
-// 175 us depth-paired vs 210 us on the W x D engine's half-empty 16-row block)
-int g_small16 = 0;
-// lea_conv3d_wino_set_block48: 48k-cout layers as 48-row blocks of the 1-D engine (1) or
-// as 32-row blocks of the W x D engine, the last one padded (0)
-int g_block48 = 1;
-int g_epibuf = 1;  // lea_conv3d_wino_set_epi_buf
-int g_halo16 = 1;  // lea_conv3d_wino2_set_halo16
-int g_pipe = 1;    // lea_conv3d_wino2_set_pipeline
-int g_wpre = 1;    // lea_conv3d_wino2p_set_wpre (r06: -0.7 % on the kernel, bit-identical)
-int g_fence = 1;   // lea_conv3d_wino_set_fence: the depth-paired 16-byte-halo tile's fenced schedule (r04 default)
-int g_lane16 = 2;  // lea_conv3d_wino2_set_lane_halo16 (2: the fenced step schedule, PV = 5; r04 default)
-// lea_conv3d_wino_set_w22: layers on the F(2,3) x F(2,3) tile (conv3d_wino22.hip): 0 none (LEA_PAIR_SUM
-// always), 1 the 16-cout layers, 2 every cout <= 32
-int g_w22 = 0;
+LEA_TUNING_INT(lea_conv3d_wino_set_variant, g_variant, 0, 0, 7, "bad variant %d")
+// depth pairs per workgroup (0 = planner)
+LEA_TUNING_INT(lea_conv3d_wino2_set_walk, g_spw, 0, 0, 64, "spw=%d")
+// couts <= 8 packed / planned as 16-row blocks for the W x D engine (1) or depth-paired for the
+// 1-D engine (0, the default: r02 sweep, L0 8->8 175 us depth-paired vs 210 us on the W x D
+// engine's half-empty 16-row block)
+LEA_TUNING_INT(lea_conv3d_wino_set_small_cout, g_small16, 0, 0, 1, "mode=%d")
+// 48k-cout layers as 48-row blocks of the 1-D engine (1) or as 32-row blocks of the W x D
+// engine, the last one padded (0)
+LEA_TUNING_INT(lea_conv3d_wino_set_block48, g_block48, 1, 0, 1, "on=%d")
+LEA_TUNING_INT(lea_conv3d_wino_set_epi_buf, g_epibuf, 1, 0, 1, "on=%d")
+LEA_TUNING_INT(lea_conv3d_wino2_set_halo16, g_halo16, 1, 0, 1, "on=%d")
+LEA_TUNING_INT(lea_conv3d_wino2_set_pipeline, g_pipe, 1, 0, 1, "on=%d")
+// (r06: -0.7 % on the kernel, bit-identical)
+LEA_TUNING_INT(lea_conv3d_wino2p_set_wpre, g_wpre, 1, 0, 1, "on=%d")
+// the depth-paired 16-byte-halo tile's fenced schedule (r04 default)
+LEA_TUNING_INT(lea_conv3d_wino_set_fence, g_fence, 1, 0, 1, "on=%d")
+// (2: the fenced step schedule, PV = 5; r04 default)
+LEA_TUNING_INT(lea_conv3d_wino2_set_lane_halo16, g_lane16, 2, 0, 2, "on=%d")
+// layers on the F(2,3) x F(2,3) tile (conv3d_wino22.hip): 0 none (LEA_PAIR_SUM always), 1 the
+// 16-cout layers, 2 every cout <= 32
+LEA_TUNING_INT(lea_conv3d_wino_set_w22, g_w22, 0, 0, 2, "on=%d")
+// the F(4,3) x F(4,3) tile (conv3d_wino44.hip) on the pipelined W x D kernel's layers (r06 default
+// 1: -9.5 % on its layers, profiles/r06_w44_ab.txt; 2 since v45, after the LDS-conflict fixes: the
+// L0 8 -> 24 group 275.6 -> 259.7 us, profiles/r06_w44_modes_ab.txt)
+LEA_TUNING_INT(lea_conv3d_wino44_set, g_w44, 2, 0, 3, "on=%d")
+LEA_TUNING_INT(lea_conv3d_wino44_set_upre, g_w44u, 0, 0, 1, "on=%d")
+LEA_TUNING_INT(lea_conv3d_wino44_set_sched, g_w44s, 0, 0, 3, "%d")
+int g_w44t = -1;  // lea_conv3d_wino44_set_tile (-1: auto)
+
 inline int host_mt(int cout) {
   if (g_small16 && cout <= 8) return 1;
   const int mt = mt_of(cout);
@@ -825,7 +832,7 @@ inline long long u22_offset(int cout, int cin) {
 // W x D engine tile for variant v (2..4), or nullptr-equivalent (q = 0) when the
 // layer's cout block has no such tile (couts <= 8 and the 48-row blocks stay 1-D)
 inline Plan2 plan2(int v, int mt, int q) {
-  Plan2 t{0, 0, 0, 0, 0, 0, 0};
+  Plan2 t{};
   if (mt != 1 && mt != 2) return t;
   if (v >= 5) {
     t.pv = mt == 2 ? 1 : 0;
@@ -847,106 +854,124 @@ inline Plan2 plan2(int v, int mt, int q) {
   return t;
 }
 
-inline Plan make_plan(int B, int cout, int D, int H, int W) {
+// The one routing decision of the f32 Winograd entries.
+Route route(int B, int cin, int cout, int D, int H, int W, bool cv, bool pair, const ConvArgs* a) {
+  ConvArgs shape{};  // a == NULL: NULL pointers and zero strides are aligned operands
+  if (!a) {
+    shape.cin = shape.cin1 = cin;
+    shape.cout = cout;
+    shape.D = D;
+    shape.H = H;
+    shape.W = W;
+    a = &shape;
+  }
+  Route r{};
+  r.cv = cv;
+  r.spw = g_spw;
+  r.planner = g_variant == 0 && g_override[0] == 0;
+  r.epi = g_epibuf && epi_buf_ok(*a);
+  r.mt = host_mt(cout);
+  // LEA_PAIR_SUM has this tile only (common() checked wino22_ok); lea_conv3d_wino_set_w22 puts
+  // the 16-cout layers (2: every cout <= 32) on it
+  if (pair || (g_w22 && !cv && (r.mt == 1 || g_w22 == 2) && r.planner && wino22_ok(*a))) {
+    r.e = Engine::Wino22;
+    return r;
+  }
   // r01 sweeps (tools/wino_sweep.py, profiles/r01_wino_sweep*.txt): F(4,3) on
   // 64-wide tile rows where they waste little of W (the L0 volumes), else on
   // 32-wide row pairs (L1, L2), F(2,3) for the 48-row blocks (their LDS budget);
   // two output planes per workgroup unless the volume is too shallow to fill the chip.
-  Plan p;
-  p.h16 = false;
-  p.mt = host_mt(cout);
-  const long long ncob = (cout + cop_of(p.mt) - 1) / cop_of(p.mt);
+  r.e = Engine::Tile1D;
+  const long long ncob = (cout + cop_of(r.mt) - 1) / cop_of(r.mt);
   auto fits = [&](int tw) { return (W + tw - 1) / tw * tw * 10 <= W * 11; };  // <= 10 % padding
-  p.f = 2;
-  p.q = 16;
-  if (p.mt != 3) {
-    p.f = 4;
-    if (!fits(64)) p.q = 8;  // F(4,3) over 32-wide row pairs: F(2,3)'s tile width, 3/4 its MFMAs
+  r.f = 2;
+  r.q = 16;
+  if (r.mt != 3) {
+    r.f = 4;
+    if (!fits(64)) r.q = 8;  // F(4,3) over 32-wide row pairs: F(2,3)'s tile width, 3/4 its MFMAs
   } else if (fits(32)) {
-    p.f = 4;  // 48-row blocks: row pairs one plane deep fit the LDS (F(2,3) otherwise)
-    p.q = 8;
+    r.f = 4;  // 48-row blocks: row pairs one plane deep fit the LDS (F(2,3) otherwise)
+    r.q = 8;
   }
   auto wgs = [&](int np, int td) {
-    const int tw = p.f * p.q, th = 4 * np * (16 / p.q);
+    const int tw = r.f * r.q, th = 4 * np * (16 / r.q);
     return (long long)((W + tw - 1) / tw) * ((H + th - 1) / th) * ((D + td - 1) / td) * B * ncob;
   };
-  p.np = (p.f == 2 && p.mt == 2 && wgs(2, 2) >= 512) ? 2 : 1;
-  p.td = (wgs(p.np, 2) >= 384 && !(p.mt == 3 && p.f == 4)) ? 2 : 1;
+  r.np = (r.f == 2 && r.mt == 2 && wgs(2, 2) >= 512) ? 2 : 1;
+  r.td = (wgs(r.np, 2) >= 384 && !(r.mt == 3 && r.f == 4)) ? 2 : 1;
   if (g_override[0] > 0) {
-    p.np = g_override[0];
-    p.td = g_override[1];
+    r.np = g_override[0];
+    r.td = g_override[1];
     if (g_override[2] > 0) {
-      p.f = g_override[2] == 8 ? 4 : g_override[2];
-      p.q = g_override[2] == 8 ? 8 : 16;
+      r.f = g_override[2] == 8 ? 4 : g_override[2];
+      r.q = g_override[2] == 8 ? 8 : 16;
     }
   }
-  if (p.mt == 0) {  // depth-paired: F(4,3), one row set, two planes (the instantiated tiles)
-    p.f = 4;
-    p.np = 1;
-    p.td = 2;
+  if (r.mt == 0) {  // depth-paired: F(4,3), one row set, two planes (the instantiated tiles)
+    r.f = 4;
+    r.np = 1;
+    r.td = 2;
   }
-  p.d2 = false;
   // r02 sweep (tools/wino2_sweep.py, profiles/r02_wino2_sweep.txt): the W x D engine
   // with the per-chunk transform pass wins on every 32-cout block (stem0 -14 %,
   // conv1/2 -14 %), the per-lane form on the 16-cout L1 cells (-11 %)
   // (a 1-D tile override from the tuning tools keeps the planner on the 1-D engine)
   const int v = g_variant == 0 ? (g_override[0] > 0 ? 1 : 5) : g_variant;
   if (v >= 2) {
-    p.p2 = plan2(v, p.mt, fits(64) ? 16 : 8);
-    p.d2 = p.p2.q > 0;
-    if (g_spw > 0) p.p2.spw = g_spw;
+    r.p2 = plan2(v, r.mt, fits(64) ? 16 : 8);
+    if (r.p2.q > 0) r.e = Engine::Tile2D;
   }
-  return p;
+  // 16-byte LDS-DMA halo pieces (4 per channel instead of 13 dword pieces) when rows are whole
+  // 16-byte blocks: W % 4 == 0 and 16-byte aligned channel bases (r03 stamps: the DMA issue held
+  // 25-27 % of the kernel's wave cycles with dword pieces).  Plain volumes only (not the cost volume).
+  const bool h16 = !cv && g_halo16 && W % 4 == 0 && ((uintptr_t)a->x & 15) == 0 && a->xbs % 4 == 0 &&
+                   (a->cin1 == a->cin || (((uintptr_t)a->x2 & 15) == 0 && a->x2bs % 4 == 0));
+  if (r.e == Engine::Tile1D) {
+    // the depth-paired 64-wide tile (the L0 8-channel cell ops)
+    r.h16 = h16 && r.mt == 0 && r.f == 4 && r.q == 16 && r.np == 1 && r.td == 2;
+    r.fence = r.h16 && g_fence;
+    return r;
+  }
+  if (!h16) return r;
+  Plan2& t = r.p2;
+  // the one-barrier pipeline uses the buffer-addressed epilogue only
+  // (layers of one or two chunks per depth pair stay on the two-barrier tile: L0 8->24
+  // ran 286 us there, 296-301 us pipelined -- r03 sweeps)
+  // (g_w44 == 2: the two-chunk layers -- L0 8 -> 24 -- on the F(4,3) x F(4,3) tile too)
+  const bool pipe = g_pipe && r.epi && (cin == 0 || cin > 2 * CIN_B || (g_w44 >= 2 && cin > CIN_B));
+  if (t.pv == 1 && t.nw == 4 && t.mte == 1) t.pv = pipe ? 3 : 2;
+  // the per-lane 16-cout tile (the L1 cells): 16-byte pieces, interleaved row sets (r04)
+  if (g_lane16 && t.pv == 0 && t.q == 8 && t.wc == 1 && t.mte == 1 && t.nw == 4 && t.occ == 2)
+    t.pv = g_lane16 == 2 ? 5 : 4;
+  // g_w44 == 3 (r06 experiment): the 16-cout layers on the F(4,3) x F(4,3) tile as half-empty
+  // 32-cout blocks (the pipelined tile's plan: pv 3 with two cout tiles)
+  if (g_w44 == 3 && pipe && r.mt == 1 && (t.pv == 4 || t.pv == 5)) {
+    t.pv = 3;
+    t.wc = 2;
+  }
+  if (t.pv != 3) return r;
+  // the pipelined tile's layers: conv3d_wino2p_kernel, or F(4,3) x F(4,3) on the same layers (r06)
+  r.e = g_w44 ? Engine::Wino44 : Engine::Wino2p;
+  r.wpre = g_wpre;
+  r.upre = g_w44u;
+  r.sched = g_w44s;
+  // The F(4,3) x F(4,3) geometry: auto takes the narrow tile where it pads fewer columns (C2's
+  // quarter-resolution volumes: W = 80 is 2.5 wide tiles, and 288 / 864 workgroups against 256
+  // CUs x 2 become 240 / 720).  The rule also takes the narrow tile for every W <= 16 and every
+  // W % 32 in 1 .. 16; of those only W = 80 was measured (profiles/w44_narrow_layers_ab.txt), the
+  // others follow from the padding argument alone.  The narrow geometry is built for the default
+  // form only (upre 0, sched 0).
+  auto padded = [&](int tw) { return (W + tw - 1) / tw * tw; };
+  r.geo = (g_w44u || g_w44s != 0) ? 32 : g_w44t > 0 ? g_w44t : padded(16) < padded(32) ? 16 : 32;
+  return r;
 }
 
-// The W x D transform-pass kernel stages its halo as 16-byte LDS-DMA pieces (PV = 2, 4
-// pieces per channel instead of 13 dword pieces) when rows are whole 16-byte blocks:
-// W % 4 == 0 and 16-byte aligned channel bases (r03 stamps: the DMA issue held 25-27 %
-// of the kernel's wave cycles with dword pieces).  Plain volumes only (not the cost volume).
-inline void plan_halo16(Plan& p, bool cv, int W, const ConvArgs* a, int cin = 0) {
-  if (a) cin = a->cin;
-  p.h16 = false;
-  if (cv || !g_halo16 || W % 4 != 0) return;
-  if (a) {
-    const bool al = ((uintptr_t)a->x & 15) == 0 && a->xbs % 4 == 0 &&
-                    (a->cin1 == a->cin || (((uintptr_t)a->x2 & 15) == 0 && a->x2bs % 4 == 0));
-    if (!al) return;
-  }
-  if (p.d2) {
-    // the one-barrier pipeline uses the buffer-addressed epilogue only
-    // (layers of one or two chunks per depth pair stay on the two-barrier tile: L0 8->24
-    // ran 286 us there, 296-301 us pipelined -- r03 sweeps)
-    // (g_w44 == 2: the two-chunk layers -- L0 8 -> 24 -- on the F(4,3) x F(4,3) tile too)
-    const bool pipe = g_pipe && g_epibuf && (a == nullptr || epi_buf_ok(*a)) &&
-                      (cin == 0 || cin > 2 * CIN_B || (g_w44 >= 2 && cin > CIN_B));
-    if (p.p2.pv == 1 && p.p2.nw == 4 && p.p2.mte == 1) p.p2.pv = pipe ? 3 : 2;
-    // the per-lane 16-cout tile (the L1 cells): 16-byte pieces, interleaved row sets (r04)
-    if (g_lane16 && p.p2.pv == 0 && p.p2.q == 8 && p.p2.wc == 1 && p.p2.mte == 1 && p.p2.nw == 4 &&
-        p.p2.occ == 2)
-      p.p2.pv = g_lane16 == 2 ? 5 : 4;
-    // g_w44 == 3 (r06 experiment): the 16-cout layers on the F(4,3) x F(4,3) tile as half-empty
-    // 32-cout blocks (the pipelined tile's plan: pv 3 with two cout tiles)
-    if (g_w44 == 3 && pipe && p.mt == 1 && (p.p2.pv == 4 || p.p2.pv == 5)) {
-      p.p2.pv = 3;
-      p.p2.wc = 2;
-    }
-  } else if (p.mt == 0 && p.f == 4 && p.q == 16 && p.np == 1 && p.td == 2) {
-    p.h16 = true;  // the depth-paired 64-wide tile (the L0 8-channel cell ops)
-  }
-}
-
-#define LEA_WINO_CASE(F, Q, MT, NP, TD, CV)                                                   \
-  if (p.f == F && p.q == Q && p.mt == MT && p.np == NP && p.td == TD) {                       \
-    using C_ = Cfg<F, Q, MT, NP, TD>;                                                         \
-    a.tiles_w = (a.W + C_::TW - 1) / C_::TW;                                                  \
-    a.ntiles = a.tiles_w * ((a.H + C_::TH - 1) / C_::TH);                                     \
-    a.ndz = (a.D + TD - 1) / TD;                                                              \
-    a.spw = std::max(1, std::min(g_spw > 0 ? g_spw : auto_walk(a, B, 2), a.ndz));             \
-    const long long n_ = (long long)a.ntiles * ((a.ndz + a.spw - 1) / a.spw) * B * a.ncob;    \
-    LEA_CHECK_ARG(n_ < (1LL << 31), "lea_conv3d(wino): grid too large");                      \
-    a.nblk = (int)n_;                                                                         \
-    conv3d_wino_kernel<F, Q, MT, NP, TD, CV><<<dim3((unsigned)n_), kConvThreads, 0, st>>>(a); \
-    return launch_status("lea_conv3d(wino)");                                                \
+#define LEA_WINO_CASE(F, Q, MT, NP, TD, CV)                                                              \
+  if (r.f == F && r.q == Q && r.mt == MT && r.np == NP && r.td == TD) {                                  \
+    using C_ = Cfg<F, Q, MT, NP, TD>;                                                                    \
+    if (!name)                                                                                           \
+      if (int rc = grid(a, B, C_::TW, C_::TH, TD, cop_of(MT), 2, r.spw, "lea_conv3d(wino)")) return rc;  \
+    LEA_WINO_KERNEL("lea_conv3d(wino)", kConvThreads, conv3d_wino_kernel<F, Q, MT, NP, TD, CV>);         \
   }
 #define LEA_WINO_TILES(CV)                                                                                  \
   LEA_WINO_CASE(2, 16, 1, 1, 1, CV) LEA_WINO_CASE(2, 16, 1, 1, 2, CV) LEA_WINO_CASE(2, 16, 1, 2, 1, CV)     \
@@ -957,40 +982,44 @@ inline void plan_halo16(Plan& p, bool cv, int W, const ConvArgs* a, int cin = 0)
   LEA_WINO_CASE(4, 8, 1, 1, 2, CV) LEA_WINO_CASE(4, 8, 2, 1, 1, CV) LEA_WINO_CASE(4, 8, 2, 1, 2, CV)      \
   LEA_WINO_CASE(4, 8, 3, 1, 1, CV) LEA_WINO_CASE(4, 16, 0, 1, 2, CV) LEA_WINO_CASE(4, 8, 0, 1, 2, CV)
 
-int run(const Plan& p, ConvArgs a, int B, hipStream_t st, bool cv) {
-  if (p.d2) return run2(p.p2, a, B, st, cv);
-  a.ncob = (a.cout + cop_of(p.mt) - 1) / cop_of(p.mt);
-  if (p.h16) {
+// Engine::Tile1D
+int run1(const Route& r, ConvArgs a, int B, hipStream_t st, const char** name) {
+  if (r.h16) {
     using C_ = Cfg<4, 16, 0, 1, 2, true>;
-    a.tiles_w = (a.W + C_::TW - 1) / C_::TW;
-    a.ntiles = a.tiles_w * ((a.H + C_::TH - 1) / C_::TH);
-    a.ndz = (a.D + 1) / 2;
-    a.spw = std::max(1, std::min(g_spw > 0 ? g_spw : auto_walk(a, B, 2), a.ndz));
-    const long long n_ = (long long)a.ntiles * ((a.ndz + a.spw - 1) / a.spw) * B * a.ncob;
-    LEA_CHECK_ARG(n_ < (1LL << 31), "lea_conv3d(wino): grid too large");
-    a.nblk = (int)n_;
-    if (g_fence)
-      conv3d_wino_kernel<4, 16, 0, 1, 2, false, true, true><<<dim3((unsigned)n_), kConvThreads, 0, st>>>(a);
+    if (!name)
+      if (int rc = grid(a, B, C_::TW, C_::TH, 2, cop_of(0), 2, r.spw, "lea_conv3d(wino)")) return rc;
+    if (r.fence)
+      LEA_WINO_KERNEL("lea_conv3d(wino)", kConvThreads, conv3d_wino_kernel<4, 16, 0, 1, 2, false, true, true>);
     else
-      conv3d_wino_kernel<4, 16, 0, 1, 2, false, true><<<dim3((unsigned)n_), kConvThreads, 0, st>>>(a);
-    return launch_status("lea_conv3d(wino)");
+      LEA_WINO_KERNEL("lea_conv3d(wino)", kConvThreads, conv3d_wino_kernel<4, 16, 0, 1, 2, false, true>);
   }
-  if (cv) {
+  if (r.cv) {
     LEA_WINO_TILES(true)
   } else {
     LEA_WINO_TILES(false)
   }
-  set_error("lea_conv3d(wino): no tile f=%d q=%d mt=%d np=%d td=%d", p.f, p.q, p.mt, p.np, p.td);
+  if (name) {  // a tile override nothing is instantiated for: the name it would have (a launch fails)
+    thread_local char none[96];
+    snprintf(none, sizeof(none), "conv3d_wino_kernel<%d, %d, %d, %d, %d, %s>", r.f, r.q, r.mt, r.np, r.td,
+             r.cv ? "true" : "false");
+    *name = none;
+    return LEA_OK;
+  }
+  set_error("lea_conv3d(wino): no tile f=%d q=%d mt=%d np=%d td=%d", r.f, r.q, r.mt, r.np, r.td);
   return LEA_E_UNSUPPORTED;
 }
 
-thread_local char g_name[96];
-
-const char* name(const Plan& p, bool cv) {
-  if (p.d2) return name2(p.p2, cv);
-  snprintf(g_name, sizeof(g_name), "conv3d_wino_kernel<%d, %d, %d, %d, %d, %s%s>", p.f, p.q, p.mt, p.np,
-           p.td, cv ? "true" : "false", p.h16 ? (g_fence ? ", true, true" : ", true") : "");
-  return g_name;
+// launch the route, or (name != NULL) answer its kernel's name
+int run(const Route& r, ConvArgs a, int B, hipStream_t st, const char** name) {
+  if (r.e == Engine::Wino22) {
+    a.uoff = u22_offset(a.cout, a.cin);
+    return run22(r, a, B, st, name);
+  }
+  if (r.epi) a.flags |= kEpiBuf;
+  if (has_l44(a.cout)) a.uoff = l44_offset(a.cout, a.cin);  // (the F(4,3) x F(4,3) tile's section)
+  if (r.e == Engine::Tile1D) return run1(r, a, B, st, name);
+  if (r.e == Engine::Wino44) return run44(r, a, B, st, name);
+  return run2(r, a, B, st, name);
 }
 
 int common(ConvArgs& a, int B, bool cv, int dtype, void* stream) {
@@ -1012,7 +1041,6 @@ int common(ConvArgs& a, int B, bool cv, int dtype, void* stream) {
     set_error("lea_conv3d(wino): dtype %d unsupported", dtype);
     return LEA_E_UNSUPPORTED;
   }
-  Plan p = make_plan(B, a.cout, a.D, a.H, a.W);
   const bool pair = a.flags & LEA_PAIR_SUM;
   if (pair) {
     LEA_CHECK_ARG(!(a.flags & LEA_RESIDUAL) && a.cin1 > 0 && a.cin1 < a.cin && !cv,
@@ -1022,15 +1050,39 @@ int common(ConvArgs& a, int B, bool cv, int dtype, void* stream) {
       return LEA_E_UNSUPPORTED;
     }
   }
-  if (pair || (g_w22 && !cv && (p.mt == 1 || g_w22 == 2) && g_variant == 0 && g_override[0] == 0 &&
-               wino22_ok(a))) {
-    a.uoff = u22_offset(a.cout, a.cin);
-    return run22(a, B, g_spw, as_stream(stream));
-  }
-  plan_halo16(p, cv, a.W, &a);
-  if (g_epibuf && epi_buf_ok(a)) a.flags |= kEpiBuf;
-  if (has_l44(a.cout)) a.uoff = l44_offset(a.cout, a.cin);  // (the F(4,3) x F(4,3) tile's section)
-  return run(p, a, B, as_stream(stream), cv);
+  return run(route(B, a.cin, a.cout, a.D, a.H, a.W, cv, pair, &a), a, B, as_stream(stream), nullptr);
+}
+
+// the name of the route's kernel (NULL when it has none)
+const char* name_of(const Route& r, int B) {
+  const char* name = nullptr;
+  run(r, ConvArgs{}, B, nullptr, &name);
+  return name;
+}
+
+// the entries' arguments (the flags are theirs to check and set)
+ConvArgs conv_args(const void* x, int64_t x_bstride, const void* x2, int64_t x2_bstride, int cin2,
+                   const float* w_packed, const float* scale, const float* shift, const void* residual,
+                   int64_t r_bstride, void* y, int64_t y_bstride, int cin, int cout, int D, int H, int W) {
+  ConvArgs a{};
+  a.x = (const float*)x;
+  a.xbs = x_bstride;
+  a.x2 = (const float*)x2;
+  a.x2bs = x2_bstride;
+  a.cin1 = cin - cin2;
+  a.wp = w_packed;
+  a.scale = scale;
+  a.shift = shift;
+  a.res = (const float*)residual;
+  a.rbs = r_bstride;
+  a.y = (float*)y;
+  a.ybs = y_bstride;
+  a.cin = cin;
+  a.cout = cout;
+  a.D = D;
+  a.H = H;
+  a.W = W;
+  return a;
 }
 
 }  // namespace wino
@@ -1088,12 +1140,7 @@ extern "C" int lea_conv3d_wino_pack_weights(const float* w, float* packed, int c
 extern "C" const char* lea_conv3d_wino_kernel_name(int B, int cin, int cout, int D, int H, int W,
                                                    int costvolume) {
   if (B <= 0 || cout <= 0 || D <= 0 || H <= 0 || W <= 0) return nullptr;
-  wino::Plan p = wino::make_plan(B, cout, D, H, W);
-  if (wino::g_w22 && !costvolume && (p.mt == 1 || (wino::g_w22 == 2 && cout <= 32)) && wino::g_variant == 0 &&
-      wino::g_override[0] == 0 && W % 4 == 0)
-    return "conv3d_wino22_kernel";  // (assumes 16-byte aligned sources)
-  wino::plan_halo16(p, costvolume != 0, W, nullptr, cin);  // (assumes 16-byte aligned sources)
-  return wino::name(p, costvolume != 0);
+  return wino::name_of(wino::route(B, cin, cout, D, H, W, costvolume != 0, false, nullptr), B);
 }
 
 extern "C" int lea_conv3d_wino_set_tile_override(int np, int td, int f) {
@@ -1109,48 +1156,7 @@ extern "C" int lea_conv3d_wino_set_tile_override(int np, int td, int f) {
   wino::g_override[2] = f;
   return 0;
 }
-
-extern "C" int lea_conv3d_wino_set_block48(int on) {
-  clear_error();
-  LEA_CHECK_ARG(on == 0 || on == 1, "lea_conv3d_wino_set_block48: on=%d", on);
-  wino::g_block48 = on;
-  return 0;
-}
-
-extern "C" int lea_conv3d_wino_set_epi_buf(int on) {
-  clear_error();
-  LEA_CHECK_ARG(on == 0 || on == 1, "lea_conv3d_wino_set_epi_buf: on=%d", on);
-  wino::g_epibuf = on;
-  return 0;
-}
-
-extern "C" int lea_conv3d_wino_set_small_cout(int mode) {
-  clear_error();
-  LEA_CHECK_ARG(mode == 0 || mode == 1, "lea_conv3d_wino_set_small_cout: mode=%d", mode);
-  wino::g_small16 = mode;
-  return 0;
-}
-
-extern "C" int lea_conv3d_wino2_set_pipeline(int on) {
-  clear_error();
-  LEA_CHECK_ARG(on == 0 || on == 1, "lea_conv3d_wino2_set_pipeline: on=%d", on);
-  wino::g_pipe = on;
-  return 0;
-}
-
-extern "C" int lea_conv3d_wino44_set(int on) {
-  clear_error();
-  LEA_CHECK_ARG(on >= 0 && on <= 3, "lea_conv3d_wino44_set: on=%d", on);
-  wino::g_w44 = on;
-  return 0;
-}
-
-extern "C" int lea_conv3d_wino44_set_group(int g) {
-  clear_error();
-  LEA_CHECK_ARG(g >= -1 && g <= 16, "lea_conv3d_wino44_set_group: %d", g);
-  wino::g_w44g = g;
-  return 0;
-}
+LEA_TUNING_HOOK(lea_conv3d_wino_set_tile_override, 3, for (int i = 0; i < 3; ++i) v[i] = wino::g_override[0] > 0 ? wino::g_override[i] : 0)
 
 extern "C" int lea_conv3d_wino44_set_tile(int t) {
   clear_error();
@@ -1158,75 +1164,12 @@ extern "C" int lea_conv3d_wino44_set_tile(int t) {
   wino::g_w44t = t;
   return 0;
 }
+LEA_TUNING_HOOK(lea_conv3d_wino44_set_tile, 1, v[0] = wino::g_w44t)
 
 extern "C" int lea_conv3d_wino44_tile(int B, int cin, int cout, int D, int H, int W) {
-  if (cin <= 0 || cin % wino::CIN_B != 0) return 0;
-  const char* name = lea_conv3d_wino_kernel_name(B, cin, cout, D, H, W, 0);
-  if (!name || strcmp(name, "conv3d_wino44_kernel") != 0) return 0;
-  return wino::tile44(B, cin, cout, D, H, W);
-}
-
-extern "C" int lea_conv3d_wino44_set_sched(int s) {
-  clear_error();
-  LEA_CHECK_ARG(s >= 0 && s <= 3, "lea_conv3d_wino44_set_sched: %d", s);
-  wino::g_w44s = s;
-  return 0;
-}
-
-extern "C" int lea_conv3d_wino44_set_upre(int on) {
-  clear_error();
-  LEA_CHECK_ARG(on == 0 || on == 1, "lea_conv3d_wino44_set_upre: on=%d", on);
-  wino::g_w44u = on;
-  return 0;
-}
-
-extern "C" int lea_conv3d_wino2p_set_wpre(int on) {
-  clear_error();
-  LEA_CHECK_ARG(on == 0 || on == 1, "lea_conv3d_wino2p_set_wpre: on=%d", on);
-  wino::g_wpre = on;
-  return 0;
-}
-
-extern "C" int lea_conv3d_wino_set_fence(int on) {
-  clear_error();
-  LEA_CHECK_ARG(on == 0 || on == 1, "lea_conv3d_wino_set_fence: on=%d", on);
-  wino::g_fence = on;
-  return 0;
-}
-
-extern "C" int lea_conv3d_wino2_set_lane_halo16(int on) {
-  clear_error();
-  LEA_CHECK_ARG(on >= 0 && on <= 2, "lea_conv3d_wino2_set_lane_halo16: on=%d", on);
-  wino::g_lane16 = on;
-  return 0;
-}
-
-extern "C" int lea_conv3d_wino2_set_halo16(int on) {
-  clear_error();
-  LEA_CHECK_ARG(on == 0 || on == 1, "lea_conv3d_wino2_set_halo16: on=%d", on);
-  wino::g_halo16 = on;
-  return 0;
-}
-
-extern "C" int lea_conv3d_wino2_set_walk(int spw) {
-  clear_error();
-  LEA_CHECK_ARG(spw >= 0 && spw <= 64, "lea_conv3d_wino2_set_walk: spw=%d", spw);
-  wino::g_spw = spw;
-  return 0;
-}
-
-extern "C" int lea_conv3d_wino_set_w22(int on) {
-  clear_error();
-  LEA_CHECK_ARG(on >= 0 && on <= 2, "lea_conv3d_wino_set_w22: on=%d", on);
-  wino::g_w22 = on;
-  return 0;
-}
-
-extern "C" int lea_conv3d_wino_set_variant(int variant) {
-  clear_error();
-  LEA_CHECK_ARG(variant >= 0 && variant <= 7, "lea_conv3d_wino_set_variant: bad variant %d", variant);
-  wino::g_variant = variant;
-  return 0;
+  if (cin <= 0 || cin % wino::CIN_B != 0 || B <= 0 || cout <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
+  const wino::Route r = wino::route(B, cin, cout, D, H, W, false, false, nullptr);
+  return r.e == wino::Engine::Wino44 ? r.geo : 0;
 }
 
 extern "C" int lea_conv3d_bnrelu_wino(const void* x, int64_t x_bstride, const void* x2,
@@ -1236,24 +1179,8 @@ extern "C" int lea_conv3d_bnrelu_wino(const void* x, int64_t x_bstride, const vo
                                       int cout, int D, int H, int W, unsigned flags, int dtype,
                                       void* stream) {
   clear_error();
-  ConvArgs a{};
-  a.x = (const float*)x;
-  a.xbs = x_bstride;
-  a.x2 = (const float*)x2;
-  a.x2bs = x2_bstride;
-  a.cin1 = cin - cin2;
-  a.wp = w_packed;
-  a.scale = scale;
-  a.shift = shift;
-  a.res = (const float*)residual;
-  a.rbs = r_bstride;
-  a.y = (float*)y;
-  a.ybs = y_bstride;
-  a.cin = cin;
-  a.cout = cout;
-  a.D = D;
-  a.H = H;
-  a.W = W;
+  ConvArgs a = wino::conv_args(x, x_bstride, x2, x2_bstride, cin2, w_packed, scale, shift, residual, r_bstride, y,
+                               y_bstride, cin, cout, D, H, W);
   a.flags = flags;
   LEA_CHECK_FLAGS(flags, LEA_RELU | LEA_RESIDUAL | LEA_PAIR_SUM, "lea_conv3d_bnrelu_wino");
   LEA_CHECK_ARG(cin2 >= 0 && cin2 <= cin && (cin2 == 0 || x2), "lea_conv3d_bnrelu_wino: bad second source");
@@ -1267,22 +1194,8 @@ extern "C" int lea_conv3d_bnrelu_costvolume_wino(const void* left, const void* r
                                                  int H, int W, unsigned flags, int dtype,
                                                  void* stream) {
   clear_error();
-  ConvArgs a{};
-  a.x = (const float*)left;
-  a.xbs = f_bstride;
-  a.x2 = (const float*)right;
-  a.x2bs = f_bstride;
-  a.cin1 = C;
-  a.wp = w_packed;
-  a.scale = scale;
-  a.shift = shift;
-  a.y = (float*)y;
-  a.ybs = y_bstride;
-  a.cin = 2 * C;
-  a.cout = cout;
-  a.D = D3;
-  a.H = H;
-  a.W = W;
+  ConvArgs a = wino::conv_args(left, f_bstride, right, f_bstride, C, w_packed, scale, shift, nullptr, 0, y, y_bstride,
+                               2 * C, cout, D3, H, W);
   a.flags = flags & LEA_RELU;
   LEA_CHECK_FLAGS(flags, LEA_RELU, "lea_conv3d_bnrelu_costvolume_wino");
   LEA_CHECK_ARG(left && right && y != left && y != right,
@@ -1290,66 +1203,65 @@ extern "C" int lea_conv3d_bnrelu_costvolume_wino(const void* left, const void* r
   return wino::common(a, B, true, dtype, stream);
 }
 
-// ---- the depth-paired tiles with the down-sampling epilogue (conv3d_wino_body, DOWN) ----
+// ---- the down-sampling epilogues: the depth-paired tiles' (conv3d_wino_body, DOWN) and the
+// F(4,3) x F(4,3) tile's (conv3d_wino44.hip, DOWN) ----
 namespace lea {
 namespace wino {
 
-// does the planner put this layer on a depth-paired tile that has a DOWN form -- the 64-wide one
-// in its default instantiation (16-byte halo, fenced schedule) or the 32-wide row pairs -- with
-// the buffer-addressed epilogue?  `a` = the entry's arguments (alignment checked), or NULL for
-// the shape alone (aligned operands assumed).  Returns Q (16 / 8), or 0
-static int dp_down2_plan(int B, int cin, int cout, int D, int H, int W, ConvArgs* a) {
-  if (B <= 0 || cin <= 0 || cout <= 0 || cout > 8 || D < 2 || H < 2 || W < 4 || D % 2 || H % 2 || W % 4 ||
-      cin % CIN_B)
-    return 0;
-  if ((long long)D * H * W * 4 >= (1LL << 32) || (long long)(cout + 47) * D * H * W >= (1LL << 31)) return 0;
-  if (!g_epibuf || g_w22 == 2 || g_variant != 0 || g_override[0] != 0) return 0;
-  Plan p = make_plan(B, cout, D, H, W);
-  if (p.mt != 0 || p.d2 || p.f != 4 || p.np != 1 || p.td != 2) return 0;
-  plan_halo16(p, false, W, a, cin);
-  if (a && !epi_buf_ok(*a)) return 0;
-  if (p.q == 16) return (p.h16 && g_fence) ? 16 : 0;
-  return p.q == 8 ? 8 : 0;
+// the shapes either down-sampling epilogue takes at all
+static bool down2_shape_ok(int B, int cin, int cout, int D, int H, int W) {
+  if (B <= 0 || cin <= 0 || cout <= 0 || D < 2 || H < 2 || W < 4 || D % 2 || H % 2 || W % 4 || cin % CIN_B)
+    return false;
+  return (long long)D * H * W * 4 < (1LL << 32) && (long long)(cout + 47) * D * H * W < (1LL << 31);
 }
 
-static int run_dp_down2(ConvArgs a, int B, int q, bool only, hipStream_t st) {
-  a.ncob = 1;
-  const int tw = 4 * q, th = 4 * (16 / q);
-  a.tiles_w = (a.W + tw - 1) / tw;
-  a.ntiles = a.tiles_w * ((a.H + th - 1) / th);
-  a.ndz = (a.D + 1) / 2;
-  a.spw = std::max(1, std::min(g_spw > 0 ? g_spw : auto_walk(a, B, 2), a.ndz));
-  const long long n_ = (long long)a.ntiles * ((a.ndz + a.spw - 1) / a.spw) * B * a.ncob;
-  LEA_CHECK_ARG(n_ < (1LL << 31), "lea_conv3d_bnrelu_wino_dp_down2: grid too large");
-  a.nblk = (int)n_;
-  const dim3 grid((unsigned)n_);
-  if (q == 16) {
-    if (only)
-      conv3d_wino_dp_down2_kernel<16, true><<<grid, kConvThreads, 0, st>>>(a);
-    else
-      conv3d_wino_dp_down2_kernel<16, false><<<grid, kConvThreads, 0, st>>>(a);
-  } else {
-    if (only)
-      conv3d_wino_dp_down2_kernel<8, true><<<grid, kConvThreads, 0, st>>>(a);
-    else
-      conv3d_wino_dp_down2_kernel<8, false><<<grid, kConvThreads, 0, st>>>(a);
-  }
-  return launch_status("lea_conv3d_bnrelu_wino_dp_down2");
+// does the route put this layer on a depth-paired tile that has a DOWN form -- the 64-wide one
+// in its default instantiation (16-byte halo, fenced schedule) or the 32-wide row pairs -- by
+// the planner's own choice and with the buffer-addressed epilogue?  `a` = the entry's arguments
+// (alignment checked), or NULL for the shape alone.  Returns Q (16 / 8), or 0
+static int dp_down2_plan(int B, int cin, int cout, int D, int H, int W, const ConvArgs* a, Route* out) {
+  if (cout > 8 || !down2_shape_ok(B, cin, cout, D, H, W)) return 0;
+  const Route r = route(B, cin, cout, D, H, W, false, false, a);
+  if (r.e != Engine::Tile1D || r.mt != 0 || !r.planner || !r.epi) return 0;
+  if (r.q == 16 ? !(r.h16 && r.fence) : r.q != 8) return 0;
+  if (out) *out = r;
+  return r.q;
+}
+
+static int run_dp_down2(const Route& r, ConvArgs a, int B, bool only, hipStream_t st, const char** name) {
+  const char* what = "lea_conv3d_bnrelu_wino_dp_down2";
+  if (!name)
+    if (int rc = grid(a, B, 4 * r.q, 4 * (16 / r.q), 2, 16, 2, r.spw, what)) return rc;
+  if (r.q == 16 && only) LEA_WINO_KERNEL(what, kConvThreads, conv3d_wino_dp_down2_kernel<16, true>);
+  if (r.q == 16) LEA_WINO_KERNEL(what, kConvThreads, conv3d_wino_dp_down2_kernel<16, false>);
+  if (only) LEA_WINO_KERNEL(what, kConvThreads, conv3d_wino_dp_down2_kernel<8, true>);
+  LEA_WINO_KERNEL(what, kConvThreads, conv3d_wino_dp_down2_kernel<8, false>);
+}
+
+// does the route put this layer on the F(4,3) x F(4,3) tile in its default instantiation
+// (conv3d_wino44_kernel<false, 0>; the DOWN form always has the wide geometry)?
+static bool down2_plan(int B, int cin, int cout, int D, int H, int W, const ConvArgs* a, Route* out) {
+  if (!down2_shape_ok(B, cin, cout, D, H, W)) return false;
+  const Route r = route(B, cin, cout, D, H, W, false, false, a);
+  if (r.e != Engine::Wino44 || r.upre || r.sched != 0) return false;
+  if (out) *out = r;
+  return true;
 }
 
 }  // namespace wino
 }  // namespace lea
 
 extern "C" int lea_conv3d_wino_dp_down2_supported(int B, int cin, int cout, int D, int H, int W) {
-  return wino::dp_down2_plan(B, cin, cout, D, H, W, nullptr) ? 1 : 0;
+  return wino::dp_down2_plan(B, cin, cout, D, H, W, nullptr, nullptr) ? 1 : 0;
 }
 
 extern "C" const char* lea_conv3d_wino_dp_down2_kernel_name(int B, int cin, int cout, int D, int H, int W,
                                                             int only) {
-  const int q = wino::dp_down2_plan(B, cin, cout, D, H, W, nullptr);
-  if (!q) return nullptr;
-  snprintf(wino::g_name, sizeof(wino::g_name), "conv3d_wino_dp_down2_kernel<%d, %s>", q, only ? "true" : "false");
-  return wino::g_name;
+  wino::Route r;
+  const char* name = nullptr;
+  if (wino::dp_down2_plan(B, cin, cout, D, H, W, nullptr, &r))
+    wino::run_dp_down2(r, ConvArgs{}, B, only != 0, nullptr, &name);
+  return name;
 }
 
 extern "C" int lea_conv3d_bnrelu_wino_dp_down2(const void* x, int64_t x_bstride, const float* w_packed,
@@ -1359,24 +1271,11 @@ extern "C" int lea_conv3d_bnrelu_wino_dp_down2(const void* x, int64_t x_bstride,
                                                unsigned flags, int dtype, void* stream) {
   const char* what = "lea_conv3d_bnrelu_wino_dp_down2";
   clear_error();
-  ConvArgs a{};
-  a.x = (const float*)x;
-  a.xbs = x_bstride;
-  a.cin1 = cin;
-  a.wp = w_packed;
-  a.scale = scale;
-  a.shift = shift;
-  a.res = (const float*)residual;
-  a.rbs = r_bstride;
-  a.y = (float*)y;  // NULL: the `only` form
-  a.ybs = y_bstride;
+  // (y NULL: the `only` form)
+  ConvArgs a = wino::conv_args(x, x_bstride, nullptr, 0, 0, w_packed, scale, shift, residual, r_bstride, y, y_bstride,
+                               cin, cout, D, H, W);
   a.y2 = (float*)y2;
   a.y2bs = y2_bstride;
-  a.cin = cin;
-  a.cout = cout;
-  a.D = D;
-  a.H = H;
-  a.W = W;
   LEA_CHECK_ARG(a.x && a.wp && a.y2, "%s: null pointer", what);
   LEA_CHECK_ARG((scale == nullptr) == (shift == nullptr), "%s: scale/shift must both be set or both NULL", what);
   LEA_CHECK_ARG(!(flags & LEA_RESIDUAL) || a.res, "%s: LEA_RESIDUAL without residual", what);
@@ -1401,8 +1300,8 @@ extern "C" int lea_conv3d_bnrelu_wino_dp_down2(const void* x, int64_t x_bstride,
     a.y = const_cast<float*>(a.res ? a.res : a.x);
     a.ybs = a.res ? a.rbs : a.xbs;
   }
-  const int q = wino::dp_down2_plan(B, cin, cout, D, H, W, &a);
-  if (!q) {
+  wino::Route r;
+  if (!wino::dp_down2_plan(B, cin, cout, D, H, W, &a, &r)) {
     set_error("%s: the planner does not put B=%d cin=%d cout=%d D=%d H=%d W=%d on a depth-paired tile with the "
               "buffer-addressed epilogue (or its settings / the operands' alignment rule it out)",
               what, B, cin, cout, D, H, W);
@@ -1412,39 +1311,23 @@ extern "C" int lea_conv3d_bnrelu_wino_dp_down2(const void* x, int64_t x_bstride,
   a.rd = axis_ratio(D, D / 2, 1);
   a.rh = axis_ratio(H, H / 2, 1);
   a.rw = axis_ratio(W, W / 2, 1);
-  return wino::run_dp_down2(a, B, q, only, as_stream(stream));
+  return wino::run_dp_down2(r, a, B, only, as_stream(stream), nullptr);
 }
 
-// ---- the F(4,3) x F(4,3) tile with the down-sampling epilogue (conv3d_wino44.hip, DOWN) ----
-namespace lea {
-namespace wino {
-
-// does the planner put this layer on the F(4,3) x F(4,3) tile in its default instantiation
-// (conv3d_wino44_kernel<false, 0>)?  `a` = the entry's arguments (alignment checked), or NULL
-// for the shape alone (aligned operands assumed, as lea_conv3d_wino_kernel_name)
-static bool down2_plan(int B, int cin, int cout, int D, int H, int W, ConvArgs* a, Plan2* out) {
-  if (B <= 0 || cin <= 0 || cout <= 0 || D < 2 || H < 2 || W < 4 || D % 2 || H % 2 || W % 4 || cin % CIN_B)
-    return false;
-  if ((long long)D * H * W * 4 >= (1LL << 32) || (long long)(cout + 47) * D * H * W >= (1LL << 31)) return false;
-  Plan p = make_plan(B, cout, D, H, W);
-  if (g_w22 && (p.mt == 1 || (g_w22 == 2 && cout <= 32)) && g_variant == 0 && g_override[0] == 0) return false;
-  plan_halo16(p, false, W, a, cin);
-  if (!p.d2 || !g_w44 || g_w44u || g_w44s != 0 || !has_l44(cout)) return false;
-  const Plan2& q = p.p2;
-  if (!(q.q == 8 && q.wc == 2 && q.mte == 1 && q.nw == 4 && q.occ == 2 && q.pv == 3)) return false;
-  if (out) *out = q;
-  return true;
+// the name of the F(4,3) x F(4,3) DOWN kernel (down: 1 one input, 2 cat) this shape runs, or NULL
+static const char* down2_name(int B, int cin, int cout, int D, int H, int W, int down) {
+  wino::Route r;
+  const char* name = nullptr;
+  if (wino::down2_plan(B, cin, cout, D, H, W, nullptr, &r)) wino::run44(r, ConvArgs{}, B, nullptr, &name, down);
+  return name;
 }
-
-}  // namespace wino
-}  // namespace lea
 
 extern "C" int lea_conv3d_wino_down2_supported(int B, int cin, int cout, int D, int H, int W) {
   return wino::down2_plan(B, cin, cout, D, H, W, nullptr, nullptr) ? 1 : 0;
 }
 
 extern "C" const char* lea_conv3d_wino_down2_kernel_name(int B, int cin, int cout, int D, int H, int W) {
-  return wino::down2_plan(B, cin, cout, D, H, W, nullptr, nullptr) ? "conv3d_wino44_down2_kernel" : nullptr;
+  return down2_name(B, cin, cout, D, H, W, 1);
 }
 
 // the two-input form (cat(x, x2) read in place, cin2 of the cin channels from x2): a chunk never
@@ -1456,7 +1339,7 @@ extern "C" int lea_conv3d_wino_down2_cat_supported(int B, int cin, int cin2, int
 
 extern "C" const char* lea_conv3d_wino_down2_cat_kernel_name(int B, int cin, int cin2, int cout, int D, int H,
                                                              int W) {
-  return lea_conv3d_wino_down2_cat_supported(B, cin, cin2, cout, D, H, W) ? "conv3d_wino44_down2_cat_kernel"
+  return lea_conv3d_wino_down2_cat_supported(B, cin, cin2, cout, D, H, W) ? down2_name(B, cin, cout, D, H, W, 2)
                                                                           : nullptr;
 }
 
@@ -1466,22 +1349,8 @@ static int wino_down2_entry(const char* what, const void* x, int64_t x_bstride, 
                             int64_t y_bstride, int B, int cin, int cout, int D, int H, int W, unsigned flags,
                             int dtype, void* stream) {
   clear_error();
-  ConvArgs a{};
-  a.x = (const float*)x;
-  a.xbs = x_bstride;
-  a.x2 = (const float*)x2;
-  a.x2bs = x2_bstride;
-  a.cin1 = cin - cin2;
-  a.wp = w_packed;
-  a.scale = scale;
-  a.shift = shift;
-  a.y = (float*)y;
-  a.ybs = y_bstride;
-  a.cin = cin;
-  a.cout = cout;
-  a.D = D;
-  a.H = H;
-  a.W = W;
+  ConvArgs a = wino::conv_args(x, x_bstride, x2, x2_bstride, cin2, w_packed, scale, shift, nullptr, 0, y, y_bstride,
+                               cin, cout, D, H, W);
   LEA_CHECK_ARG(a.x && a.wp && a.y, "%s: null pointer", what);
   LEA_CHECK_ARG((scale == nullptr) == (shift == nullptr), "%s: scale/shift must both be set or both NULL", what);
   LEA_CHECK_ARG(B > 0 && cin > 0 && cout > 0 && D > 0 && H > 0 && W > 0,
@@ -1509,8 +1378,8 @@ static int wino_down2_entry(const char* what, const void* x, int64_t x_bstride, 
   }
   // float2 stores through 32-bit byte offsets of a cout block of the L1 tensor
   LEA_CHECK_ARG(((uintptr_t)y & 15) == 0 && y_bstride % 4 == 0, "%s: y needs 16-byte alignment", what);
-  wino::Plan2 q;
-  if (!wino::down2_plan(B, cin, cout, D, H, W, &a, &q)) {
+  wino::Route r;
+  if (!wino::down2_plan(B, cin, cout, D, H, W, &a, &r)) {
     set_error("%s: the planner does not put B=%d cin=%d cout=%d D=%d H=%d W=%d on the F(4,3) x F(4,3) tile "
               "(or its settings / the operands' alignment rule it out)", what, B, cin, cout, D, H, W);
     return LEA_E_UNSUPPORTED;
@@ -1519,7 +1388,7 @@ static int wino_down2_entry(const char* what, const void* x, int64_t x_bstride, 
   a.rh = axis_ratio(H, H / 2, 1);
   a.rw = axis_ratio(W, W / 2, 1);
   a.uoff = wino::l44_offset(cout, cin);
-  return wino::run44(a, B, q.spw, as_stream(stream), true);
+  return wino::run44(r, a, B, as_stream(stream), nullptr, x2 ? 2 : 1);
 }
 
 extern "C" int lea_conv3d_bnrelu_wino_down2(const void* x, int64_t x_bstride, const float* w_packed,

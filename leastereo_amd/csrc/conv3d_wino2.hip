@@ -1101,24 +1101,14 @@ long long lane_weights_floats(int cout, int cin) {
 }
 
 
-thread_local char g_name2[96];
-
-
 #define LEA_WINO2_DBG
 #define LEA_WINO2_CASE(Q, WC, MTE, NW, OCC, PV, CV)                                                \
   if (p.q == Q && p.wc == WC && p.mte == MTE && p.nw == NW && p.occ == OCC && p.pv == PV) {        \
     using C_ = Cfg2<Q, WC, MTE, NW, OCC, PV>;                                                      \
-    a.ncob = (a.cout + C_::COP - 1) / C_::COP;                                                     \
-    a.tiles_w = (a.W + C_::TW - 1) / C_::TW;                                                       \
-    a.ntiles = a.tiles_w * ((a.H + C_::TH - 1) / C_::TH);                                          \
-    a.ndz = (a.D + C_::TD - 1) / C_::TD;                                                           \
-    a.spw = std::max(1, std::min(p.spw > 0 ? p.spw : auto_walk(a, B, C_::WG_PER_CU), a.ndz));    \
-    const long long n_ = (long long)a.ntiles * ((a.ndz + a.spw - 1) / a.spw) * B * a.ncob;         \
-    LEA_CHECK_ARG(n_ < (1LL << 31), "lea_conv3d(wino2): grid too large");                          \
-    a.nblk = (int)n_;                                                                              \
+    if (!name)                                                                                     \
+      if (int rc = grid(a, B, C_::TW, C_::TH, C_::TD, C_::COP, C_::WG_PER_CU, r.spw, "lea_conv3d(wino2)")) return rc; \
     LEA_WINO2_DBG                                                                                  \
-    conv3d_wino2_kernel<Q, WC, MTE, NW, OCC, PV, CV><<<dim3((unsigned)n_), NW * 64, 0, st>>>(a);   \
-    return launch_status("lea_conv3d(wino2)");                                                    \
+    LEA_WINO_KERNEL("lea_conv3d(wino2)", NW * 64, conv3d_wino2_kernel<Q, WC, MTE, NW, OCC, PV, CV>); \
   }
 #define LEA_WINO2_TILES(CV)                                                                        \
   LEA_WINO2_CASE(8, 1, 1, 4, 2, 0, CV) LEA_WINO2_CASE(8, 2, 1, 4, 2, 0, CV)                        \
@@ -1127,42 +1117,29 @@ thread_local char g_name2[96];
   LEA_WINO2_CASE(16, 1, 2, 4, 1, 0, CV) LEA_WINO2_CASE(8, 2, 1, 4, 2, 1, CV)                       \
   LEA_WINO2_CASE(8, 2, 1, 8, 2, 1, CV) LEA_WINO2_CASE(8, 1, 2, 4, 1, 1, CV)
 
-int run2(const Plan2& p, ConvArgs a, int B, hipStream_t st, bool cv) {
-  if (cv) {
+// Engine::Tile2D and Engine::Wino2p (the one-barrier pipeline: the PV = 2 tile's geometry)
+int run2(const Route& r, ConvArgs a, int B, hipStream_t st, const char** name) {
+  const Plan2& p = r.p2;
+  if (r.cv) {
     LEA_WINO2_TILES(true)
   } else {
     LEA_WINO2_TILES(false)
     LEA_WINO2_CASE(8, 2, 1, 4, 2, 2, false)
     LEA_WINO2_CASE(8, 1, 1, 4, 2, 4, false)
     LEA_WINO2_CASE(8, 1, 1, 4, 2, 5, false)
-    if (p.q == 8 && p.wc == 2 && p.mte == 1 && p.nw == 4 && p.occ == 2 && p.pv == 3) {
-      if (g_w44) return run44(a, B, p.spw, st);  // F(4,3) x F(4,3) on the same layers (r06)
+    if (r.e == Engine::Wino2p) {
       using C_ = Cfg2<8, 2, 1, 4, 2, 2>;
-      a.ncob = (a.cout + C_::COP - 1) / C_::COP;
-      a.tiles_w = (a.W + C_::TW - 1) / C_::TW;
-      a.ntiles = a.tiles_w * ((a.H + C_::TH - 1) / C_::TH);
-      a.ndz = (a.D + C_::TD - 1) / C_::TD;
-      a.spw = std::max(1, std::min(p.spw > 0 ? p.spw : auto_walk(a, B, C_::WG_PER_CU), a.ndz));
-      const long long n_ = (long long)a.ntiles * ((a.ndz + a.spw - 1) / a.spw) * B * a.ncob;
-      LEA_CHECK_ARG(n_ < (1LL << 31), "lea_conv3d(wino2): grid too large");
-      a.nblk = (int)n_;
-      if (g_wpre)
-        conv3d_wino2p_kernel<true><<<dim3((unsigned)n_), 256, 0, st>>>(a);
+      if (!name)
+        if (int rc = grid(a, B, C_::TW, C_::TH, C_::TD, C_::COP, C_::WG_PER_CU, r.spw, "lea_conv3d(wino2)")) return rc;
+      if (r.wpre)
+        LEA_WINO_KERNEL_AS("conv3d_wino2p_kernel", "lea_conv3d(wino2p)", 256, conv3d_wino2p_kernel<true>);
       else
-        conv3d_wino2p_kernel<false><<<dim3((unsigned)n_), 256, 0, st>>>(a);
-      return launch_status("lea_conv3d(wino2p)");
+        LEA_WINO_KERNEL_AS("conv3d_wino2p_kernel", "lea_conv3d(wino2p)", 256, conv3d_wino2p_kernel<false>);
     }
   }
   set_error("lea_conv3d(wino2): no tile q=%d wc=%d mte=%d nw=%d occ=%d pv=%d", p.q, p.wc, p.mte, p.nw,
             p.occ, p.pv);
   return LEA_E_UNSUPPORTED;
-}
-
-const char* name2(const Plan2& p, bool cv) {
-  if (p.pv == 3 && !cv) return g_w44 ? "conv3d_wino44_kernel" : "conv3d_wino2p_kernel";
-  snprintf(g_name2, sizeof(g_name2), "conv3d_wino2_kernel<%d, %d, %d, %d, %d, %d, %s>", p.q, p.wc, p.mte,
-           p.nw, p.occ, p.pv, cv ? "true" : "false");
-  return g_name2;
 }
 
 }  // namespace wino

@@ -307,25 +307,19 @@ bool wino22_ok(const ConvArgs& a) {
          16LL * a.D * a.H * a.W * 4 < (long long)kEpiOob;
 }
 
-int run22(ConvArgs a, int B, int spw, hipStream_t st) {
+// Engine::Wino22
+int run22(const Route& r, ConvArgs a, int B, hipStream_t st, const char** name) {
   using C = Cfg22;
-  a.ncob = (a.cout + 15) / 16;
-  a.tiles_w = (a.W + C::TW - 1) / C::TW;
-  a.ntiles = a.tiles_w * ((a.H + C::TH - 1) / C::TH);
-  a.ndz = (a.D + C::TD - 1) / C::TD;
-  // depth pairs per workgroup: two when that leaves one round of workgroups (2 per CU) instead
-  // of two (r05 tools/w22_ab.py, C2 L1 16 -> 16: 960 workgroups 47 us, 480 walking 2 pairs 44 us;
-  // C5's 3696 workgroups equal either way)
-  if (spw <= 0) {
-    const long long base = (long long)a.ntiles * a.ndz * B * a.ncob;
-    spw = base > 512 && base <= 1024 ? 2 : 1;
+  if (!name) {
+    int rc = grid(a, B, C::TW, C::TH, C::TD, 16, 2, r.spw > 0 ? r.spw : 1, "lea_conv3d(wino22)");
+    // depth pairs per workgroup: two when that leaves one round of workgroups (2 per CU) instead
+    // of two (r05 tools/w22_ab.py, C2 L1 16 -> 16: 960 workgroups 47 us, 480 walking 2 pairs 44 us;
+    // C5's 3696 workgroups equal either way)
+    if (!rc && r.spw <= 0 && a.nblk > 512 && a.nblk <= 1024)
+      rc = grid(a, B, C::TW, C::TH, C::TD, 16, 2, 2, "lea_conv3d(wino22)");
+    if (rc) return rc;
   }
-  a.spw = std::max(1, std::min(spw, a.ndz));
-  const long long n = (long long)a.ntiles * ((a.ndz + a.spw - 1) / a.spw) * B * a.ncob;
-  LEA_CHECK_ARG(n < (1LL << 31), "lea_conv3d(wino22): grid too large");
-  a.nblk = (int)n;
-  conv3d_wino22_kernel<<<dim3((unsigned)n), 512, 0, st>>>(a);
-  return launch_status("lea_conv3d(wino22)");
+  LEA_WINO_KERNEL("lea_conv3d(wino22)", 512, conv3d_wino22_kernel);
 }
 
 }  // namespace wino

@@ -16,7 +16,7 @@
 // points 3 xh .. 3 xh + 2 of cout tile wc (16 couts) -- 18 points, 72 accumulator VGPRs.  The
 // workgroup = 2 x-halves x 2 cout tiles = 4 waves over one 32 (W) x 2 (H) x 4 (D) x 32 (cout)
 // output tile; two workgroups per CU (74 KB of LDS each).  A second geometry, 16 (W) x 4 (H) x
-// 4 (D), covers the same 64 voxels per plane (w44::Geo<4>; the host's tile44 picks per shape).
+// 4 (D), covers the same 64 voxels per plane (w44::Geo<4>; the host's route() picks per shape).
 //
 // Item i = (depth quad, 4-channel chunk), the one-barrier pipeline of conv3d_wino2p_kernel:
 //   top      this wave's halo(i + 1) pieces and weights g(i) have landed (vmcnt), barrier
@@ -60,7 +60,7 @@ static_assert(GS % 8 == 0 && XHS % 4 == 0, "V bank map");
 
 // The tile's geometry: a wave's 16 MFMA columns are Q_ W groups x 16 / Q_ rows.  Geo<8> is the
 // 32 (W) x 2 (H) tile, Geo<4> the 16 x 4 one (the same 64 voxels per plane; taken where it pads
-// fewer columns of W: tile44 below).  Channel bases, XS, GS and XHS are common to both.
+// fewer columns of W: route(), conv3d_wino.hip).  Channel bases, XS, GS and XHS are common to both.
 //   halo: rows of RWA floats in RSLOTS row slots per plane.  Geo<4> leaves the slot before its last
 //         halo row empty: a 32-lane ds_read_b64 group of the V-pass is 4 groups x 4 channels x 2
 //         rows, and with rows 24 floats apart the rows of a pair must be 16 or 48 (mod 64) apart to
@@ -675,7 +675,7 @@ template <bool UPRE, int SCHED>
 __global__ __launch_bounds__(256, 2) void conv3d_wino44_kernel(const ConvArgs a) {
   conv3d_wino44_body<w44::Geo<8>, UPRE, SCHED, false>(a);
 }
-// the 16 x 4 geometry, in the default form only (lea_conv3d_wino44_set_tile, tile44 below)
+// the 16 x 4 geometry, in the default form only (lea_conv3d_wino44_set_tile; route(), conv3d_wino.hip)
 __global__ __launch_bounds__(256, 2) void conv3d_wino44_kernel_16x4(const ConvArgs a) {
   conv3d_wino44_body<w44::Geo<4>, false, 0, false>(a);
 }
@@ -688,66 +688,32 @@ __global__ __launch_bounds__(256, 2) void conv3d_wino44_down2_cat_kernel(const C
   conv3d_wino44_body<w44::Geo<8>, false, 0, true>(a);
 }
 
-// lea_conv3d_wino44_set (r06 default 1: -9.5 % on its layers, profiles/r06_w44_ab.txt; 2 since v45,
-// after the LDS-conflict fixes: the L0 8 -> 24 group 275.6 -> 259.7 us, profiles/r06_w44_modes_ab.txt)
-int g_w44 = 2;
-int g_w44u = 0;  // lea_conv3d_wino44_set_upre
-int g_w44s = 0;  // lea_conv3d_wino44_set_sched
-int g_w44g = -1;  // lea_conv3d_wino44_set_group (-1: auto)
-int g_w44t = -1;  // lea_conv3d_wino44_set_tile (-1: auto)
+// the workgroup order (-1: auto), a rule of this launch alone (run44 below)
+LEA_TUNING_INT(lea_conv3d_wino44_set_group, g_w44g, -1, -1, 16, "%d")
 
-// The tile geometry of a layer on this kernel, by its shape alone: 32 (the 32 x 2 tile) or 16
-// (16 x 4).  Auto takes the narrow tile where it pads fewer columns (C2's quarter-resolution
-// volumes: W = 80 is 2.5 wide tiles, and 288 / 864 workgroups against 256 CUs x 2 become 240 /
-// 720).  The rule also takes the narrow tile for every W <= 16 and every W % 32 in 1 .. 16; of
-// those only W = 80 was measured (profiles/w44_narrow_layers_ab.txt), the others follow from the
-// padding argument alone.  The narrow geometry is built for the default form only (upre 0,
-// sched 0); the down-sampling entries always launch the wide one.
-int tile44(int B, int cin, int cout, int D, int H, int W) {
-  (void)B, (void)cin, (void)cout, (void)D, (void)H;
-  if (g_w44u || g_w44s != 0) return 32;
-  if (g_w44t > 0) return g_w44t;
-  auto padded = [&](int tw) { return (W + tw - 1) / tw * tw; };
-  return padded(w44::Geo<4>::TW) < padded(w44::Geo<8>::TW) ? 16 : 32;
-}
-
-int run44(ConvArgs a, int B, int spw, hipStream_t st, bool down) {
-  const bool narrow = !down && tile44(B, a.cin, a.cout, a.D, a.H, a.W) == 16;
+// Engine::Wino44 (route() chose the geometry, upre and sched; the down-sampling entries pass the
+// default instantiation's route and always launch the wide tile)
+int run44(const Route& r, ConvArgs a, int B, hipStream_t st, const char** name, int down) {
+  const bool narrow = !down && r.geo == 16;
   const int tw = narrow ? w44::Geo<4>::TW : w44::Geo<8>::TW, th = narrow ? w44::Geo<4>::TH : w44::Geo<8>::TH;
-  a.ncob = (a.cout + 31) / 32;
-  a.tiles_w = (a.W + tw - 1) / tw;
-  a.ntiles = a.tiles_w * ((a.H + th - 1) / th);
-  a.ndz = (a.D + w44::TD - 1) / w44::TD;
-  a.spw = std::max(1, std::min(spw > 0 ? spw : auto_walk(a, B, 2), a.ndz));
-  const long long n_ = (long long)a.ntiles * ((a.ndz + a.spw - 1) / a.spw) * B * a.ncob;
-  LEA_CHECK_ARG(n_ < (1LL << 31), "lea_conv3d(wino44): grid too large");
-  a.nblk = (int)n_;
-  // auto: 16 x 16-tile groups on the large grids (C2: conv1/2 and stem1, 3840 workgroups; HBM
-  // traffic -42 / -44 %, time unchanged, profiles/r06_w44_group_traffic2.txt), linear on the
-  // small ones (<= 864 workgroups, whose whole grid fits the L2s; grouped +1-2 %,
-  // r06_w44_group_ab.txt)
-  a.grp = g_w44g >= 0 ? g_w44g : (n_ >= 2048 ? 16 : 0);
-  const dim3 grid((unsigned)n_);
-  if (down) {  // (the host entry checked: the plain form's default instantiation)
-    if (a.x2 && a.cin1 < a.cin)
-      conv3d_wino44_down2_cat_kernel<<<grid, 256, 0, st>>>(a);
-    else
-      conv3d_wino44_down2_kernel<<<grid, 256, 0, st>>>(a);
-    return launch_status("lea_conv3d(wino44 down2)");
+  if (!name) {
+    if (int rc = grid(a, B, tw, th, w44::TD, 32, 2, r.spw, "lea_conv3d(wino44)")) return rc;
+    // auto: 16 x 16-tile groups on the large grids (C2: conv1/2 and stem1, 3840 workgroups; HBM
+    // traffic -42 / -44 %, time unchanged, profiles/r06_w44_group_traffic2.txt), linear on the
+    // small ones (<= 864 workgroups, whose whole grid fits the L2s; grouped +1-2 %,
+    // r06_w44_group_ab.txt)
+    a.grp = g_w44g >= 0 ? g_w44g : (a.nblk >= 2048 ? 16 : 0);
   }
-  if (narrow)
-    conv3d_wino44_kernel_16x4<<<grid, 256, 0, st>>>(a);
-  else if (g_w44u)
-    conv3d_wino44_kernel<true, 0><<<grid, 256, 0, st>>>(a);
-  else if (g_w44s == 1)
-    conv3d_wino44_kernel<false, 1><<<grid, 256, 0, st>>>(a);
-  else if (g_w44s == 2)
-    conv3d_wino44_kernel<false, 2><<<grid, 256, 0, st>>>(a);
-  else if (g_w44s == 3)
-    conv3d_wino44_kernel<false, 3><<<grid, 256, 0, st>>>(a);
-  else
-    conv3d_wino44_kernel<false, 0><<<grid, 256, 0, st>>>(a);
-  return launch_status("lea_conv3d(wino44)");
+  if (down == 2) LEA_WINO_KERNEL("lea_conv3d(wino44 down2)", 256, conv3d_wino44_down2_cat_kernel);
+  if (down) LEA_WINO_KERNEL("lea_conv3d(wino44 down2)", 256, conv3d_wino44_down2_kernel);
+#define LEA_WINO44_CASE(...) LEA_WINO_KERNEL_AS("conv3d_wino44_kernel", "lea_conv3d(wino44)", 256, __VA_ARGS__)
+  if (narrow) LEA_WINO44_CASE(conv3d_wino44_kernel_16x4);
+  if (r.upre) LEA_WINO44_CASE(conv3d_wino44_kernel<true, 0>);
+  if (r.sched == 1) LEA_WINO44_CASE(conv3d_wino44_kernel<false, 1>);
+  if (r.sched == 2) LEA_WINO44_CASE(conv3d_wino44_kernel<false, 2>);
+  if (r.sched == 3) LEA_WINO44_CASE(conv3d_wino44_kernel<false, 3>);
+  LEA_WINO44_CASE(conv3d_wino44_kernel<false, 0>);
+#undef LEA_WINO44_CASE
 }
 
 }  // namespace wino

@@ -189,14 +189,7 @@ __global__ __launch_bounds__(kDisp3Threads) void disparity_rows3_f32(const float
 // C4 275.6 -> 266.4 us; not at D3 = 88), 2 (r05) = the row-staged kernel for the configured
 // (D3, maxdisp), 1 = the register kernel for them, 0 = the online-softmin kernel everywhere
 // (A/B and tests)
-static int g_disp_reg = 4;
-extern "C" int lea_disparity_set_register_form(int on) {
-  using namespace lea;
-  clear_error();
-  LEA_CHECK_ARG(on >= 0 && on <= 4, "lea_disparity_set_register_form: %d", on);
-  g_disp_reg = on;
-  return 0;
-}
+static LEA_TUNING_INT(lea_disparity_set_register_form, g_disp_reg, 4, 0, 4, "%d")
 
 extern "C" int lea_disparity_regression(const void* cost, float* disp, int B, int D3, int H3,
                                         int W3, int maxdisp, int dtype, void* stream) {

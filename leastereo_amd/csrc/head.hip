@@ -364,13 +364,7 @@ __global__ __launch_bounds__(256) void tapsum_fused(const void* __restrict__ qv,
 // lea_tapsum_set_rows: 2 (default, r05) = passes 1 + 2 fused (tapsum_fused), 1 = the
 // row-staged pass 2 after pass 1 through the workspace, each when R output rows' sources fit
 // 64 KB of LDS; 0 = pass 1, then one workgroup per output row gathering through the L1
-static int g_tapsum_rows = 2;
-extern "C" int lea_tapsum_set_rows(int on) {
-  lea::clear_error();
-  LEA_CHECK_ARG(on >= 0 && on <= 2, "lea_tapsum_set_rows: %d", on);
-  g_tapsum_rows = on;
-  return 0;
-}
+static LEA_TUNING_INT(lea_tapsum_set_rows, g_tapsum_rows, 2, 0, 2, "%d")
 
 static int hwpass(const float* ws, void* y, int64_t y_bstride, int B, int cout, int Hi, int Wi, int Do,
                   int Ho, int Wo, const float* scale, const float* shift, unsigned flags, hipStream_t st) {

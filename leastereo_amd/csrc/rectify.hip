@@ -208,6 +208,7 @@ extern "C" int lea_rectify_set_tile(int mode) {
   lea::g_rect_tile.store(mode, std::memory_order_relaxed);
   return LEA_OK;
 }
+LEA_TUNING_HOOK(lea_rectify_set_tile, 1, v[0] = lea::g_rect_tile.load(std::memory_order_relaxed))
 
 extern "C" int lea_rectify_pair_u8(const void* left, const void* right, int pix_stride, int B, int H, int W,
                                    const float* calib, int Bc, const float* maps_in, int Bm, int Ho, int Wo, int fill,

@@ -300,19 +300,10 @@ __global__ __launch_bounds__(256) void resample3d_sep_down2_f32(
   }
 }
 
-int g_resample_mode = 0;  // lea_resample_set_mode: 0 auto, 1 row-staged, 2 gather
+// 0 auto, 1 row-staged, 2 gather
+LEA_TUNING_INT(lea_resample_set_mode, g_resample_mode, 0, 0, 2, "mode=%d")
 
 }  // namespace lea
-
-extern "C" int lea_resample_set_mode(int mode) {
-  lea::clear_error();
-  if (mode < 0 || mode > 2) {
-    lea::set_error("lea_resample_set_mode: mode=%d", mode);
-    return LEA_E_INVALID;
-  }
-  lea::g_resample_mode = mode;
-  return 0;
-}
 
 extern "C" int lea_staged_rows(int Hi, int Ho, int ac, int R, int halo) {
   lea::clear_error();

@@ -120,8 +120,29 @@ struct Plan2 {
   int q, wc, mte, nw, occ;
   int pv;   // V transformed once per chunk into LDS by the workgroup: 1 = halo staged by
             // dword LDS-DMA pieces, 2 = by 16-byte pieces (W % 4 == 0, aligned sources)
-  int spw;  // depth pairs walked per workgroup
 };
+
+// The kernel one layer runs on, decided once (route(), conv3d_wino.hip) from the shape, the
+// operands' alignment and the tuning hooks; the launch, the name query and the support /
+// geometry queries all read it, and nothing else reads a routing hook.
+enum class Engine { Tile1D, Tile2D, Wino2p, Wino44, Wino22 };
+struct Route {
+  Engine e;
+  int mt;                // 16-row cout tiles per block of the packed layout (0: depth-paired)
+  int f, q, np, td;      // Tile1D: conv3d_wino_kernel<f, q, mt, np, td, cv>
+  bool h16, fence;       //   its 16-byte-halo form and that form's fenced schedule
+  Plan2 p2;              // Tile2D: conv3d_wino2_kernel<q, wc, mte, nw, occ, pv, cv>
+  bool wpre;             // Wino2p: conv3d_wino2p_kernel<wpre>
+  int geo, sched;        // Wino44: 32 (32 x 2 tile) or 16 (16 x 4), conv3d_wino44_kernel<upre, sched>
+  bool upre;
+  bool cv;               // the cost volume is formed in the halo stage
+  bool epi;              // the buffer-addressed epilogue (kEpiBuf)
+  bool planner;          // no variant or 1-D tile override is set: the planner's own choice
+  int spw;               // lea_conv3d_wino2_set_walk: depth groups per workgroup (0 = auto_walk)
+};
+// a == NULL: the shape alone, aligned operands assumed
+Route route(int B, int cin, int cout, int D, int H, int W, bool cv, bool pair, const ConvArgs* a);
+
 // Depth groups (pairs) per workgroup when the planner leaves it open (both engines) (r02 walk sweep,
 // profiles/r02_wino2_walk_sweep.txt): walking 4 pairs gains 4-17 % on the L0 layers
 // (cin 8-32: 2-8 chunks per pair) and 2 on the 16-channel L1 cells, as long as about a
@@ -135,8 +156,38 @@ inline int auto_walk(const ConvArgs& a, int B, int wg_per_cu) {
   while (s < 4 && base / (2 * s) >= round * 15 / 16) s *= 2;
   return s;
 }
+// The grid of every launch: tiles of tw x th voxels by td planes, cout blocks of cop channels,
+// `walk` depth groups per workgroup (0: auto_walk at wg_per_cu workgroups per CU)
+inline int grid(ConvArgs& a, int B, int tw, int th, int td, int cop, int wg_per_cu, int walk, const char* what) {
+  a.ncob = (a.cout + cop - 1) / cop;
+  a.tiles_w = (a.W + tw - 1) / tw;
+  a.ntiles = a.tiles_w * ((a.H + th - 1) / th);
+  a.ndz = (a.D + td - 1) / td;
+  a.spw = std::max(1, std::min(walk > 0 ? walk : auto_walk(a, B, wg_per_cu), a.ndz));
+  const long long n = (long long)a.ntiles * ((a.ndz + a.spw - 1) / a.spw) * B * a.ncob;
+  LEA_CHECK_ARG(n < (1LL << 31), "%s: grid too large", what);
+  a.nblk = (int)n;
+  return LEA_OK;
+}
+// Launch the kernel named by the macro's tail (template commas and all) over a.nblk workgroups,
+// or, in a name query (name != NULL), answer AS: one expansion serves both.
+#define LEA_WINO_KERNEL_AS(AS, WHAT, THREADS, ...)                      \
+  do {                                                                  \
+    if (name) {                                                         \
+      *name = AS;                                                       \
+      return LEA_OK;                                                    \
+    }                                                                   \
+    __VA_ARGS__<<<dim3((unsigned)a.nblk), THREADS, 0, st>>>(a);         \
+    return launch_status(WHAT);                                         \
+  } while (0)
+#define LEA_WINO_KERNEL(WHAT, THREADS, ...) LEA_WINO_KERNEL_AS(#__VA_ARGS__, WHAT, THREADS, __VA_ARGS__)
 
-int run2(const Plan2& p, ConvArgs a, int B, hipStream_t st, bool cv);
+// the engines' launches: (route, arguments, batch, stream, name query or NULL)
+int run2(const Route& r, ConvArgs a, int B, hipStream_t st, const char** name);
+// down: 0 = the plain kernel, 1 = conv3d_wino44_down2_kernel, 2 = conv3d_wino44_down2_cat_kernel
+int run44(const Route& r, ConvArgs a, int B, hipStream_t st, const char** name, int down = 0);
+int run22(const Route& r, ConvArgs a, int B, hipStream_t st, const char** name);
+
 // the PV = 3 tile's per-lane weight copy (16-byte slices) (appended to the packed weights of 32-cout
 // blocks by lea_conv3d_wino_pack_weights), in floats, and its packer
 long long lane_weights_floats(int cout, int cin);
@@ -145,29 +196,19 @@ __global__ void pack_wino_lane_kernel(const float* __restrict__ w, float* __rest
                                       int nchunks, long long total);
 __global__ void pack_wino_lane_wpre_kernel(const float* __restrict__ w, float* __restrict__ out, int cout, int cin,
                                            int nchunks, long long total);
-extern int g_wpre;  // lea_conv3d_wino2p_set_wpre
-// F(4,3) x F(4,3) tile (conv3d_wino44.hip, r06): the layers of the pipelined W x D kernel when
-// g_w44 (lea_conv3d_wino44_set); its per-lane weight section (the last of lane_weights_floats)
-extern int g_w44;
-extern int g_w44u;  // lea_conv3d_wino44_set_upre
-extern int g_w44s;  // lea_conv3d_wino44_set_sched
-extern int g_w44g;  // lea_conv3d_wino44_set_group
-extern int g_w44t;  // lea_conv3d_wino44_set_tile
-int tile44(int B, int cin, int cout, int D, int H, int W);  // 32 (the 32 x 2 tile) or 16 (16 x 4)
+// F(4,3) x F(4,3) tile (conv3d_wino44.hip, r06): its per-lane weight section (the last of
+// lane_weights_floats)
 long long lane44_floats(int cout, int cin);
 long long lane44_g_floats(int cout, int cin);  // the G_W' g part (the U copy follows)
 __global__ void pack_wino44_lane_kernel(const float* __restrict__ w, float* __restrict__ out, int cout, int cin,
                                         int nchunks, long long total);
 __global__ void pack_wino44_lane_u_kernel(const float* __restrict__ w, float* __restrict__ out, int cout, int cin,
                                           int nchunks, long long total);
-int run44(ConvArgs a, int B, int spw, hipStream_t st, bool down = false);  // down: conv3d_wino44_down2_kernel
-const char* name2(const Plan2& p, bool cv);
 
 // F(2,3) x F(2,3) tile for the 16-cout layers (conv3d_wino22.hip): the U section the packer
 // appends for 16-cout blocks (floats), the host's shape / alignment check and the launch
 long long u22_section(int cout, int cin);
 bool wino22_ok(const ConvArgs& a);
-int run22(ConvArgs a, int B, int spw, hipStream_t st);
 __global__ void pack_wino22_kernel(const float* __restrict__ w, float* __restrict__ out, int cout, int cin,
                                    long long total);
 

@@ -30,6 +30,25 @@ static void expect_name(const char* what, const char* name, const char* prefix) 
   }
 }
 
+// the setters by name (this driver links the units directly), to call what lea_tuning_name lists
+struct Hook1 { const char* name; int (*set)(int); };
+struct Hook3 { const char* name; int (*set)(int, int, int); };
+#define H(f) {#f, f}
+static const Hook1 kHooks1[] = {
+    H(lea_conv3d_set_rs_gather), H(lea_conv1x1_set_vector), H(lea_conv3d_bf16_set_variant),
+    H(lea_conv3d_bf16_set_stream1x1), H(lea_conv3d_bf16_set_pair_split), H(lea_resample_bf16_set_batch),
+    H(lea_resample_bf16_set_cols), H(lea_resample_set_mode), H(lea_conv2d_set_small),
+    H(lea_disparity_set_register_form), H(lea_tapsum_set_rows), H(lea_conv3d_wino_set_w22),
+    H(lea_conv3d_wino_set_variant), H(lea_conv3d_wino2_set_walk), H(lea_conv3d_wino2_set_halo16),
+    H(lea_conv3d_wino2_set_lane_halo16), H(lea_conv3d_wino_set_fence), H(lea_conv3d_wino2_set_pipeline),
+    H(lea_conv3d_wino2p_set_wpre), H(lea_conv3d_wino44_set), H(lea_conv3d_wino44_set_upre),
+    H(lea_conv3d_wino44_set_sched), H(lea_conv3d_wino44_set_group), H(lea_conv3d_wino44_set_tile),
+    H(lea_conv3d_wino_set_epi_buf), H(lea_conv3d_wino_set_small_cout), H(lea_conv3d_wino_set_block48),
+    H(lea_rectify_set_tile)};
+static const Hook3 kHooks3[] = {H(lea_conv3d_set_tile_override), H(lea_conv3d_bf16_set_tile_override),
+                                H(lea_conv3d_wino_set_tile_override)};
+#undef H
+
 int main() {
   if (lea_abi_version() <= 0) {
     std::printf("FAIL abi version\n");
@@ -161,6 +180,35 @@ int main() {
   // tuning hooks: out-of-range values are rejected
   expect_err("walk range", lea_conv3d_wino2_set_walk(-1));
   expect_err("resample batch range", lea_resample_bf16_set_batch(3));
+  // every registered hook: read it, set it back (a no-op), read it again
+  int nhooks = 0;
+  for (const char* s; (s = lea_tuning_name(nhooks)) != nullptr; ++nhooks) {
+    int v[3] = {-99, -99, -99}, w[3] = {-99, -99, -99};
+    const int n = lea_tuning_get(s, v, 3);
+    int rc = -1;
+    for (const Hook1& h : kHooks1)
+      if (n == 1 && std::strcmp(h.name, s) == 0) rc = h.set(v[0]);
+    for (const Hook3& h : kHooks3)
+      if (n == 3 && std::strcmp(h.name, s) == 0) rc = h.set(v[0], v[1], v[2]);
+    if (rc != 0 || lea_tuning_get(s, w, n) != n || std::memcmp(v, w, sizeof(v)) != 0) {
+      std::printf("FAIL hook %s: n=%d set(get) rc=%d err='%s'\n", s, n, rc, lea_last_error());
+      ++g_fail;
+    }
+    if (n > 0) expect_err("tuning_get short", lea_tuning_get(s, v, n - 1), -1);
+  }
+  if (nhooks != (int)(sizeof(kHooks1) / sizeof(kHooks1[0]) + sizeof(kHooks3) / sizeof(kHooks3[0]))) {
+    std::printf("FAIL %d hooks registered\n", nhooks);
+    ++g_fail;
+  }
+  int one = 0;
+  expect_err("tuning_get unknown", lea_tuning_get("lea_no_such_set", &one, 1), -1);
+  expect_err("tuning_get null name", lea_tuning_get(nullptr, &one, 1), -1);
+  expect_err("tuning_get capacity 0", lea_tuning_get("lea_conv3d_wino44_set", &one, 0), -1);
+  expect_err("tuning_get null values", lea_tuning_get("lea_conv3d_wino44_set", nullptr, 1), -1);
+  if (lea_tuning_name(-1) != nullptr || lea_tuning_name(nhooks + 1) != nullptr) {
+    std::printf("FAIL tuning_name out of range\n");
+    ++g_fail;
+  }
   // after a good query the error string is cleared
   (void)lea_conv3d_wino2_set_walk(0);
   if (lea_last_error() == nullptr || lea_last_error()[0] != '\0') {

@@ -184,15 +184,11 @@ def test_planner_queries_at_the_routed_shapes():
     assert not lib.lea_conv3d_wino_down2_cat_supported(1, 32, 6, 32, 4, 4, 32)    # a chunk straddles the sources
     assert not lib.lea_conv3d_wino_down2_cat_supported(1, 32, 0, 32, 4, 4, 32)
     assert not lib.lea_conv3d_wino_down2_cat_supported(1, 32, 32, 32, 4, 4, 32)
-    try:  # another instantiation of the plain depth-paired launch: no DOWN form beside it
-        for setter, v, back in (("lea_conv3d_wino_set_fence", 0, 1), ("lea_conv3d_wino_set_epi_buf", 0, 1),
-                                ("lea_conv3d_wino2_set_halo16", 0, 1), ("lea_conv3d_wino_set_small_cout", 1, 0)):
-            assert getattr(lib, setter)(v) == 0
+    # another instantiation of the plain depth-paired launch: no DOWN form beside it
+    for setter, v in (("lea_conv3d_wino_set_fence", 0), ("lea_conv3d_wino_set_epi_buf", 0),
+                      ("lea_conv3d_wino2_set_halo16", 0), ("lea_conv3d_wino_set_small_cout", 1)):
+        with _lib.tuning(**{setter: v}):
             assert not lib.lea_conv3d_wino_dp_down2_supported(1, 8, 8, 64, 192, 320), setter
-            assert getattr(lib, setter)(back) == 0
-    finally:
-        lib.lea_conv3d_wino_set_fence(1), lib.lea_conv3d_wino_set_epi_buf(1)
-        lib.lea_conv3d_wino2_set_halo16(1), lib.lea_conv3d_wino_set_small_cout(0)
     assert lib.lea_conv3d_wino_dp_down2_supported(1, 8, 8, 64, 192, 320)
     # down on D; odd D, H; W % 4 != 0; rows of three planes that do not fit the LDS
     for bad in ((4, 4, 8, 2, 8, 16), (4, 4, 8, 7, 8, 16), (4, 4, 8, 8, 7, 16), (4, 4, 8, 8, 8, 18), (4, 4, 8, 8, 8, 4096)):

@@ -119,15 +119,12 @@ def test_wino_down2_argument_checks():
         assert lib.lea_conv3d_wino_down2_kernel_name(*shape) == b"conv3d_wino44_down2_kernel"
         # the plain form's reported name is what it was
         assert lib.lea_conv3d_wino_kernel_name(shape[0], shape[1], shape[2], *shape[3:], 0) == b"conv3d_wino44_kernel"
-    try:  # another tile or instantiation of the plain form: no DOWN form beside it
-        for setter, v in (("lea_conv3d_wino44_set", 0), ("lea_conv3d_wino44_set_upre", 1),
-                          ("lea_conv3d_wino44_set_sched", 1)):
-            assert getattr(lib, setter)(v) == 0
+    # another tile or instantiation of the plain form: no DOWN form beside it
+    for setter, v in (("lea_conv3d_wino44_set", 0), ("lea_conv3d_wino44_set_upre", 1),
+                      ("lea_conv3d_wino44_set_sched", 1)):
+        with _lib.tuning(**{setter: v}):
             assert not lib.lea_conv3d_wino_down2_supported(1, 32, 32, 64, 192, 320), setter
             assert call() == UNSUPPORTED, setter
-            assert getattr(lib, setter)(2 if setter == "lea_conv3d_wino44_set" else 0) == 0
-    finally:
-        lib.lea_conv3d_wino44_set(2), lib.lea_conv3d_wino44_set_upre(0), lib.lea_conv3d_wino44_set_sched(0)
 
 
 def test_supported_helpers_are_false_off_the_device():

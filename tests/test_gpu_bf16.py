@@ -129,20 +129,16 @@ def test_resample_bf16_cols_kernel_is_the_gather_kernel(b, c, src, dst, ac):
     wave into registers) gives the per-output gather kernel's bits, into a channel slice too
     (odd sizes, a partial last column tile, the last source row pairing with itself)."""
     from leastereo_amd import _lib
-    lib = _lib.load()
     g = torch.Generator().manual_seed(b * 100 + c)
     x = kernels.to_c8(torch.randn((b, c) + src, generator=g).to(DEV))
     scale = (torch.rand(c, generator=g) + 0.5).to(DEV)
     shift = (torch.randn(c, generator=g) * 0.1).to(DEV)
     outs = []
-    try:
-        for cols in (0, 1, 2):  # gather, column walker R = 8, R = 16
-            assert lib.lea_resample_bf16_set_cols(cols) == 0
+    for cols in (0, 1, 2):  # gather, column walker R = 8, R = 16
+        with _lib.tuning(lea_resample_bf16_set_cols=cols):
             big = torch.full((b, c // 8 + 2) + tuple(dst) + (8,), 7.0, device=DEV, dtype=torch.bfloat16)
             kernels.resample_trilinear_bf16(x, dst, ac, big[:, 1:1 + c // 8], scale, shift, relu=True)
             outs.append(big)
-    finally:
-        lib.lea_resample_bf16_set_cols(1)
     assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
     assert bool((outs[1][:, 0] == 7.0).all()) and bool((outs[1][:, -1] == 7.0).all())
 
@@ -376,7 +372,6 @@ def test_stream_kernel_is_the_tile_kernel(b, cin, cout, shape, mode):
     on odd D (a half last step), ragged H/W, column segments along D, every epilogue,
     an output block slice, and vs float64 torch within the bf16 tolerance."""
     from leastereo_amd import _lib
-    lib = _lib.load()
     d, h, w = shape
     g = torch.Generator().manual_seed(cin + cout + d)
     x = _bf(torch.randn((b, cin) + shape, generator=g))
@@ -388,8 +383,7 @@ def test_stream_kernel_is_the_tile_kernel(b, cin, cout, shape, mode):
     packed = kernels.pack_conv_weight_bf16(wt.to(DEV))
     outs = []
     for variant in (0, 1):
-        assert lib.lea_conv3d_bf16_set_variant(variant) == 0
-        try:
+        with _lib.tuning(lea_conv3d_bf16_set_variant=variant):
             name = kernels.conv_kernel_name_bf16(b, cout, cin, d, h, w, 3)
             assert name.startswith("conv_bf16_stream_kernel<" if variant == 0 else "conv_bf16_kernel<"), name
             big = torch.zeros((b, cout // 8 + 2, d, h, w, 8), device=DEV, dtype=torch.bfloat16)
@@ -401,8 +395,6 @@ def test_stream_kernel_is_the_tile_kernel(b, cin, cout, shape, mode):
             torch.cuda.synchronize()
             assert float(big[:, 0].float().abs().sum()) == 0 and float(big[:, -1].float().abs().sum()) == 0
             outs.append(out.clone())
-        finally:
-            lib.lea_conv3d_bf16_set_variant(0)
     assert torch.equal(outs[0], outs[1])
     want = F.conv3d(x.double(), wt.double(), None, 1, 1)
     want = torch.relu(want * scale.double().view(1, -1, 1, 1, 1) + shift.double().view(1, -1, 1, 1, 1))
@@ -445,7 +437,6 @@ def test_stream_1x1_is_the_tile_kernel(b, cin, cout, shape, mode, cin2):
     cout blocks, two sources (a block-slice cat), residual and accumulate epilogues, an
     output block slice; and matches float64 torch within the bf16 tolerance."""
     from leastereo_amd import _lib
-    lib = _lib.load()
     g = torch.Generator().manual_seed(cin * 3 + cout + b)
     x = _bf(torch.randn((b, cin) + shape, generator=g))
     wt = _bf(torch.randn(cout, cin, 1, 1, 1, generator=g) / np.sqrt(cin))
@@ -457,8 +448,7 @@ def test_stream_1x1_is_the_tile_kernel(b, cin, cout, shape, mode, cin2):
     packed = kernels.pack_conv_weight_bf16(wt.to(DEV))
     outs = []
     for on in (1, 0):
-        assert lib.lea_conv3d_bf16_set_stream1x1(on) == 0
-        try:
+        with _lib.tuning(lea_conv3d_bf16_set_stream1x1=on):
             name = kernels.conv_kernel_name_bf16(b, cout, cin, *shape, 1)
             assert name.startswith("conv1x1_c8_kernel<" if on else "conv_bf16_kernel<1,"), name
             big = torch.zeros((b, cout // 8 + 2) + shape + (8,), device=DEV, dtype=torch.bfloat16)
@@ -469,8 +459,6 @@ def test_stream_1x1_is_the_tile_kernel(b, cin, cout, shape, mode, cin2):
             torch.cuda.synchronize()
             assert float(big[:, 0].float().abs().sum()) == 0 and float(big[:, -1].float().abs().sum()) == 0
             outs.append(out.clone())
-        finally:
-            lib.lea_conv3d_bf16_set_stream1x1(1)
     assert torch.equal(outs[0], outs[1])
     want = F.conv3d(x.double(), wt.double())
     want = torch.relu(want * scale.double().view(1, -1, 1, 1, 1) + shift.double().view(1, -1, 1, 1, 1))
@@ -490,7 +478,6 @@ def test_pair_sum_bf16_vs_torch(c, shape, split):
     (split 0) -- against float64 torch on the same bf16 operands, written into a block slice of
     a cat buffer; odd D / ragged H, W."""
     from leastereo_amd import _lib
-    lib = _lib.load()
     g = torch.Generator().manual_seed(c * 3 + shape[0])
     xa, xb = _bf(torch.randn((2, c) + shape, generator=g)), _bf(torch.randn((2, c) + shape, generator=g))
     wa = _bf(torch.randn(c, c, 3, 3, 3, generator=g) / np.sqrt(c * 27))
@@ -506,10 +493,7 @@ def test_pair_sum_bf16_vs_torch(c, shape, split):
     out = big[:, 1:1 + c // 8]
     xa8, xb8 = kernels.to_c8(xa.to(DEV)), kernels.to_c8(xb.to(DEV))
     assert kernels.pair_sum_supported_bf16(xa8, xb8, out)
-    try:
-        assert lib.lea_conv3d_bf16_set_pair_split(split) == 0
+    with _lib.tuning(lea_conv3d_bf16_set_pair_split=split):
         kernels.conv3d_bnrelu_bf16(xa8, packed, c, 3, sc.to(DEV), sh.to(DEV), True, out, x2=xb8, pair_sum=True)
-    finally:
-        lib.lea_conv3d_bf16_set_pair_split(3)
     _close(kernels.from_c8(out.contiguous()), want)
     assert bool((big[:, 0] == 5.0).all()) and bool((big[:, -1] == 5.0).all())

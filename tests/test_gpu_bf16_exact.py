@@ -168,13 +168,10 @@ def test_tile_kernel_every_tile(kind, cin, cout, th, td, mt):
     lib = _lib.load()
     case = conv_case(kind, cin, cout, 3, VOL_A)
     assert ("k3", th, td, mt) not in REFUSED
-    try:
-        assert lib.lea_conv3d_bf16_set_tile_override(th, td, mt) == 0
+    with _lib.tuning(lea_conv3d_bf16_set_tile_override=(th, td, mt)):
         assert kernels.conv_kernel_name_bf16(2, cout, cin, *VOL_A, 3) == tile_name(cin, cout, 3, th, td, mt)
         runs = [(m, 0) for m in MODES] + ([("plain", 32)] if cin == 64 else [])
         outs = [(m, c2, run_conv(case, cout, 3, m, c2)) for m, c2 in runs]
-    finally:
-        lib.lea_conv3d_bf16_set_tile_override(0, 0, 0)
     for mode, c2, got in outs:
         judge("tile", f"{cin}->{cout} th{th} td{td} mt{mt} {mode}{' x2' if c2 else ''}", kind, got,
               case["want"][mode], case["e32"][mode])
@@ -188,14 +185,9 @@ def test_tile_kernel_1x1_every_tile(kind, cin, cout, th, mt):
     with (mt, wc) = (1, 4) / (2, 2) (128 -> 64)."""
     lib = _lib.load()
     case = conv_case(kind, cin, cout, 1, VOL_A)
-    try:
-        assert lib.lea_conv3d_bf16_set_stream1x1(0) == 0
-        assert lib.lea_conv3d_bf16_set_tile_override(th, 1, mt) == 0
+    with _lib.tuning(lea_conv3d_bf16_set_stream1x1=0, lea_conv3d_bf16_set_tile_override=(th, 1, mt)):
         assert kernels.conv_kernel_name_bf16(2, cout, cin, *VOL_A, 1) == tile_name(cin, cout, 1, th, 1, mt)
         outs = [(m, run_conv(case, cout, 1, m)) for m in MODES]
-    finally:
-        lib.lea_conv3d_bf16_set_tile_override(0, 0, 0)
-        lib.lea_conv3d_bf16_set_stream1x1(1)
     for mode, got in outs:
         judge("tile 1x1", f"{cin}->{cout} th{th} mt{mt} {mode}", kind, got, case["want"][mode], case["e32"][mode])
 
@@ -206,16 +198,13 @@ def test_refused_overrides():
     k1 = conv_case("int", 24, 8, 1, (4, 3, 5))
     cv = costvolume_case("int", 16, 16, 27, (5, 19))
     for entry, th, td, mt in sorted(REFUSED):
-        try:
-            assert lib.lea_conv3d_bf16_set_tile_override(th, td, mt) == 0
+        with _lib.tuning(lea_conv3d_bf16_set_tile_override=(th, td, mt)):
             with pytest.raises(_lib.HipKernelError, match=UNSUPPORTED):
                 if entry == "k1":
                     run_conv(k1, 8, 1, "plain")
                 else:
                     kernels.conv3d_bnrelu_costvolume_bf16(cv["flc"], cv["frc"], 27, cv["packed"], 16,
                                                           cv["scale_d"], cv["shift_d"])
-        finally:
-            lib.lea_conv3d_bf16_set_tile_override(0, 0, 0)
     assert lib.lea_conv3d_bf16_set_tile_override(12, 2, 1) == _lib.LEA_E_INVALID  # no such tile at all
     assert lib.lea_conv3d_bf16_set_tile_override(0, 0, 0) == 0
 
@@ -262,13 +251,10 @@ def test_pair_launch_rounds_as_its_kernel(kind, c, shape, split):
     assert kernels.pair_sum_supported_bf16(case["xa"], case["xb"], s.out)
     th, nb = (8, 1) if c == 8 else (4, 2)
     assert kernels.conv_kernel_name_bf16(2, c, c, *shape, 3) == f"conv_bf16_stream_kernel<1, 1, {th}, {nb}, 1>"
-    try:
-        assert lib.lea_conv3d_bf16_set_pair_split(split) == 0
+    with _lib.tuning(lea_conv3d_bf16_set_pair_split=split):
         kernels.conv3d_bnrelu_bf16(case["xa"], case["packed"], c, 3, case["sc"], case["sh"], True, s.out,
                                    x2=case["xb"], pair_sum=True)
         s.check()
-    finally:
-        lib.lea_conv3d_bf16_set_pair_split(3)
     want, alts = J.pair_wants(case["a64"], case["b64"], case["e32"], round_a)
     got = from_c8(s.out)
     judge("pair kernel" if round_a else "pair on stream", f"c{c} {shape} split{split}", kind, got, want,
@@ -321,8 +307,7 @@ def test_costvolume_entry(kind, c, cout, maxdisp, hw, th, td, mt):
     case = costvolume_case(kind, c, cout, maxdisp, hw)
     d3 = maxdisp // 3
     assert ("costvolume", th, td, mt) not in REFUSED
-    try:
-        assert lib.lea_conv3d_bf16_set_tile_override(th, td, mt) == 0
+    with _lib.tuning(lea_conv3d_bf16_set_tile_override=(th, td, mt)):
         name = kernels.conv_kernel_name_bf16(2, cout, 2 * c, d3, *hw, 3, True)
         if th:
             assert name == tile_name(2 * c, cout, 3, th, td, mt, cv=True)
@@ -330,8 +315,6 @@ def test_costvolume_entry(kind, c, cout, maxdisp, hw, th, td, mt):
         got = kernels.conv3d_bnrelu_costvolume_bf16(case["flc"], case["frc"], maxdisp, case["packed"], cout,
                                                     case["scale_d"], case["shift_d"])
         torch.cuda.synchronize()
-    finally:
-        lib.lea_conv3d_bf16_set_tile_override(0, 0, 0)
     judge("cost volume", f"C{c}->{cout} md{maxdisp} {hw} th{th} td{td} mt{mt}", kind, from_c8(got), case["want"],
           case["e32"])
 

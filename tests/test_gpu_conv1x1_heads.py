@@ -58,16 +58,12 @@ def test_each_head_is_its_single_launch(b, cin, cin2, cout_a, bn_a, cout_b, bn_b
 def test_both_forms_of_the_kernel_agree():
     """The vector form (lea_conv1x1_set_vector) and the one-float-per-lane form of the two-head
     kernel store the same values, as the single-output kernel's do."""
-    lib = _lib.load()
     x, _, (wa, wb), (fa, fb) = _operands(2, 64, 0, 16, 8, (4, 6, 16), 5)
     stacked = kernels.pack_conv_weight(torch.cat((wa, wb), 0))
     outs = []
-    try:
-        for on in (0, 1):
-            assert lib.lea_conv1x1_set_vector(on) == 0
+    for on in (0, 1):
+        with _lib.tuning(lea_conv1x1_set_vector=on):
             outs.append(kernels.conv1x1_heads(x, stacked, 16, *fa, True, 8, None, None, False))
-    finally:
-        lib.lea_conv1x1_set_vector(1)
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
 
 

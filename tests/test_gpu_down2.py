@@ -13,7 +13,6 @@ Whole model: the 1x1 conv after the down-sampling moves from the register-staged
 engine to the streamed 1x1 kernel, whose sums associate differently, so fused against unfused
 is held to the project's end-to-end bar (EPE < 1e-3 px, tests/test_gpu_parity.py
 test_e2e_golden), as is the fused route against the reference's golden disparity."""
-import os
 
 import numpy as np
 import pytest
@@ -105,8 +104,7 @@ def test_wino44_down2_is_bit_identical(b, cin, cout, vol, walk, relu):
     scale = (torch.rand(cout, generator=g) + 0.5).to(DEV)
     shift = (torch.randn(cout, generator=g) * 0.3).to(DEV)  # some outputs negative: the ReLU matters
     packed = kernels.pack_conv_weight_wino(wt)
-    assert lib.lea_conv3d_wino2_set_walk(walk) == 0
-    try:
+    with _lib.tuning(lea_conv3d_wino2_set_walk=walk):
         assert kernels.wino_kernel_name(b, cout, d, h, w, cin=cin) == "conv3d_wino44_kernel"
         assert kernels.conv3d_wino_down2_supported(x, cout)
         assert kernels.wino_down2_kernel_name(b, cin, cout, d, h, w) == "conv3d_wino44_down2_kernel"
@@ -114,8 +112,6 @@ def test_wino44_down2_is_bit_identical(b, cin, cout, vol, walk, relu):
         want = kernels.resample_trilinear(full, (d // 2, h // 2, w // 2))
         with kernels.KernelProbe() as probe:
             got = kernels.conv3d_bnrelu_wino_down2(x, packed, cout, scale, shift, relu)
-    finally:
-        assert lib.lea_conv3d_wino2_set_walk(0) == 0
     assert [r[0] for r in probe.records] == ["conv3d_wino44_down2_kernel"]
     assert probe.records[0][2] == 4.0 * (x.numel() + got.numel() + cout * cin * 27)
     if relu:
@@ -130,12 +126,8 @@ def test_wino44_down2_refuses_what_the_tile_does_not_take():
     assert not kernels.conv3d_wino_down2_supported(x.cpu(), 32)
     assert not kernels.conv3d_wino_down2_supported(x, 16)  # the 16-cout layers run another tile
     assert kernels.wino_down2_kernel_name(1, 32, 16, 6, 4, 32) is None
-    lib = _lib.load()
-    assert lib.lea_conv3d_wino44_set(0) == 0  # the F(4,3) x F(2,3) tile: no DOWN form
-    try:
+    with _lib.tuning(lea_conv3d_wino44_set=0):  # the F(4,3) x F(2,3) tile: no DOWN form
         assert not kernels.conv3d_wino_down2_supported(x, 32)
-    finally:
-        assert lib.lea_conv3d_wino44_set(int(os.environ.get("LEASTEREO_WINO44") or 2)) == 0
 
 
 # ---------------------------------------------------------------------- whole model

@@ -118,13 +118,10 @@ def dp_case():
             # the partial sums the launch accumulates onto: a channel slice, as a cell's slot is
             partial = torch.randn((b, cout + 8) + vol, generator=g).to(DEV)
             packed = kernels.pack_conv_weight_wino(wt)
-            assert lib.lea_conv3d_wino2_set_walk(walk) == 0
-            try:
+            with _lib.tuning(lea_conv3d_wino2_set_walk=walk):
                 act = kernels.conv3d_bnrelu_wino(x, packed, cout, scale, shift, relu)
                 full = partial.clone()
                 kernels.conv3d_bnrelu_wino(x, packed, cout, scale, shift, relu, out=full[:, 8:], accumulate=True)
-            finally:
-                assert lib.lea_conv3d_wino2_set_walk(0) == 0
             if relu:
                 assert float((act == 0).float().mean()) > 0.05
             want = kernels.resample_trilinear(full[:, 8:], (d // 2, h // 2, w // 2))
@@ -147,13 +144,9 @@ def test_dp_down2_is_bit_identical(dp_case, b, cin, cout, vol, walk, relu, only)
     assert kernels.wino_dp_down2_kernel_name(b, cin, cout, d, h, w, only) == name
     y = partial.clone()
     down = torch.full((b, cout + 8, d // 2, h // 2, w // 2), 7.0, device=DEV)
-    assert lib.lea_conv3d_wino2_set_walk(walk) == 0
-    try:
-        with kernels.KernelProbe() as probe:
-            kernels.conv3d_bnrelu_wino_dp_down2(x, packed, cout, scale, shift, relu, y[:, 8:], down[:, :cout],
-                                                accumulate=True, only=only)
-    finally:
-        assert lib.lea_conv3d_wino2_set_walk(0) == 0
+    with _lib.tuning(lea_conv3d_wino2_set_walk=walk), kernels.KernelProbe() as probe:
+        kernels.conv3d_bnrelu_wino_dp_down2(x, packed, cout, scale, shift, relu, y[:, 8:], down[:, :cout],
+                                            accumulate=True, only=only)
     assert [r[0] for r in probe.records] == [name]
     assert torch.equal(down[:, :cout], want)
     assert bool((down[:, cout:] == 7.0).all())   # nothing past the slice

@@ -20,8 +20,6 @@ models meet E <= 2^-18 on every input used here (same file), so no bar exceeds 1
 A chain of four ConvBR layers and the disparity head ask the same question one step further.
 Measured values: DESIGN.md, "fp32 engine numerics" (run with -s for the table).
 """
-import contextlib
-import os
 
 import numpy as np
 import pytest
@@ -33,29 +31,6 @@ from tests import f32_judge as J
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-W44_DEFAULT = 2  # lea_conv3d_wino44_set's library default (csrc/conv3d_wino44.hip g_w44)
-
-# every tuning setter used here -> the arguments of its library default
-DEFAULTS = {
-    "lea_conv3d_wino44_set": lambda: (int(os.environ.get("LEASTEREO_WINO44") or W44_DEFAULT),),
-    "lea_conv3d_wino_set_tile_override": lambda: (0, 0, 0),
-    "lea_conv3d_wino_set_variant": lambda: (0,),
-    "lea_conv3d_wino_set_w22": lambda: (0,),
-    "lea_conv1x1_set_vector": lambda: (1,),
-    "lea_disparity_set_register_form": lambda: (4,),
-}
-
-
-@contextlib.contextmanager
-def tuned(settings):
-    lib = _lib.load()
-    try:
-        for name, args in settings:
-            assert getattr(lib, name)(*args) == 0, (name, args)
-        yield
-    finally:
-        for name, _ in settings:
-            getattr(lib, name)(*DEFAULTS[name]())
 
 
 def _direct(j, split=0, **_):
@@ -136,7 +111,7 @@ PATHS = {
 def test_path_error_is_within_four_times_its_model(path):
     key, model, entry, settings, want_name, _, opts = PATHS[path]
     failures = []
-    with tuned(settings):
+    with _lib.tuning(**dict(settings)):
         for case, seed in J.INPUT_SETS:
             j = J.judged(key, case, seed)
             name, y = entry(j, **opts)
@@ -172,7 +147,7 @@ def test_chain_error_is_within_four_times_its_model(engine):
     x0, ws, scales, shifts, _ = J.chain_case()
     e_model = J.chain_error(J.chain_f32(lambda x, w: J.model(model, x, w)))
     c, shape = J.CHAIN_C, J.CHAIN_SHAPE
-    with tuned(settings):
+    with _lib.tuning(**dict(settings)):
         if engine == "direct":
             name = kernels.conv_kernel_name(1, c, *shape, 3)
         else:
@@ -229,7 +204,7 @@ def test_disparity_forms_on_sharp_and_shifted_volumes(shape, md, fast):
         e_cpu = float(np.abs(ref.disp_forward(x, md).double().numpy() - want).max())
         bar = max(J.MARGIN * e_cpu, 32 * float(np.spacing(np.float32(md))))
         for form in (0, 1, 2, 3, 4):
-            with tuned((("lea_disparity_set_register_form", (form,)),)):
+            with _lib.tuning(lea_disparity_set_register_form=form):
                 y = kernels.disparity_regression(x.to(DEV), md, fast).cpu()
             assert torch.isfinite(y).all(), (tag, form, fast)
             err = np.abs(y.double().numpy() - want)

@@ -163,24 +163,16 @@ def test_small_kernel_every_instantiation(kind, cin, cout):
     """conv2d_small_kernel<CIN, NG> on 9 x 35 (a second 32-column tile 3 wide, a ragged row tile for
     TH = 8, 4 and 2) and 1 x 1; plain, residual, accumulate and no ReLU; couts that are no
     multiple of 8 (5, 12, 20) must leave the sentinel channels after them untouched."""
-    lib = _lib.load()
-    try:
-        assert lib.lea_conv2d_set_small(1) == 0
+    with _lib.tuning(lea_conv2d_set_small=1):
         for hw, batch in J.SMALL_SHAPES:
             conv2d_entry("small", kind, cin, cout, hw, batch, small_name(cin, cout))
-    finally:
-        lib.lea_conv2d_set_small(1)
 
 
 def test_small_cases_cover_all_twelve_instantiations():
     """The names the library reports for the cases above are the twelve of
     conv2d_small.hip:155-158 (each case asserts its own name before it launches)."""
-    lib = _lib.load()
-    try:
-        assert lib.lea_conv2d_set_small(1) == 0
+    with _lib.tuning(lea_conv2d_set_small=1):
         names = {kernels.conv2d_kernel_name(2, cout, *J.HW_RAGGED, cin) for cin, cout in J.SMALL}
-    finally:
-        lib.lea_conv2d_set_small(1)
     assert names == {f"conv2d_small_kernel<{ci}, {ng}>" for ci in (4, 8, 12, 16) for ng in (1, 2, 4)}, names
     assert names == {small_name(cin, cout) for cin, cout in J.SMALL}
 
@@ -192,22 +184,14 @@ def test_dma2d_engine_every_tile(kind, cin, cout, hw, batch):
     48, 64), several cout blocks (96: two of mt 3, 192: three of mt 4), the 4 x 16 tile on 9 x 35 /
     9 x 36 and the 8 x 16 tile on 123 x 250 at batch 2 (512 workgroups per cout block, the last
     row tile 3 high, the last column tile 10 wide)."""
-    lib = _lib.load()
     mt, nt = J.DMA2D[(cin, cout, hw, batch)]
-    try:
-        assert lib.lea_conv2d_set_small(0) == 0
+    with _lib.tuning(lea_conv2d_set_small=0):
         conv2d_entry("dma2d", kind, cin, cout, hw, batch, dma2d_name(mt, nt))
-    finally:
-        lib.lea_conv2d_set_small(1)
 
 
 def test_dma2d_cases_cover_all_eight_tiles():
-    lib = _lib.load()
-    try:
-        assert lib.lea_conv2d_set_small(0) == 0
+    with _lib.tuning(lea_conv2d_set_small=0):
         names = {kernels.conv2d_kernel_name(b, cout, hw[0], hw[1], cin) for cin, cout, hw, b in J.DMA2D}
-    finally:
-        lib.lea_conv2d_set_small(1)
     assert names == {dma2d_name(mt, nt) for mt in (1, 2, 3, 4) for nt in (1, 2)}, names
 
 

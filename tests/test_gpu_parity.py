@@ -189,7 +189,6 @@ def test_conv1x1_vector_form_is_the_scalar_form(b, cin, cin2, cout, shape, resid
     """lea_conv1x1_set_vector(1) (lane n owns NT consecutive voxels: vector loads and
     stores) stores exactly what the one-float-per-lane form stores, into a channel slice,
     with the residual epilogue and a second source; both against torch in float64."""
-    lib = _lib.load()
     g = torch.Generator(device=DEV).manual_seed(cin + cout + cin2)
     x = torch.randn((b, cin) + shape, device=DEV, generator=g)
     x2 = torch.randn((b, cin2) + shape, device=DEV, generator=g) if cin2 else None
@@ -200,15 +199,12 @@ def test_conv1x1_vector_form_is_the_scalar_form(b, cin, cin2, cout, shape, resid
     base = torch.randn((b, cout + 8) + shape, device=DEV, generator=g)
     pw = kernels.pack_conv_weight(w)
     outs = []
-    try:
-        for on in (0, 1):
-            assert lib.lea_conv1x1_set_vector(on) == 0
+    for on in (0, 1):
+        with _lib.tuning(lea_conv1x1_set_vector=on):
             y = base.clone()
             kernels.conv3d_bnrelu(x, pw, cout, 1, scale, shift, relu=True, out=y[:, 4:4 + cout], x2=x2,
                                   residual=res)
             outs.append(y)
-    finally:
-        lib.lea_conv1x1_set_vector(1)
     assert torch.equal(outs[0], outs[1])
     xin = torch.cat((x, x2), 1) if cin2 else x
     want = torch.relu(F.conv3d(xin.double(), w.double()) * scale.double().view(1, -1, 1, 1, 1)
@@ -230,7 +226,6 @@ def test_resampled_1x1_gather_matches_staged_engine(cin, cout, src, dst):
     """The gather-GEMM (lea_conv3d_set_rs_gather(1), the default for resampled 1x1 convs)
     stores what the register-staged engine stores (up to the MFMA summation order), into
     a channel slice, with and without the accumulate epilogue."""
-    lib = _lib.load()
     g = torch.Generator(device=DEV).manual_seed(cin + cout)
     x = torch.randn((2, cin) + src, device=DEV, generator=g)
     w = torch.randn(cout, cin, 1, 1, 1, device=DEV, generator=g) / np.sqrt(cin)
@@ -239,15 +234,12 @@ def test_resampled_1x1_gather_matches_staged_engine(cin, cout, src, dst):
     r = torch.randn((2, cout + 8) + dst, device=DEV, generator=g)
     pw = kernels.pack_conv_weight(w)
     outs = []
-    try:
-        for on in (0, 1):
-            assert lib.lea_conv3d_set_rs_gather(on) == 0
+    for on in (0, 1):
+        with _lib.tuning(lea_conv3d_set_rs_gather=on):
             for acc in (False, True):
                 y = r.clone()
                 kernels.conv3d_bnrelu_resampled(x, dst, pw, cout, 1, scale, shift, True, y[:, 3:3 + cout], acc)
                 outs.append(y)
-    finally:
-        lib.lea_conv3d_set_rs_gather(1)
     for a, b in ((outs[0], outs[2]), (outs[1], outs[3])):
         np.testing.assert_allclose(b.cpu().numpy(), a.cpu().numpy(), rtol=1e-5, atol=1e-5)
     xi = F.interpolate(x.double(), dst, mode="trilinear", align_corners=True)
@@ -296,17 +288,13 @@ def test_head_tapsum_rows_pass_is_the_gather_pass(b, cout, src, dst):
     """The fused tap-sum head (passes 1 + 2 in one launch, the default since r05), the
     row-staged pass 2 after pass 1 and the per-row gather pass produce identical bits, f32
     and bf16 (c8) partial sums alike; a non-float4 f32 layout too (odd W)."""
-    lib = _lib.load()
     g = torch.Generator().manual_seed(13)
     q = torch.randn((b, 27 * cout) + src, generator=g).to(DEV)
     qc = kernels.to_c8(torch.cat([q, torch.zeros((b, (-27 * cout) % 8) + src, device=DEV)], 1))
     out = {}
     for on in (2, 1, 0):
-        assert lib.lea_tapsum_set_rows(on) == 0
-        try:
+        with _lib.tuning(lea_tapsum_set_rows=on):
             out[on] = (kernels.tapsum_upsample(q, cout, dst), kernels.tapsum_upsample_bf16(qc, cout, dst))
-        finally:
-            lib.lea_tapsum_set_rows(2)
     for on in (1, 0):
         assert torch.equal(out[2][0], out[on][0]) and torch.equal(out[2][1], out[on][1]), on
     assert not torch.isnan(out[2][0]).any()
@@ -363,18 +351,14 @@ def test_resample_kernels_are_bit_identical(src, dst, ac, epi, ch):
     rows), the row-staged and the gather kernels give the same bits -- trilerp's expression
     tree in each -- with and without the BN/ReLU epilogue, up- and down-sampling, ragged
     row blocks (H 141), 3 to 24 channels, and match torch."""
-    lib = _lib.load()
     g = torch.Generator().manual_seed(sum(dst))
     x = torch.randn((2, ch) + src, generator=g)
     scale = (torch.rand(ch, generator=g) + 0.5).to(DEV) if epi else None
     shift = (torch.randn(ch, generator=g) * 0.1).to(DEV) if epi else None
     outs = []
-    try:
-        for mode in (0, 1, 2):
-            assert lib.lea_resample_set_mode(mode) == 0
+    for mode in (0, 1, 2):
+        with _lib.tuning(lea_resample_set_mode=mode):
             outs.append(kernels.resample_trilinear(x.to(DEV), dst, ac, None, scale, shift, relu=epi).cpu())
-    finally:
-        lib.lea_resample_set_mode(0)
     assert all(torch.equal(outs[0], o) for o in outs[1:])
     want = F.interpolate(x, dst, mode="trilinear", align_corners=ac)
     if epi:
@@ -402,18 +386,14 @@ def test_disparity_register_form_matches_the_lds_form(shape, md):
     axis, softmin shifted by the smallest plane value) and the online-softmin LDS kernel
     agree to fp32 summation noise, f32 and fast-exp alike, and all meet the oracle at the
     1e-3 px bar."""
-    lib = _lib.load()
     g = torch.Generator().manual_seed(11)
     x = torch.randn(shape, generator=g) * 3
     refd = ref.disp_forward(x.double(), md).numpy()
     for fast in (False, True):
         out = {}
         for on in (4, 3, 2, 1, 0):
-            assert lib.lea_disparity_set_register_form(on) == 0
-            try:
+            with _lib.tuning(lea_disparity_set_register_form=on):
                 out[on] = kernels.disparity_regression(x.to(DEV), md, fast).cpu().double().numpy()
-            finally:
-                lib.lea_disparity_set_register_form(4)
             err = np.abs(out[on] - refd)
             assert err.max() < 2e-3 and err.mean() < 1e-4, (fast, on, err.max(), err.mean())
         assert np.abs(out[1] - out[0]).max() < 1e-3 and np.abs(out[2] - out[1]).max() < 1e-3
@@ -479,7 +459,6 @@ def test_conv2d_few_channel_tile_vs_torch(b, cin, cout, hw, res):
     the DMA / MFMA engine it replaces there, against float64 torch: the 1/3 and 1/6
     resolution cell shapes, ragged tiles, cin not a multiple of 4, the cell-sum epilogues
     (accumulate, residual) and an output slice of a wider tensor (the cell's channel slot)."""
-    lib = _lib.load()
     g = torch.Generator().manual_seed(cin * 11 + cout + hw[1])
     x = torch.randn((b, cin) + hw, generator=g)
     w = torch.randn(cout, cin, 3, 3, generator=g) / np.sqrt(cin * 9)
@@ -492,9 +471,8 @@ def test_conv2d_few_channel_tile_vs_torch(b, cin, cout, hw, res):
         refy = refy + r.double()
     pw = kernels.pack_conv2d_weight(w.to(DEV))
     ys = {}
-    try:
-        for small in (1, 0):
-            assert lib.lea_conv2d_set_small(small) == 0
+    for small in (1, 0):
+        with _lib.tuning(lea_conv2d_set_small=small):
             name = kernels.conv2d_kernel_name(b, cout, hw[0], hw[1], cin)
             assert name.startswith("conv2d_small_kernel<") == bool(small), name
             big = torch.full((b, cout + 16, 1) + hw, 7.0, device=DEV)
@@ -506,8 +484,6 @@ def test_conv2d_few_channel_tile_vs_torch(b, cin, cout, hw, res):
             if res == "slice":
                 assert torch.all(big[:, :8] == 7.0) and torch.all(big[:, 8 + cout:] == 7.0)
             ys[small] = y.squeeze(2).cpu().double().numpy()
-    finally:
-        lib.lea_conv2d_set_small(1)
     for small, y in ys.items():
         np.testing.assert_allclose(y, refy.numpy(), rtol=1e-4, atol=1e-4, err_msg=f"small={small}")
 

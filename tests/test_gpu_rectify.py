@@ -219,14 +219,12 @@ def test_both_tiles_give_the_same_bits():
     img = rj.recipe_image((4, 61, 127), 3, seed=2)
     c = np.stack([_rig_calib("rational8", (67, 131)), _rig_calib("fisheye", (67, 131))])
     a = run_raw(img[:2], img[2:], calib=c, size=(67, 131), fill=1)
-    assert lib.lea_rectify_set_tile(2) == _lib.LEA_E_INVALID and lib.lea_rectify_set_tile(1) == 0
-    try:
+    assert lib.lea_rectify_set_tile(2) == _lib.LEA_E_INVALID
+    with _lib.tuning(lea_rectify_set_tile=1):
         b = run_raw(img[:2], img[2:], calib=c, size=(67, 131), fill=1)
         maps = rj.plant_specials(rj.smooth_warp(1, 33, 1031, 61, 127, seed=1), 61, 127, seed=5)
         wide = run_raw(img[:1], img[2:3], maps=maps, fill=171)   # two row-shaped workgroups along x
         assert_pixels_are_judge(wide, img[:1], img[2:3], maps, 171, "row tile")
-    finally:
-        assert lib.lea_rectify_set_tile(0) == 0
     for k in a:
         assert np.array_equal(a[k].view(np.uint8), b[k].view(np.uint8)), k
 

@@ -9,7 +9,6 @@ That bar is a coarse one (two to three decimal digits above a correct float32 en
 N(0,1) inputs only): the tight bar of every Winograd dispatch path -- 4 x a float32 model of
 its algorithm, on inputs with DC offsets, large magnitudes and outliers -- is
 tests/test_gpu_f32_numerics.py (DESIGN.md, "fp32 engine numerics")."""
-import os
 
 import numpy as np
 import pytest
@@ -20,10 +19,6 @@ from leastereo_amd import _lib, kernels
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-WPRE_DEFAULT = 1  # lea_conv3d_wino2p_set_wpre's library default (csrc/conv3d_wino.hip g_wpre)
-W44U_DEFAULT = 0  # lea_conv3d_wino44_set_upre's library default (csrc/conv3d_wino44.hip g_w44u)
-W44G_DEFAULT = -1  # lea_conv3d_wino44_set_group's library default (g_w44g: auto)
-W44_DEFAULT = 2  # lea_conv3d_wino44_set's library default (csrc/conv3d_wino44.hip g_w44)
 
 
 def _ref(x, w, scale, shift, relu, res=None):
@@ -79,8 +74,7 @@ def test_wino_every_tile(np_, td, cout, f):
     w = torch.randn(cout, 32, 3, 3, 3, generator=g) / np.sqrt(32 * 27)
     r = torch.randn((2, cout, 5, 11, 45), generator=g)
     want = _ref(x, w, None, None, False, r)
-    assert lib.lea_conv3d_wino_set_tile_override(np_, td, f) == 0
-    try:
+    with _lib.tuning(lea_conv3d_wino_set_tile_override=(np_, td, f)):
         name = kernels.wino_kernel_name(2, cout, 5, 11, 45)
         mt = {16: 1, 48: 3, 64: 2}[cout]
         ff, q = (4, 8) if f == 8 else (f, 16)
@@ -88,8 +82,6 @@ def test_wino_every_tile(np_, td, cout, f):
         out = r.to(DEV).clone()
         kernels.conv3d_bnrelu_wino(x.to(DEV), kernels.pack_conv_weight_wino(w.to(DEV)), cout, None,
                                    None, relu=False, out=out, accumulate=True)
-    finally:
-        lib.lea_conv3d_wino_set_tile_override(0, 0, 0)
     np.testing.assert_allclose(out.cpu().double().numpy(), want.numpy(), rtol=1e-4, atol=1e-4)
 
 
@@ -148,8 +140,7 @@ def test_small_cout_tiles_match_the_direct_engine_at_full_size(mode, name):
     MFMA tile, mode 0, the default) and the W x D engine's 16-row block (mode 1) -- vs
     the direct engine.  Packing and launch share the mode."""
     lib = _lib.load()
-    assert lib.lea_conv3d_wino_set_small_cout(mode) == 0
-    try:
+    with _lib.tuning(lea_conv3d_wino_set_small_cout=mode):
         assert kernels.wino_kernel_name(1, 8, 64, 192, 320) == name
         g = torch.Generator(device=DEV).manual_seed(4)
         x = torch.randn((1, 8, 64, 192, 320), device=DEV, generator=g)
@@ -158,8 +149,6 @@ def test_small_cout_tiles_match_the_direct_engine_at_full_size(mode, name):
         b = kernels.conv3d_bnrelu_wino(x, kernels.pack_conv_weight_wino(w), 8, None, None, relu=False)
         err = float((a - b).abs().max())
         assert err <= 1e-4 * float(a.abs().max()), err
-    finally:
-        lib.lea_conv3d_wino_set_small_cout(0)
 
 
 def test_model_uses_the_winograd_engine():
@@ -181,11 +170,8 @@ def test_e2e_golden_with_every_eligible_layer_on_winograd(monkeypatch, variant):
     case on the direct engine): EPE vs the reference fp32 / fp64 disparity, with the
     planner's engines (variant 0: W x D where it applies) and F(4,3) along W only."""
     monkeypatch.setattr(kernels, "WINO_MIN_VOXELS", 0)
-    assert _lib.load().lea_conv3d_wino_set_variant(variant) == 0
-    try:
+    with _lib.tuning(lea_conv3d_wino_set_variant=variant):
         _e2e_golden_cases()
-    finally:
-        _lib.load().lea_conv3d_wino_set_variant(0)
 
 
 def _e2e_golden_cases():
@@ -236,8 +222,8 @@ def wino_variant():
 
     def use(v):
         assert lib.lea_conv3d_wino_set_variant(v) == 0
-    yield use
-    lib.lea_conv3d_wino_set_variant(0)
+    with _lib.tuning(lea_conv3d_wino_set_variant=None):
+        yield use
 
 
 @pytest.mark.parametrize("variant", [2, 3, 4, 5, 6, 7])
@@ -275,11 +261,8 @@ def test_wino2_keeps_the_1d_engine_where_it_has_no_tile(wino_variant, variant):
     wino_variant(variant)
     lib = _lib.load()
     assert kernels.wino_kernel_name(1, 8, 64, 192, 320).startswith("conv3d_wino_kernel<")
-    assert lib.lea_conv3d_wino_set_small_cout(1) == 0
-    try:
+    with _lib.tuning(lea_conv3d_wino_set_small_cout=1):
         assert kernels.wino_kernel_name(1, 8, 64, 192, 320).startswith("conv3d_wino2_kernel<")
-    finally:
-        lib.lea_conv3d_wino_set_small_cout(0)
     assert kernels.wino_kernel_name(1, 48, 32, 96, 160).startswith("conv3d_wino_kernel<")
 
 
@@ -344,18 +327,14 @@ def test_depth_walk_is_bit_identical(b, cin, cout, shape, small):
     scale = torch.rand(cout, device=DEV, generator=g) + 0.5
     shift = torch.randn(cout, device=DEV, generator=g) * 0.1
     r = torch.randn((b, cout) + shape, device=DEV, generator=g)
-    assert lib.lea_conv3d_wino_set_small_cout(small) == 0
-    try:
+    with _lib.tuning(lea_conv3d_wino_set_small_cout=small):
         pw = kernels.pack_conv_weight_wino(w)
         outs = []
         for walk in (1, 2, 3, 4):
-            assert lib.lea_conv3d_wino2_set_walk(walk) == 0
-            y = r.clone()
-            kernels.conv3d_bnrelu_wino(x, pw, cout, scale, shift, True, y, True)
-            outs.append(y)
-    finally:
-        lib.lea_conv3d_wino2_set_walk(0)
-        lib.lea_conv3d_wino_set_small_cout(0)
+            with _lib.tuning(lea_conv3d_wino2_set_walk=walk):
+                y = r.clone()
+                kernels.conv3d_bnrelu_wino(x, pw, cout, scale, shift, True, y, True)
+                outs.append(y)
     for y in outs[1:]:
         assert torch.equal(y, outs[0])
     want = F.conv3d(x.double(), w.double(), None, 1, 1)
@@ -376,30 +355,22 @@ def test_buffer_epilogue_is_bit_identical(b, cin, cout, shape, small, variant):
     stores, into a channel slice of a larger buffer, with and without the residual.  (The
     two-chunk 8 -> 24 shape runs on the F(4,3) x F(4,3) tile by default, which has the
     buffer epilogue only: this test keeps it on the W x D engine it is about, mode 1.)"""
-    lib = _lib.load()
-    assert lib.lea_conv3d_wino44_set(1) == 0
     g = torch.Generator(device=DEV).manual_seed(cin * 5 + cout + shape[2])
     x = torch.randn((b, cin) + shape, device=DEV, generator=g)
     w = torch.randn(cout, cin, 3, 3, 3, device=DEV, generator=g) / np.sqrt(cin * 27)
     scale = torch.rand(cout, device=DEV, generator=g) + 0.5
     shift = torch.randn(cout, device=DEV, generator=g) * 0.1
     r = torch.randn((b, cout + 8) + shape, device=DEV, generator=g)
-    assert lib.lea_conv3d_wino_set_small_cout(small) == 0
-    assert lib.lea_conv3d_wino_set_variant(variant) == 0
-    try:
+    with _lib.tuning(lea_conv3d_wino44_set=1, lea_conv3d_wino_set_small_cout=small,
+                     lea_conv3d_wino_set_variant=variant):
         pw = kernels.pack_conv_weight_wino(w)
         outs = []
         for on in (0, 1):
-            assert lib.lea_conv3d_wino_set_epi_buf(on) == 0
-            for acc in (False, True):
-                y = r.clone()
-                kernels.conv3d_bnrelu_wino(x, pw, cout, scale, shift, True, y[:, 4:4 + cout], acc)
-                outs.append(y)
-    finally:
-        lib.lea_conv3d_wino_set_epi_buf(1)
-        lib.lea_conv3d_wino_set_variant(0)
-        lib.lea_conv3d_wino_set_small_cout(0)
-        lib.lea_conv3d_wino44_set(int(os.environ.get("LEASTEREO_WINO44") or W44_DEFAULT))
+            with _lib.tuning(lea_conv3d_wino_set_epi_buf=on):
+                for acc in (False, True):
+                    y = r.clone()
+                    kernels.conv3d_bnrelu_wino(x, pw, cout, scale, shift, True, y[:, 4:4 + cout], acc)
+                    outs.append(y)
     assert torch.equal(outs[0], outs[2]) and torch.equal(outs[1], outs[3])
     assert torch.equal(outs[3][:, :4], r[:, :4]) and torch.equal(outs[3][:, 4 + cout:], r[:, 4 + cout:])
     want = F.conv3d(x.double(), w.double(), None, 1, 1)
@@ -437,12 +408,11 @@ def test_wd_halo16_is_bit_identical_to_dword_pieces(b, cin, c1, cout, shape, mod
     x1, x2 = (xs[:, :c1].contiguous(), xs[:, c1:].contiguous()) if c1 < cin else (xs, None)
     pw = kernels.pack_conv_weight_wino(w.to(DEV))
     outs = {}
-    assert lib.lea_conv3d_wino44_set(0) == 0  # this test is the F(4,3) x F(2,3) kernel's
     # (halo16, pipeline, fence, W-transformed per-lane weights: r06 lea_conv3d_wino2p_set_wpre)
     for on, pipe, fence, wpre in ((1, 1, 1, 0), (1, 0, 1, 0), (0, 1, 1, 0), (1, 1, 0, 0), (1, 1, 1, 1)):
-        assert lib.lea_conv3d_wino2_set_halo16(on) == 0 and lib.lea_conv3d_wino2_set_pipeline(pipe) == 0
-        assert lib.lea_conv3d_wino_set_fence(fence) == 0 and lib.lea_conv3d_wino2p_set_wpre(wpre) == 0
-        try:
+        # lea_conv3d_wino44_set(0): this test is the F(4,3) x F(2,3) kernel's
+        with _lib.tuning(lea_conv3d_wino44_set=0, lea_conv3d_wino2_set_halo16=on, lea_conv3d_wino2_set_pipeline=pipe,
+                         lea_conv3d_wino_set_fence=fence, lea_conv3d_wino2p_set_wpre=wpre):
             name = kernels.wino_kernel_name(b, cout, *shape, cin=cin)
             if cout <= 8:
                 want_name = "conv3d_wino_kernel<4, 16, 0, 1, 2, false%s>" % (
@@ -456,12 +426,6 @@ def test_wd_halo16_is_bit_identical_to_dword_pieces(b, cin, c1, cout, shape, mod
             outs[(on, pipe, fence, wpre)] = kernels.conv3d_bnrelu_wino(
                 x1, pw, cout, scale.to(DEV), shift.to(DEV), relu=True, out=out, accumulate=mode == "acc", x2=x2,
                 residual=r.to(DEV) if mode == "res" else None)
-        finally:
-            lib.lea_conv3d_wino2_set_halo16(1)
-            lib.lea_conv3d_wino2_set_pipeline(1)
-            lib.lea_conv3d_wino_set_fence(1)
-            lib.lea_conv3d_wino2p_set_wpre(int(os.environ.get("LEASTEREO_WINO2P_WPRE") or WPRE_DEFAULT))
-    lib.lea_conv3d_wino44_set(int(os.environ.get("LEASTEREO_WINO44") or W44_DEFAULT))
     base = outs[(0, 1, 1, 0)]
     assert all(torch.equal(o, base) for o in outs.values()), [k for k, o in outs.items() if not torch.equal(o, base)]
     np.testing.assert_allclose(outs[(1, 1, 1, 0)].cpu().double().numpy(), want.numpy(), rtol=1e-4, atol=1e-4)
@@ -492,16 +456,13 @@ def test_lane_halo16_is_bit_identical_to_dword_pieces(b, cin, c1, cout, shape, m
     pw = kernels.pack_conv_weight_wino(w.to(DEV))
     outs = {}
     for on in (1, 2, 0):
-        assert lib.lea_conv3d_wino2_set_lane_halo16(on) == 0
-        try:
+        with _lib.tuning(lea_conv3d_wino2_set_lane_halo16=on):
             name = kernels.wino_kernel_name(b, cout, *shape, cin=cin)
             assert name == "conv3d_wino2_kernel<8, 1, 1, 4, 2, %d, false>" % {1: 4, 2: 5, 0: 0}[on], name
             out = r.to(DEV).clone() if mode == "acc" else None
             outs[on] = kernels.conv3d_bnrelu_wino(x1, pw, cout, scale.to(DEV), shift.to(DEV), relu=True, out=out,
                                                   accumulate=mode == "acc", x2=x2,
                                                   residual=r.to(DEV) if mode == "res" else None)
-        finally:
-            lib.lea_conv3d_wino2_set_lane_halo16(2)
     assert torch.equal(outs[1], outs[0]) and torch.equal(outs[2], outs[0])
     np.testing.assert_allclose(outs[1].cpu().double().numpy(), want.numpy(), rtol=1e-4, atol=1e-4)
 
@@ -532,9 +493,8 @@ def test_wino22_vs_torch(b, cin, cout, shape, mode, split):
     xd = x.to(DEV)
     x1, x2 = (xd[:, :split].contiguous(), xd[:, split:].contiguous()) if split else (xd, None)
     got = {}
-    try:
-        for on in (1, 0):
-            assert lib.lea_conv3d_wino_set_w22(on) == 0
+    for on in (1, 0):
+        with _lib.tuning(lea_conv3d_wino_set_w22=on):
             name = kernels.wino_kernel_name(b, cout, *shape)
             assert (name == "conv3d_wino22_kernel") == bool(on), name
             out = r.to(DEV).clone() if mode == "acc" else None
@@ -542,8 +502,6 @@ def test_wino22_vs_torch(b, cin, cout, shape, mode, split):
                                                  out=out, accumulate=mode == "acc", x2=x2,
                                                  residual=r.to(DEV) if mode == "res" else None)
             np.testing.assert_allclose(got[on].cpu().double().numpy(), want, rtol=1e-4, atol=1e-4)
-    finally:
-        lib.lea_conv3d_wino_set_w22(0)
 
 
 def test_wino22_writes_only_its_channel_slice():
@@ -553,12 +511,9 @@ def test_wino22_writes_only_its_channel_slice():
     x = torch.randn((1, 16, 4, 9, 40), generator=g).to(DEV)
     w = (torch.randn(16, 16, 3, 3, 3, generator=g) / np.sqrt(16 * 27)).to(DEV)
     big = torch.full((1, 48, 4, 9, 40), 3.0, device=DEV)
-    try:
-        assert lib.lea_conv3d_wino_set_w22(1) == 0
+    with _lib.tuning(lea_conv3d_wino_set_w22=1):
         kernels.conv3d_bnrelu_wino(x, kernels.pack_conv_weight_wino(w), 16, None, None, relu=False,
                                    out=big[:, 16:32])
-    finally:
-        lib.lea_conv3d_wino_set_w22(0)
     want = F.conv3d(x.double(), w.double(), None, 1, 1)
     np.testing.assert_allclose(big[:, 16:32].cpu().double().numpy(), want.cpu().numpy(), rtol=1e-4, atol=1e-4)
     assert bool((big[:, :16] == 3.0).all()) and bool((big[:, 32:] == 3.0).all())
@@ -588,9 +543,7 @@ def test_wino44_vs_float64(b, cin, c1, cout, shape, mode):
     pw = kernels.pack_conv_weight_wino(w.to(DEV))
     outs = {}
     for on, upre, grp in ((0, 0, 0), (1, 0, 0), (1, 1, 0), (1, 0, 2), (1, 0, 3), (1, 0, 16)):
-        assert lib.lea_conv3d_wino44_set(on) == 0 and lib.lea_conv3d_wino44_set_upre(upre) == 0
-        assert lib.lea_conv3d_wino44_set_group(grp) == 0
-        try:
+        with _lib.tuning(lea_conv3d_wino44_set=on, lea_conv3d_wino44_set_upre=upre, lea_conv3d_wino44_set_group=grp):
             name = kernels.wino_kernel_name(b, cout, *shape, cin=cin)
             if cin > 8:
                 assert name == ("conv3d_wino44_kernel" if on else "conv3d_wino2p_kernel"), name
@@ -598,10 +551,6 @@ def test_wino44_vs_float64(b, cin, c1, cout, shape, mode):
             outs[(on, upre, grp)] = kernels.conv3d_bnrelu_wino(
                 x1, pw, cout, scale.to(DEV), shift.to(DEV), relu=True, out=out, accumulate=mode == "acc", x2=x2,
                 residual=r.to(DEV) if mode == "res" else None).cpu().double()
-        finally:
-            lib.lea_conv3d_wino44_set(int(os.environ.get("LEASTEREO_WINO44") or W44_DEFAULT))
-            lib.lea_conv3d_wino44_set_upre(int(os.environ.get("LEASTEREO_WINO44_UPRE") or W44U_DEFAULT))
-            lib.lea_conv3d_wino44_set_group(W44G_DEFAULT)
     np.testing.assert_allclose(outs[(1, 0, 0)].numpy(), want.numpy(), rtol=1e-4, atol=1e-4)
     np.testing.assert_allclose(outs[(1, 0, 0)].numpy(), outs[(0, 0, 0)].numpy(), rtol=1e-4, atol=1e-4)
     # U precomputed by the packer (lea_conv3d_wino44_set_upre): the kernel's own operations, same bits
@@ -626,14 +575,11 @@ def test_wino44_modes_vs_float64(mode, b, cin, cout, shape, res):
     r = torch.randn((b, cout) + shape, generator=g)
     want = _ref(x, w, scale, shift, True, r if res else None)
     pw = kernels.pack_conv_weight_wino(w.to(DEV))
-    assert lib.lea_conv3d_wino44_set(mode) == 0
-    try:
+    with _lib.tuning(lea_conv3d_wino44_set=mode):
         assert kernels.wino_kernel_name(b, cout, *shape, cin=cin) == "conv3d_wino44_kernel"
         out = r.to(DEV).clone() if res == "acc" else None
         y = kernels.conv3d_bnrelu_wino(x.to(DEV), pw, cout, scale.to(DEV), shift.to(DEV), relu=True, out=out,
                                        accumulate=res == "acc", residual=r.to(DEV) if res == "res" else None)
-    finally:
-        lib.lea_conv3d_wino44_set(int(os.environ.get("LEASTEREO_WINO44") or W44_DEFAULT))
     np.testing.assert_allclose(y.cpu().double().numpy(), want.numpy(), rtol=1e-4, atol=1e-4)
 
 
@@ -652,14 +598,11 @@ def test_wino44_grouped_order_on_large_grids(cin, cout, shape):
     shift = torch.randn(cout, device=DEV, generator=g) * 0.1
     pw = kernels.pack_conv_weight_wino(w)
     outs = []
-    try:
-        for grp in (0, -1, 16):
-            assert lib.lea_conv3d_wino44_set_group(grp) == 0
+    for grp in (0, -1, 16):
+        with _lib.tuning(lea_conv3d_wino44_set_group=grp):
             y = torch.full((1, cout) + shape, float("nan"), device=DEV)
             kernels.conv3d_bnrelu_wino(x, pw, cout, scale, shift, True, y)
             outs.append(y)
-    finally:
-        lib.lea_conv3d_wino44_set_group(W44G_DEFAULT)
     assert kernels.wino_kernel_name(1, cout, *shape, cin=cin) == "conv3d_wino44_kernel"
     assert torch.isfinite(outs[0]).all()
     assert torch.equal(outs[1], outs[0]) and torch.equal(outs[2], outs[0])
@@ -670,3 +613,29 @@ def test_wino44_grouped_order_on_large_grids(cin, cout, shape):
     want = torch.relu(want * scale.double().cpu().view(1, -1, 1, 1, 1) + shift.double().cpu().view(1, -1, 1, 1, 1))
     np.testing.assert_allclose(outs[0][:, :, d0:, h0:, w0:].double().cpu().numpy(), want.numpy(),
                                rtol=1e-4, atol=1e-4)
+
+
+@pytest.mark.parametrize("cin,cout,shape", [(32, 32, (4, 2, 32)), (16, 16, (6, 5, 68))])
+def test_tuning_block_launches_what_the_raw_setter_calls_launch(cin, cout, shape):
+    """_lib.tuning(lea_conv3d_wino44_set=0) against lea_conv3d_wino44_set(0) ... set(previous):
+    the same bits inside the block and after it."""
+    lib = _lib.load()
+    g = torch.Generator(device=DEV).manual_seed(cin + cout)
+    x = torch.randn((1, cin) + shape, device=DEV, generator=g)
+    pw = kernels.pack_conv_weight_wino(torch.randn(cout, cin, 3, 3, 3, device=DEV, generator=g) / np.sqrt(cin * 27))
+
+    def run():
+        return kernels.wino_kernel_name(1, cout, *shape, cin=cin), kernels.conv3d_bnrelu_wino(x, pw, cout, None, None, True)
+    previous, = _lib.tuning_get("lea_conv3d_wino44_set")
+    with _lib.tuning(lea_conv3d_wino44_set=None):  # (the raw calls below are the test's subject)
+        assert lib.lea_conv3d_wino44_set(0) == 0
+        raw_in = run()
+        assert lib.lea_conv3d_wino44_set(previous) == 0
+        raw_after = run()
+    with _lib.tuning(lea_conv3d_wino44_set=0):
+        got_in = run()
+    got_after = run()
+    assert _lib.tuning_get("lea_conv3d_wino44_set") == (previous,)
+    assert got_in[0] == raw_in[0] and torch.equal(got_in[1], raw_in[1])
+    assert got_after[0] == raw_after[0] and torch.equal(got_after[1], raw_after[1])
+    assert bool(torch.isfinite(got_in[1]).all()) and bool(torch.isfinite(got_after[1]).all())

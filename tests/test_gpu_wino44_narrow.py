@@ -11,7 +11,6 @@ sources, batch 2).  Then the narrow tile against float64 torch at the project's 
 the float32 judge (tests/f32_judge.py) under the rule of tests/test_gpu_f32_numerics.py, and the
 whole model with the tile forced wide and on auto."""
 import itertools
-import os
 
 import numpy as np
 import pytest
@@ -26,8 +25,6 @@ from tests.golden_util import normal, state_dict
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-TILE_DEFAULT = -1  # lea_conv3d_wino44_set_tile's library default (csrc/conv3d_wino44.hip g_w44t: auto)
-W44_DEFAULT = 2  # lea_conv3d_wino44_set's (g_w44)
 
 # case: (batch, cin, first source's channels, cout, (D, H, W))
 CASES = {
@@ -40,13 +37,6 @@ CASES = {
     "g": (1, 128, 64, 64, (4, 4, 16)),
     "h": (2, 32, 32, 32, (5, 6, 20)),
 }
-
-
-def _restore(lib):
-    lib.lea_conv3d_wino44_set_tile(int(os.environ.get("LEASTEREO_WINO44_TILE") or TILE_DEFAULT))
-    lib.lea_conv3d_wino2_set_walk(int(os.environ.get("LEASTEREO_WINO2_WALK") or 0))
-    lib.lea_conv3d_wino44_set_group(-1)
-    lib.lea_conv3d_wino44_set(int(os.environ.get("LEASTEREO_WINO44") or W44_DEFAULT))
 
 
 def _operands(case):
@@ -69,9 +59,8 @@ def _run(case, ops, tile, relu, resid, affine, walk=0, group=-1):
     _, x1, x2, _, pw, scale, shift, res = ops
     big = torch.full((b, cout + 16) + vol, float("nan"), device=DEV)
     y = big[:, 8:8 + cout]
-    try:
-        assert lib.lea_conv3d_wino44_set_tile(tile) == 0
-        assert lib.lea_conv3d_wino2_set_walk(walk) == 0 and lib.lea_conv3d_wino44_set_group(group) == 0
+    with _lib.tuning(lea_conv3d_wino44_set_tile=tile, lea_conv3d_wino2_set_walk=walk,
+                     lea_conv3d_wino44_set_group=group):
         assert kernels.wino_kernel_name(b, cout, *vol, cin=cin) == "conv3d_wino44_kernel"
         assert lib.lea_conv3d_wino44_tile(b, cin, cout, *vol) == tile
         if resid == "acc":
@@ -79,8 +68,6 @@ def _run(case, ops, tile, relu, resid, affine, walk=0, group=-1):
         kernels.conv3d_bnrelu_wino(x1, pw, cout, scale if affine else None, shift if affine else None, relu=relu,
                                    out=y, accumulate=resid == "acc", x2=x2,
                                    residual=res if resid == "res" else None)
-    finally:
-        _restore(lib)
     assert bool(big[:, :8].isnan().all()) and bool(big[:, 8 + cout:].isnan().all()), "sentinel channels written"
     return y.clone()
 
@@ -138,8 +125,7 @@ def test_narrow_tile_error_is_within_four_times_its_model(key, mode):
     """E <= 4 x max(E(wino_f32(4, 4)), E(direct_f32)) on the judge's inputs: Judged.bar."""
     lib = _lib.load()
     failures = []
-    try:
-        assert lib.lea_conv3d_wino44_set(mode) == 0 and lib.lea_conv3d_wino44_set_tile(16) == 0
+    with _lib.tuning(lea_conv3d_wino44_set=mode, lea_conv3d_wino44_set_tile=16):
         for case, seed in J.INPUT_SETS:
             j = J.judged(key, case, seed)
             x, w = torch.from_numpy(j.x).to(DEV), torch.from_numpy(j.w).to(DEV)
@@ -155,8 +141,6 @@ def test_narrow_tile_error_is_within_four_times_its_model(key, mode):
                   f"direct {j.e['direct'][0]:.2e} bar {bar:.2e}")
             if not e <= bar:
                 failures.append((case, seed, e, bar))
-    finally:
-        _restore(lib)
     assert not failures, (key, failures)
 
 
@@ -171,9 +155,8 @@ def test_disparity_is_equal_with_the_tile_wide_and_auto(height, width, maxdisp):
     m = m.to(DEV).eval()
     left, right = normal(931, (1, 3, height, width)).to(DEV), normal(932, (1, 3, height, width)).to(DEV)
     out = {}
-    try:
-        for tile in (32, -1):
-            assert lib.lea_conv3d_wino44_set_tile(tile) == 0
+    for tile in (32, -1):
+        with _lib.tuning(lea_conv3d_wino44_set_tile=tile):
             with torch.no_grad(), kernels.KernelProbe() as probe:
                 out[tile] = m(left, right)
             shapes = [r.shape for r in probe.records if r.name == "conv3d_wino44_kernel"]
@@ -184,7 +167,5 @@ def test_disparity_is_equal_with_the_tile_wide_and_auto(height, width, maxdisp):
             elif width == 576:
                 assert (1, 32, 96, 8, 24, 48) in [tuple(s[:6]) for s in shapes] and tiles == {16, 32}
                 assert lib.lea_conv3d_wino44_tile(1, 32, 96, 8, 24, 48) == 16
-    finally:
-        _restore(lib)
     assert not out[32].isnan().any()
     assert torch.equal(out[-1], out[32])

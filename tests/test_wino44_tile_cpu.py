@@ -1,14 +1,11 @@
 """lea_conv3d_wino44_set_tile / lea_conv3d_wino44_tile (the F(4,3) x F(4,3) tile's geometry:
-32 x 2 or 16 x 4, csrc/conv3d_wino44.hip tile44) through the query and the setter alone: nothing
+32 x 2 or 16 x 4, route() in csrc/conv3d_wino.hip) through the query and the setter alone: nothing
 launches."""
-import os
-
 import pytest
 
 from leastereo_amd import _lib
 
 INVALID = 1001
-TILE_DEFAULT = -1  # the library default (g_w44t: auto)
 
 C2_L0, C2_L1, C2_L2 = (64, 192, 320), (32, 96, 160), (16, 48, 80)
 C5_L0, C5_L1, C5_L2 = (88, 336, 504), (44, 168, 252), (22, 84, 126)
@@ -20,9 +17,8 @@ DOWN2 = ((1, 32, 32, 64, 192, 320), (1, 32, 32, 88, 336, 504), (2, 32, 32, 16, 3
 
 @pytest.fixture
 def lib():
-    lib = _lib.load()
-    yield lib
-    lib.lea_conv3d_wino44_set_tile(int(os.environ.get("LEASTEREO_WINO44_TILE") or TILE_DEFAULT))
+    with _lib.tuning(lea_conv3d_wino44_set_tile=None):  # (the tests call the setter themselves)
+        yield _lib.load()
 
 
 def test_setter_takes_auto_and_the_two_widths_only(lib):
@@ -67,19 +63,13 @@ def test_forced_tiles_and_shapes_off_the_tile(lib):
         assert lib.lea_conv3d_wino44_tile(1, 30, 32, *C2_L2) == 0
         assert lib.lea_conv3d_wino44_tile(0, 32, 32, *C2_L2) == 0
     # the narrow geometry is built for the default form only
-    try:
-        assert lib.lea_conv3d_wino44_set_upre(1) == 0
+    with _lib.tuning(lea_conv3d_wino44_set_upre=1):
         assert lib.lea_conv3d_wino44_tile(1, 32, 32, *C2_L2) == 32
-        assert lib.lea_conv3d_wino44_set_upre(0) == 0 and lib.lea_conv3d_wino44_set_sched(1) == 0
+    with _lib.tuning(lea_conv3d_wino44_set_upre=0, lea_conv3d_wino44_set_sched=1):
         assert lib.lea_conv3d_wino44_tile(1, 32, 32, *C2_L2) == 32
-    finally:
-        lib.lea_conv3d_wino44_set_upre(0), lib.lea_conv3d_wino44_set_sched(0)
     # the two-barrier tile takes the layers with lea_conv3d_wino44_set(0): not this tile's
-    try:
-        assert lib.lea_conv3d_wino44_set(0) == 0
+    with _lib.tuning(lea_conv3d_wino44_set=0):
         assert lib.lea_conv3d_wino44_tile(1, 32, 32, *C2_L2) == 0
-    finally:
-        lib.lea_conv3d_wino44_set(int(os.environ.get("LEASTEREO_WINO44") or 2))
 
 
 def test_names_and_down2_answers_do_not_depend_on_the_tile(lib):
