@@ -129,8 +129,16 @@ int lea_conv3d_bnrelu_costvolume(const void* left, const void* right, int64_t f_
 const char* lea_conv3d_costvolume_kernel_name(int B, int cout, int D3, int H, int W);
 
 /* Name of the kernel instantiation a conv of this output shape launches
- * (matches the demangled name rocprofv3 reports); NULL if unsupported. */
+ * (matches the demangled name rocprofv3 reports), for a single source of at most 128 input
+ * channels; NULL if unsupported.  Every *_kernel_name query answers NULL, with lea_last_error
+ * set, for a plan without an instantiation (a tile override can ask for one): the launch
+ * returns LEA_E_UNSUPPORTED. */
 const char* lea_conv3d_kernel_name(int B, int cout, int D, int H, int W, int k, int resampled);
+/* The same for the whole argument list of lea_conv3d_bnrelu / lea_conv3d_bnrelu_resampled
+ * (cin2 of the cin input channels in the second source): a resampled 1x1 of more than 128
+ * input channels or of two sources runs on the register-staged engine. */
+const char* lea_conv3d_launch_kernel_name(int B, int cin, int cin2, int cout, int D, int H, int W, int k,
+                                          int resampled);
 
 /* ---- 2D feature net (retrain/new_model_2d.py; models/operations_2d.py:31-47) ----
  * 1x1 Conv2d and bilinear (align_corners) resizes of the feature net use the 3D
@@ -666,9 +674,14 @@ int lea_conv3d_bnrelu_costvolume_bf16(const void* left, const void* right, int64
                                       int H, int W, unsigned flags, void* stream);
 
 
-/* Kernel instantiation the bf16 conv of this shape launches. */
+/* Kernel instantiation the bf16 conv of this shape launches from one source without flags. */
 const char* lea_conv3d_kernel_name_bf16(int B, int cout, int cin, int D, int H, int W, int k,
                                         int costvolume);
+/* The same for the whole argument list of lea_conv3d_bnrelu_bf16 (cin2 of the cin input channels
+ * in the second source; flags: LEA_PAIR_SUM selects the pair launch's kernel); NULL where the
+ * launch refuses. */
+const char* lea_conv3d_launch_kernel_name_bf16(int B, int cin, int cin2, int cout, int D, int H, int W, int k,
+                                               unsigned flags, int costvolume);
 
 /* 1 if lea_conv3d_bnrelu_bf16 takes LEA_PAIR_SUM for two sources of `cin` channels each
  * into `cout` (3x3x3) at this shape -- the planner's D-streaming form under the current

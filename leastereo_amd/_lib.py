@@ -43,6 +43,7 @@ SIGNATURES = {
     "lea_conv3d_bnrelu_resampled": (_i, [_p, _i64, _i, _i, _i, _p, _p, _p, _p, _i64, _p, _i64,
                                          _i, _i, _i, _i, _i, _i, _i, _u, _i, _p]),
     "lea_conv3d_kernel_name": (ctypes.c_char_p, [_i, _i, _i, _i, _i, _i, _i]),
+    "lea_conv3d_launch_kernel_name": (ctypes.c_char_p, [_i] * 9),
     "lea_conv3d_set_tile_override": (_i, [_i, _i, _i]),
     "lea_conv3d_bnrelu_costvolume": (_i, [_p, _p, _i64, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _i,
                                           _i, _u, _i, _p]),
@@ -102,6 +103,7 @@ SIGNATURES = {
     "lea_conv3d_bnrelu_costvolume_bf16": (_i, [_p, _p, _i64, _p, _p, _p, _p, _i64, _i, _i, _i, _i,
                                                _i, _i, _u, _p]),
     "lea_conv3d_kernel_name_bf16": (ctypes.c_char_p, [_i, _i, _i, _i, _i, _i, _i, _i]),
+    "lea_conv3d_launch_kernel_name_bf16": (ctypes.c_char_p, [_i] * 8 + [_u, _i]),
     "lea_conv3d_bf16_pair_supported": (_i, [_i, _i, _i, _i, _i, _i]),
     "lea_conv3d_bf16_set_tile_override": (_i, [_i, _i, _i]),
     "lea_conv3d_bf16_set_variant": (_i, [_i]),

@@ -90,7 +90,31 @@ inline int launch_status(const char* what) {
     }                                                                                        \
   } while (0)
 
+// Launch the kernel named by the macro's tail (template commas and all) as <<<GRID, THREADS, LDS,
+// st>>> ARGS (the parenthesised argument list), or, in a name query (name != NULL), answer AS: one
+// expansion serves both, so a name cannot drift from the launch.  Expects `st` and `name` in scope.
+#define LEA_LAUNCH_AS(AS, WHAT, GRID, THREADS, LDS, ARGS, ...) \
+  do {                                                         \
+    if (name) {                                                \
+      *name = AS;                                              \
+      return LEA_OK;                                           \
+    }                                                          \
+    __VA_ARGS__<<<GRID, THREADS, LDS, st>>> ARGS;              \
+    return ::lea::launch_status(WHAT);                         \
+  } while (0)
+#define LEA_LAUNCH(WHAT, GRID, THREADS, LDS, ARGS, ...) \
+  LEA_LAUNCH_AS(#__VA_ARGS__, WHAT, GRID, THREADS, LDS, ARGS, __VA_ARGS__)
+
 constexpr int kWave = 64;
+
+// The walking 1x1 kernels (f32 gather-GEMM, bf16 streamed 1x1): about 8192 waves over the
+// `groups` (batch x cout blocks), four per workgroup, each walking *tpw 16-voxel tiles of the flat
+// run of `vox` voxels.  Returns the workgroups per group.
+inline long long walk_grid(long long vox, long long groups, int* tpw) {
+  const long long tiles = (vox + 15) / 16, t = (tiles * groups + 8191) / 8192;
+  *tpw = (int)(t > 1 ? t : 1);
+  return (tiles + 4 * *tpw - 1) / (4 * *tpw);
+}
 
 // do the byte spans [a, a + an) and [b, b + bn) share a byte?  (the entries' aliasing checks)
 inline bool spans_overlap(const void* a, size_t an, const void* b, size_t bn) {

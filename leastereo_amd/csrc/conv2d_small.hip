@@ -135,23 +135,21 @@ LEA_TUNING_INT(lea_conv2d_set_small, g_conv2d_small, 1, 0, 1, "on=%d")
 
 bool conv2d_small_ok(int cin, int cout) { return g_conv2d_small && cin <= 16 && cout <= 32; }
 
-static int ng_of(int cout) { return cout <= 8 ? 1 : cout <= 16 ? 2 : 4; }
-
-const char* conv2d_small_name(int cin, int cout) {
-  static thread_local char name[64];
-  snprintf(name, sizeof(name), "conv2d_small_kernel<%d, %d>", (cin + 3) / 4 * 4, ng_of(cout));
-  return name;
+// engine 6's plan: conv2d_small_kernel<mt = cin padded to fours, nt = groups of 8 couts>
+Plan conv2d_small_plan(int cin, int cout) {
+  Plan p{};
+  p.engine = 6;
+  p.mt = (cin + 3) / 4 * 4;
+  p.nt = cout <= 8 ? 1 : cout <= 16 ? 2 : 4;
+  return p;
 }
 
-int run_conv2d_small(const ConvArgs& a, int B, hipStream_t st) {
-  const int ng = ng_of(a.cout), cin4 = (a.cin + 3) / 4 * 4, th = 8 / ng;
-  LEA_CHECK_ARG(B <= 65535 && (a.H + th - 1) / th <= 65535, "lea_conv2d: grid too large");
+int run_conv2d_small(const Plan& p, const ConvArgs& a, int B, hipStream_t st, const char** name) {
+  const int th = 8 / p.nt;
+  LEA_CHECK_ARG(name || (B <= 65535 && (a.H + th - 1) / th <= 65535), "lea_conv2d: grid too large");
   const dim3 grid((a.W + kSmallTW - 1) / kSmallTW, (a.H + th - 1) / th, B);
-#define LEA_SMALL2D(CI, G)                                                      \
-  if (cin4 == CI && ng == G) {                                                  \
-    conv2d_small_kernel<CI, G><<<grid, 256, 0, st>>>(a);                        \
-    return launch_status("lea_conv2d(small)");                                  \
-  }
+#define LEA_SMALL2D(CI, G) \
+  if (p.mt == CI && p.nt == G) LEA_LAUNCH("lea_conv2d(small)", grid, 256, 0, (a), conv2d_small_kernel<CI, G>);
   LEA_SMALL2D(4, 1) LEA_SMALL2D(4, 2) LEA_SMALL2D(4, 4)
   LEA_SMALL2D(8, 1) LEA_SMALL2D(8, 2) LEA_SMALL2D(8, 4)
   LEA_SMALL2D(12, 1) LEA_SMALL2D(12, 2) LEA_SMALL2D(12, 4)
@@ -170,26 +168,11 @@ extern "C" int lea_conv2d_bnrelu_pair(const void* x, int64_t x_bstride, const fl
                                       void* stream) {
   using namespace lea;
   clear_error();
-  ConvArgs a{};
-  a.x = (const float*)x;
-  a.xbs = x_bstride;
-  a.cin1 = cin;
-  a.wp = w_packed;
-  a.scale = scale;
-  a.shift = shift;
-  a.res = (const float*)residual;
-  a.rbs = r_bstride;
-  a.y = (float*)y;
-  a.ybs = y_bstride;
+  ConvArgs a = conv_args(x, x_bstride, nullptr, 0, 0, w_packed, scale, shift, residual, r_bstride, y, y_bstride, cin,
+                         cout, 1, H, W, flags);
   a.y2 = (float*)y2;
   a.y2bs = y2_bstride;
   a.csplit = c1;
-  a.cin = cin;
-  a.cout = cout;
-  a.D = 1;
-  a.H = H;
-  a.W = W;
-  a.flags = flags;
   LEA_CHECK_ARG(a.x && a.wp && a.y && a.y2, "lea_conv2d_bnrelu_pair: null pointer");
   LEA_CHECK_ARG((a.scale == nullptr) == (a.shift == nullptr),
                 "lea_conv2d_bnrelu_pair: scale/shift must both be set or both NULL");
@@ -203,11 +186,5 @@ extern "C" int lea_conv2d_bnrelu_pair(const void* x, int64_t x_bstride, const fl
     set_error("lea_conv2d_bnrelu_pair: cin=%d cout=%d beyond the few-channel tile", cin, cout);
     return LEA_E_UNSUPPORTED;
   }
-  return run_conv2d_small(a, B, as_stream(stream));
-}
-
-extern "C" const char* lea_conv2d_kernel_name_cin(int B, int cin, int cout, int H, int W) {
-  if (B <= 0 || cin <= 0 || cout <= 0 || H <= 0 || W <= 0) return nullptr;
-  if (lea::conv2d_small_ok(cin, cout)) return lea::conv2d_small_name(cin, cout);
-  return lea_conv2d_kernel_name(B, cout, H, W);
+  return run_conv2d_small(conv2d_small_plan(cin, cout), a, B, as_stream(stream), nullptr);
 }

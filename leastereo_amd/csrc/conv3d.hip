@@ -578,16 +578,6 @@ size_t packed_floats(int cout, int cin, int k) {
 
 // ------------------------------------------------------------------------- dispatch
 
-// LDS bytes of a double-buffered DMA-engine workgroup (0 if not instantiated).
-inline int dma_lds_bytes(int mt, int nt, int tw, int td) {
-  switch (mt) {
-    case 1: return dma_lds_bytes_mt1(nt, tw, td);
-    case 2: return dma_lds_bytes_mt2(nt, tw, td);
-    case 3: return dma_lds_bytes_mt3(nt, tw, td);
-    default: return dma_lds_bytes_mt4(nt, tw, td);
-  }
-}
-
 int g_tile_override[3] = {0, 0, 0};
 
 inline bool prefer_tw64(int W) {
@@ -598,32 +588,60 @@ inline bool prefer_tw64(int W) {
 // lea_conv3d_set_rs_gather: 1 (default) = the resampled 1x1 convs on the gather-GEMM
 // (conv1x1_rs_f32_kernel), 0 = the register-staged engine
 LEA_TUNING_INT(lea_conv3d_set_rs_gather, g_rs_gather, 1, 0, 1, "on=%d")
+// the NT-float vector form of conv1x1_kernel
+LEA_TUNING_INT(lea_conv1x1_set_vector, g_1x1_vec, 1, 0, 1, "on=%d")
 
-inline Plan make_plan(int B, int cout, int D, int H, int W, int k, bool resample) {
-  Plan p;
+// What is launched: lea_conv3d_bnrelu, _resampled, _costvolume, lea_conv1x1_heads,
+// lea_conv2d_bnrelu, or a 2D conv on the DMA tile whatever its cin (the windowed launch's groups
+// and lea_conv2d_kernel_name)
+enum class Kind { Conv, Resampled, CostVolume, Heads, Conv2D, Dma2D };
+
+// The plan of one launch (cin2 of the cin input channels come from the second source).
+// a == NULL (the host queries): the shape alone, aligned operands and an input within the
+// gather-GEMM's buffer range assumed.
+Plan route(Kind kind, int B, int cin, int cin2, int cout, int D, int H, int W, int k, const ConvArgs* a) {
+  Plan p{};
   p.td = 1;
+  p.ks = k;
+  p.kd = 3;
   p.mt = mt_for(cout);
+  const bool resample = kind == Kind::Resampled;
+  const long long ncob = (cout + p.mt * 16 - 1) / (p.mt * 16);
+  if (kind == Kind::Conv2D || kind == Kind::Dma2D) {
+    // the feature net's Conv2d 3x3 / stride 1 / pad 1 (models/operations_2d.py:31-47): the
+    // few-channel tile, else the DMA engine as the D = 1 case of a (1, 3, 3) kernel
+    if (kind == Kind::Conv2D && conv2d_small_ok(cin, cout)) return conv2d_small_plan(cin, cout);
+    p.kd = 1;
+    p.tw = 16;
+    const long long wgs8 = (long long)((W + 15) / 16) * ((H + 7) / 8) * B * ncob;
+    p.nt = wgs8 >= 512 ? 2 : 1;  // 8 x 16 tiles, or 4 x 16 on small maps
+    return p;
+  }
   // same-box sweep (r02): the gather-GEMM wins on the L1 -> L2 preprocess (64 channels,
   // 61 K output voxels: 35 -> 29.5 us) and loses on the L0 -> L1 ones (32 channels, 491 K:
-  // 122 -> 136 us: twice the load instructions of the staged engine's row gathers)
-  if (k == 1 && resample && g_rs_gather && (long long)B * D * H * W <= 131072) {
+  // 122 -> 136 us: twice the load instructions of the staged engine's row gathers).  Wider
+  // inputs than its LDS weight block holds, a second source or an input beyond the buffer
+  // range stay on the register-staged engine.
+  if (k == 1 && resample && g_rs_gather && (long long)B * D * H * W <= 131072 && cin <= kRsMaxCin && cin2 == 0 &&
+      (!a || (long long)cin * a->Di * a->Hi * a->Wi * 4 < 0xFFFFFF00LL)) {
     p.engine = 5;
-    p.nt = 0;
-    p.tw = 0;
     return p;
   }
   if (k == 1 && !resample) {
     p.engine = 1;
+    p.heads = kind == Kind::Heads;
     p.nt = 4;
-    p.tw = 0;
     const long long vox = (long long)D * H * W;
     if ((vox + kConvWaves * 64 - 1) / (kConvWaves * 64) * B < 512) p.nt = 2;
+    // the vector form needs every per-channel and per-batch base on an NT-float boundary
+    auto al = [&](const void* q, long long bs) { return (uintptr_t)q % (p.nt * 4) == 0 && bs % p.nt == 0; };
+    p.vec = g_1x1_vec && vox % p.nt == 0 &&
+            (!a || (al(a->x, a->xbs) && al(a->x2, a->x2bs) && al(a->y, a->ybs) && al(a->res, a->rbs) && al(a->y2, a->y2bs)));
     return p;
   }
   if (k == 3 && cout <= 2 && !resample) {
     p.engine = 3;
-    p.mt = cout;  // conv3d_valu_kernel<cout> (plan_name; one cout block either way)
-    p.nt = 0;
+    p.mt = cout;  // conv3d_valu_kernel<cout>
     p.tw = 64;
     return p;
   }
@@ -631,14 +649,12 @@ inline Plan make_plan(int B, int cout, int D, int H, int W, int k, bool resample
     p.engine = 4;
     p.mt = 1;
     p.tw = 16;
-    p.td = 1;
     const long long wgs8 = (long long)((W + 15) / 16) * ((H + 7) / 8) * ((D + 1) / 2) * B;
     p.nt = wgs8 >= 512 ? 2 : 1;
     return p;
   }
   p.engine = resample ? 2 : 0;
   p.tw = prefer_tw64(W) ? 64 : 32;
-  p.td = 1;
   if (resample) {
     // register-staged resampling engine; for k = 1 (the level-change preprocess,
     // latency-bound gathers) quarter-height tiles shrink the LDS stage so 8
@@ -646,7 +662,7 @@ inline Plan make_plan(int B, int cout, int D, int H, int W, int k, bool resample
     p.nt = (k == 1) ? (p.mt == 1 ? 2 : 1) : (p.mt == 1 ? 8 : 4);
     return p;
   }
-  const long long ncob = (cout + p.mt * 16 - 1) / (p.mt * 16);
+  p.cv = kind == Kind::CostVolume;
   if (g_tile_override[0] > 0) {  // lea_conv3d_set_tile_override (tuning tools)
     p.nt = g_tile_override[0];
     p.tw = g_tile_override[1];
@@ -669,131 +685,68 @@ inline Plan make_plan(int B, int cout, int D, int H, int W, int k, bool resample
   return p;
 }
 
-template <typename K>
-int launch(K kernel, const ConvArgs& a0, int th, int tw, int B, hipStream_t st, int td = 1) {
-  ConvArgs a = a0;
-  const long long nt = (long long)((a.W + tw - 1) / tw) * ((a.H + th - 1) / th);
-  LEA_CHECK_ARG(nt < (1LL << 31) && a.D <= 65535 && (long long)B * a.ncob <= 65535,
-                "lea_conv3d: grid too large");
-  a.tiles_w = (a.W + tw - 1) / tw;
-  dim3 grid((unsigned)nt, (a.D + td - 1) / td, B * a.ncob);
-  kernel<<<grid, kConvThreads, 0, st>>>(a);
-  return launch_status("lea_conv3d");
-}
-
-#define LEA_TILE_TH(KS, MT, NT, TW) (TileCfg<KS, MT, NT, TW>::TH)
-
-template <int KS, int MT, int NT>
-int run_rs(const ConvArgs& a, int tw, int B, hipStream_t st) {
-  if (tw == 64) return launch(conv3d_reg_kernel<KS, MT, NT, 64, true>, a, LEA_TILE_TH(KS, MT, NT, 64), 64, B, st);
-  return launch(conv3d_reg_kernel<KS, MT, NT, 32, true>, a, LEA_TILE_TH(KS, MT, NT, 32), 32, B, st);
-}
-
-// the NT-float vector form of conv1x1_kernel
-LEA_TUNING_INT(lea_conv1x1_set_vector, g_1x1_vec, 1, 0, 1, "on=%d")
-
-// hb: the second head of lea_conv1x1_heads (null: the single-output kernel)
-template <int MT, int NT>
-int launch_1x1(const ConvArgs& a, int B, hipStream_t st, const Conv1x1HeadB* hb = nullptr) {
-  const long long vox = (long long)a.D * a.H * a.W;
-  const long long per = kConvWaves * NT * 16;
-  const long long gx = (vox + per - 1) / per;
-  LEA_CHECK_ARG(gx < (1LL << 31) && (long long)B * a.ncob <= 65535, "lea_conv3d: grid too large");
-  // the vector form needs every per-channel and per-batch base on an NT-float boundary
-  auto al = [](const void* q) { return q == nullptr || ((uintptr_t)q % (NT * 4)) == 0; };
-  const bool vec = g_1x1_vec && vox % NT == 0 && al(a.x) && al(a.x2) && al(a.y) && al(a.res) &&
-                   a.xbs % NT == 0 && a.x2bs % NT == 0 && a.ybs % NT == 0 && a.rbs % NT == 0 &&
-                   (hb == nullptr || (al(hb->y) && hb->ybs % NT == 0));
-  const dim3 grid((unsigned)gx, B * a.ncob);
-  if (hb != nullptr) {
-    if (vec) conv1x1_heads_kernel<MT, NT, true><<<grid, kConvThreads, 0, st>>>(a, *hb);
-    else conv1x1_heads_kernel<MT, NT, false><<<grid, kConvThreads, 0, st>>>(a, *hb);
-    return launch_status("lea_conv1x1_heads");
+// One instantiation of an engine of this file: launched if the plan names it
+#define LEA_GRID(...)                                               \
+  if (const int rc = name ? LEA_OK : grid(a, B, __VA_ARGS__)) return rc
+#define LEA_REG_CASE(KS, MT, NT, TW)                                                    \
+  if (p.ks == KS && p.mt == MT && p.nt == NT && p.tw == TW) {                           \
+    LEA_GRID(MT * 16, TW, TileCfg<KS, MT, NT, TW>::TH, 1, 0, &g);                       \
+    LEA_LAUNCH("lea_conv3d", g, kConvThreads, 0, (a), conv3d_reg_kernel<KS, MT, NT, TW, true>); \
   }
-  if (vec) conv1x1_kernel<MT, NT, true><<<grid, kConvThreads, 0, st>>>(a);
-  else conv1x1_kernel<MT, NT, false><<<grid, kConvThreads, 0, st>>>(a);
-  return launch_status("lea_conv3d");
+#define LEA_REG_TW(KS, MT, NT) LEA_REG_CASE(KS, MT, NT, 32) LEA_REG_CASE(KS, MT, NT, 64)
+// (both VEC forms answer one name)
+#define LEA_1X1_CASE(MT, NT)                                                                      \
+  if (p.mt == MT && p.nt == NT) {                                                                 \
+    LEA_GRID(MT * 16, 0, 0, 1, NT * 16, &g);                                                      \
+    if (p.heads && p.vec)                                                                         \
+      LEA_LAUNCH_AS("conv1x1_heads_kernel<" #MT ", " #NT ">", "lea_conv1x1_heads", g, kConvThreads, 0, (a, *hb), \
+                    conv1x1_heads_kernel<MT, NT, true>);                                          \
+    if (p.heads)                                                                                  \
+      LEA_LAUNCH_AS("conv1x1_heads_kernel<" #MT ", " #NT ">", "lea_conv1x1_heads", g, kConvThreads, 0, (a, *hb), \
+                    conv1x1_heads_kernel<MT, NT, false>);                                         \
+    if (p.vec)                                                                                    \
+      LEA_LAUNCH_AS("conv1x1_kernel<" #MT ", " #NT ">", "lea_conv3d", g, kConvThreads, 0, (a), conv1x1_kernel<MT, NT, true>); \
+    LEA_LAUNCH_AS("conv1x1_kernel<" #MT ", " #NT ">", "lea_conv3d", g, kConvThreads, 0, (a), conv1x1_kernel<MT, NT, false>); \
+  }
+#define LEA_RS_GATHER_CASE(MT)                                                                   \
+  if (p.mt == MT) {                                                                              \
+    LEA_GRID(MT * 16, 0, 0, 1, 16, &g, &tpw);                                                    \
+    LEA_LAUNCH("lea_conv3d(rs gather)", g, 256, 0, (a, tpw), conv1x1_rs_f32_kernel<MT>);         \
+  }
+
+// Launch plan p or (name != NULL) answer its kernel's name; LEA_E_UNSUPPORTED for a plan without
+// an instantiation (a tile override can ask for one).  hb: the second head of lea_conv1x1_heads.
+int run(const Plan& p, ConvArgs a, int B, hipStream_t st, const char** name, const Conv1x1HeadB* hb = nullptr) {
+  dim3 g;
+  int tpw = 0;
+  switch (p.engine) {
+    case 0: return run_dma(p, a, B, st, name);
+    case 1:  // 1x1x1 without resample: streaming engine over the flat voxel run
+      LEA_1X1_CASE(1, 4) LEA_1X1_CASE(1, 2) LEA_1X1_CASE(2, 4) LEA_1X1_CASE(2, 2)
+      LEA_1X1_CASE(3, 4) LEA_1X1_CASE(3, 2) LEA_1X1_CASE(4, 4) LEA_1X1_CASE(4, 2)
+      break;
+    case 2:
+      LEA_REG_TW(3, 1, 8) LEA_REG_TW(3, 2, 4) LEA_REG_TW(3, 3, 4) LEA_REG_TW(3, 4, 4)
+      LEA_REG_TW(1, 1, 2) LEA_REG_TW(1, 2, 1) LEA_REG_TW(1, 3, 1) LEA_REG_TW(1, 4, 1)
+      break;
+    case 3:
+      LEA_GRID(16, 64, 8, 1, 0, &g);
+      if (p.mt == 1) LEA_LAUNCH("lea_conv3d", g, kConvThreads, 0, (a), conv3d_valu_kernel<1>);
+      LEA_LAUNCH("lea_conv3d", g, kConvThreads, 0, (a), conv3d_valu_kernel<2>);
+    case 4: return run_dma_dp(p, a, B, st, name);
+    case 5:
+      LEA_RS_GATHER_CASE(1) LEA_RS_GATHER_CASE(2) LEA_RS_GATHER_CASE(3) LEA_RS_GATHER_CASE(4)
+      break;
+    case 6: return run_conv2d_small(p, a, B, st, name);
+  }
+  set_error("lea_conv3d: no kernel for engine %d <%d, %d, %d>", p.engine, p.mt, p.nt, p.tw);
+  return LEA_E_UNSUPPORTED;
 }
 
-int run_1x1(const Plan& p, const ConvArgs& a, int B, hipStream_t st, const Conv1x1HeadB* hb = nullptr) {
-  if (p.mt == 1) return p.nt == 4 ? launch_1x1<1, 4>(a, B, st, hb) : launch_1x1<1, 2>(a, B, st, hb);
-  if (p.mt == 2) return p.nt == 4 ? launch_1x1<2, 4>(a, B, st, hb) : launch_1x1<2, 2>(a, B, st, hb);
-  if (p.mt == 3) return p.nt == 4 ? launch_1x1<3, 4>(a, B, st, hb) : launch_1x1<3, 2>(a, B, st, hb);
-  return p.nt == 4 ? launch_1x1<4, 4>(a, B, st, hb) : launch_1x1<4, 2>(a, B, st, hb);
-}
-
-template <int MT>
-int launch_rs_gather(ConvArgs a, int B, hipStream_t st) {
-  const long long vout = (long long)a.D * a.H * a.W;
-  const long long tiles = (vout + 15) / 16;
-  // about 8192 waves over the batch and cout blocks, each walking tpw tiles
-  const long long tpw = std::max(1LL, (tiles * B * a.ncob + 8191) / 8192);
-  const long long gx = (tiles + 4 * tpw - 1) / (4 * tpw);
-  LEA_CHECK_ARG(gx < (1LL << 31) && (long long)B * a.ncob <= 65535, "lea_conv3d: grid too large");
-  conv1x1_rs_f32_kernel<MT><<<dim3((unsigned)gx, B * a.ncob), 256, 0, st>>>(a, (int)tpw);
-  return launch_status("lea_conv3d(rs gather)");
-}
-
-int run_plan(const Plan& p, ConvArgs a, int B, int k, hipStream_t st) {
-  a.ncob = (a.cout + p.mt * 16 - 1) / (p.mt * 16);
-  if (p.engine == 5) {
-    const long long xbytes = (long long)a.cin * a.Di * a.Hi * a.Wi * 4;
-    if (a.cin <= kRsMaxCin && a.cin1 == a.cin && xbytes < 0xFFFFFF00LL) {
-      if (p.mt == 1) return launch_rs_gather<1>(a, B, st);
-      if (p.mt == 2) return launch_rs_gather<2>(a, B, st);
-      if (p.mt == 3) return launch_rs_gather<3>(a, B, st);
-      return launch_rs_gather<4>(a, B, st);
-    }
-    // wider inputs than the LDS weight block holds: the register-staged engine
-    if (p.mt == 1) return run_rs<1, 1, 2>(a, prefer_tw64(a.W) ? 64 : 32, B, st);
-    if (p.mt == 2) return run_rs<1, 2, 1>(a, prefer_tw64(a.W) ? 64 : 32, B, st);
-    if (p.mt == 3) return run_rs<1, 3, 1>(a, prefer_tw64(a.W) ? 64 : 32, B, st);
-    return run_rs<1, 4, 1>(a, prefer_tw64(a.W) ? 64 : 32, B, st);
-  }
-  if (p.engine == 3) {
-    if (a.cout == 1) return launch(conv3d_valu_kernel<1>, a, 8, 64, B, st);
-    return launch(conv3d_valu_kernel<2>, a, 8, 64, B, st);
-  }
-  if (p.engine == 4) return run_dma_dp(p, a, B, st);
-  if (p.engine == 0) {
-    if (p.mt == 1) return run_dma_mt1(p, a, B, st);
-    if (p.mt == 2) return run_dma_mt2(p, a, B, st);
-    if (p.mt == 3) return run_dma_mt3(p, a, B, st);
-    return run_dma_mt4(p, a, B, st);
-  }
-  if (p.engine == 2) {
-    if (k == 3) {
-      if (p.mt == 1) return run_rs<3, 1, 8>(a, p.tw, B, st);
-      if (p.mt == 2) return run_rs<3, 2, 4>(a, p.tw, B, st);
-      if (p.mt == 3) return run_rs<3, 3, 4>(a, p.tw, B, st);
-      return run_rs<3, 4, 4>(a, p.tw, B, st);
-    }
-    if (p.mt == 1) return run_rs<1, 1, 2>(a, p.tw, B, st);
-    if (p.mt == 2) return run_rs<1, 2, 1>(a, p.tw, B, st);
-    if (p.mt == 3) return run_rs<1, 3, 1>(a, p.tw, B, st);
-    return run_rs<1, 4, 1>(a, p.tw, B, st);
-  }
-  // 1x1x1 without resample: streaming engine over the flat voxel run
-  return run_1x1(p, a, B, st);
-}
-
-thread_local char g_name[96];
-
-const char* plan_name(const Plan& p, int k) {
-  if (p.engine == 5)
-    snprintf(g_name, sizeof(g_name), "conv1x1_rs_f32_kernel<%d>", p.mt);
-  else if (p.engine == 3)
-    snprintf(g_name, sizeof(g_name), "conv3d_valu_kernel<%d>", p.mt == 1 ? 1 : 2);
-  else if (p.engine == 0)
-    snprintf(g_name, sizeof(g_name), "conv3d_dma_kernel<%d, %d, %d, %d, %d, false>", p.mt, p.nt,
-             p.tw, p.td, k == 2 ? 1 : 3);
-  else if (p.engine == 4)
-    snprintf(g_name, sizeof(g_name), "conv3d_dma_kernel<1, %d, %d, 1, 4, false>", p.nt, p.tw);
-  else if (p.engine == 2)
-    snprintf(g_name, sizeof(g_name), "conv3d_reg_kernel<%d, %d, %d, %d, true>", k, p.mt, p.nt, p.tw);
-  else
-    snprintf(g_name, sizeof(g_name), "conv1x1_kernel<%d, %d>", p.mt, p.nt);
-  return g_name;
+// the kernel a plan runs, or NULL (lea_last_error says why) for a plan without an instantiation
+const char* plan_name(const Plan& p) {
+  const char* name = nullptr;
+  return run(p, ConvArgs{}, 1, nullptr, &name) == LEA_OK ? name : nullptr;
 }
 
 // ------------------------------------------------------------ 2D 3x3 (feature net)
@@ -804,18 +757,6 @@ size_t packed_floats_2d(int cout, int cin) {
   return mt == 1 ? packed_floats_t<3, 1, 1>(cout, cin)
          : mt == 2 ? packed_floats_t<3, 2, 1>(cout, cin)
          : mt == 3 ? packed_floats_t<3, 3, 1>(cout, cin) : packed_floats_t<3, 4, 1>(cout, cin);
-}
-
-inline Plan make_plan_2d(int B, int cout, int H, int W) {
-  Plan p;
-  p.engine = 0;
-  p.mt = mt_for(cout);
-  p.tw = 16;
-  p.td = 1;
-  const long long ncob = (cout + p.mt * 16 - 1) / (p.mt * 16);
-  const long long wgs8 = (long long)((W + 15) / 16) * ((H + 7) / 8) * B * ncob;
-  p.nt = wgs8 >= 512 ? 2 : 1;  // 8 x 16 tiles, or 4 x 16 on small maps
-  return p;
 }
 
 int conv_common(ConvArgs& a, int B, int k, bool resample, int dtype, void* stream) {
@@ -847,16 +788,24 @@ int conv_common(ConvArgs& a, int B, int k, bool resample, int dtype, void* strea
     set_error("lea_conv3d: dtype %d unsupported", dtype);
     return LEA_E_UNSUPPORTED;
   }
-  const Plan p = make_plan(B, a.cout, a.D, a.H, a.W, k, resample);
-  return run_plan(p, a, B, k, as_stream(stream));
+  const Plan p = route(resample ? Kind::Resampled : Kind::Conv, B, a.cin, a.cin - a.cin1, a.cout, a.D, a.H, a.W, k, &a);
+  return run(p, a, B, as_stream(stream), nullptr);
 }
 
 }  // namespace lea
 
+extern "C" const char* lea_conv3d_launch_kernel_name(int B, int cin, int cin2, int cout, int D, int H, int W, int k,
+                                                     int resampled) {
+  lea::clear_error();
+  if (B <= 0 || cin <= 0 || cin2 < 0 || cin2 >= cin || cout <= 0 || (k != 1 && k != 3) || D <= 0 || H <= 0 || W <= 0)
+    return nullptr;
+  return lea::plan_name(lea::route(resampled ? lea::Kind::Resampled : lea::Kind::Conv, B, cin, cin2, cout, D, H, W, k, nullptr));
+}
+
+// (without the input channels: a single source within the gather-GEMM's limit)
 extern "C" const char* lea_conv3d_kernel_name(int B, int cout, int D, int H, int W, int k,
                                               int resample) {
-  if (B <= 0 || cout <= 0 || (k != 1 && k != 3) || D <= 0 || H <= 0 || W <= 0) return nullptr;
-  return lea::plan_name(lea::make_plan(B, cout, D, H, W, k, resample != 0), k);
+  return lea_conv3d_launch_kernel_name(B, lea::kRsMaxCin, 0, cout, D, H, W, k, resample);
 }
 
 extern "C" int lea_conv3d_set_tile_override(int nt, int tw, int td) {
@@ -914,33 +863,15 @@ extern "C" int lea_conv3d_bnrelu(const void* x, int64_t x_bstride, const void* x
                                  int64_t r_bstride, void* y, int64_t y_bstride, int B, int cin,
                                  int cout, int D, int H, int W, int k, unsigned flags, int dtype,
                                  void* stream) {
-  lea::ConvArgs a{};
-  a.x = (const float*)x;
-  a.xbs = x_bstride;
-  a.x2 = (const float*)x2;
-  a.x2bs = x2_bstride;
-  a.cin1 = cin - cin2;
-  a.wp = w_packed;
-  a.scale = scale;
-  a.shift = shift;
-  a.res = (const float*)residual;
-  a.rbs = r_bstride;
-  a.y = (float*)y;
-  a.ybs = y_bstride;
-  a.cin = cin;
-  a.cout = cout;
-  a.D = D;
-  a.H = H;
-  a.W = W;
-  a.flags = flags;
+  lea::ConvArgs a = lea::conv_args(x, x_bstride, x2, x2_bstride, cin2, w_packed, scale, shift, residual, r_bstride, y,
+                                   y_bstride, cin, cout, D, H, W, flags);
   return lea::conv_common(a, B, k, false, dtype, stream);
 }
 
 extern "C" const char* lea_conv1x1_heads_kernel_name(int B, int cout, int D, int H, int W) {
+  lea::clear_error();
   if (B <= 0 || cout <= 0 || D <= 0 || H <= 0 || W <= 0) return nullptr;
-  const lea::Plan p = lea::make_plan(B, cout, D, H, W, 1, false);
-  snprintf(lea::g_name, sizeof(lea::g_name), "conv1x1_heads_kernel<%d, %d>", p.mt, p.nt);
-  return lea::g_name;
+  return lea::plan_name(lea::route(lea::Kind::Heads, B, 1, 0, cout, D, H, W, 1, nullptr));
 }
 
 extern "C" int lea_conv1x1_heads(const void* x, int64_t x_bstride, const void* x2, int64_t x2_bstride,
@@ -973,27 +904,12 @@ extern "C" int lea_conv1x1_heads(const void* x, int64_t x_bstride, const void* x
     set_error("lea_conv1x1_heads: dtype %d unsupported", dtype);
     return LEA_E_UNSUPPORTED;
   }
-  ConvArgs a{};
-  a.x = (const float*)x;
-  a.xbs = x_bstride;
-  a.x2 = (const float*)x2;
-  a.x2bs = x2_bstride;
-  a.cin1 = cin - cin2;
-  a.wp = w_packed;
-  a.scale = scale_a;
-  a.shift = shift_a;
-  a.y = (float*)y_a;
-  a.ybs = ya_bstride;
-  a.cin = cin;
-  a.cout = cout_a + cout_b;
-  a.D = D;
-  a.H = H;
-  a.W = W;
-  a.flags = flags_a;
-  const Conv1x1HeadB hb{(float*)y_b, yb_bstride, scale_b, shift_b, cout_a, flags_b};
-  const Plan p = make_plan(B, a.cout, D, H, W, 1, false);
-  a.ncob = (a.cout + p.mt * 16 - 1) / (p.mt * 16);
-  return run_1x1(p, a, B, as_stream(stream), &hb);
+  ConvArgs a = conv_args(x, x_bstride, x2, x2_bstride, cin2, w_packed, scale_a, shift_a, nullptr, 0, y_a, ya_bstride,
+                         cin, cout_a + cout_b, D, H, W, flags_a);
+  a.y2 = (float*)y_b;  // (the kernel reads head B from hb; route() its alignment from here)
+  a.y2bs = yb_bstride;
+  const Conv1x1HeadB hb{a.y2, a.y2bs, scale_b, shift_b, cout_a, flags_b};
+  return run(route(Kind::Heads, B, cin, cin2, a.cout, D, H, W, 1, &a), a, B, as_stream(stream), nullptr, &hb);
 }
 
 extern "C" size_t lea_conv2d_packed_floats(int cout, int cin) {
@@ -1022,9 +938,17 @@ extern "C" int lea_conv2d_pack_weights(const float* w, float* packed, int cout, 
   return launch_status("lea_conv2d_pack_weights");
 }
 
+extern "C" const char* lea_conv2d_kernel_name_cin(int B, int cin, int cout, int H, int W) {
+  lea::clear_error();
+  if (B <= 0 || cin <= 0 || cout <= 0 || H <= 0 || W <= 0) return nullptr;
+  return lea::plan_name(lea::route(lea::Kind::Conv2D, B, cin, 0, cout, 1, H, W, 3, nullptr));
+}
+
+// (without the input channels: the DMA tile)
 extern "C" const char* lea_conv2d_kernel_name(int B, int cout, int H, int W) {
+  lea::clear_error();
   if (B <= 0 || cout <= 0 || H <= 0 || W <= 0) return nullptr;
-  return lea::plan_name(lea::make_plan_2d(B, cout, H, W), 2);
+  return lea::plan_name(lea::route(lea::Kind::Dma2D, B, 1, 0, cout, 1, H, W, 3, nullptr));
 }
 
 extern "C" int lea_conv2d_bnrelu(const void* x, int64_t x_bstride, const float* w_packed,
@@ -1033,23 +957,8 @@ extern "C" int lea_conv2d_bnrelu(const void* x, int64_t x_bstride, const float* 
                                  int cout, int H, int W, unsigned flags, int dtype, void* stream) {
   using namespace lea;
   clear_error();
-  ConvArgs a{};
-  a.x = (const float*)x;
-  a.xbs = x_bstride;
-  a.cin1 = cin;
-  a.wp = w_packed;
-  a.scale = scale;
-  a.shift = shift;
-  a.res = (const float*)residual;
-  a.rbs = r_bstride;
-  a.y = (float*)y;
-  a.ybs = y_bstride;
-  a.cin = cin;
-  a.cout = cout;
-  a.D = 1;
-  a.H = H;
-  a.W = W;
-  a.flags = flags;
+  const ConvArgs a = conv_args(x, x_bstride, nullptr, 0, 0, w_packed, scale, shift, residual, r_bstride, y, y_bstride,
+                               cin, cout, 1, H, W, flags);
   LEA_CHECK_ARG(a.x && a.wp && a.y, "lea_conv2d: null pointer");
   LEA_CHECK_ARG((a.scale == nullptr) == (a.shift == nullptr),
                 "lea_conv2d: scale/shift must both be set or both NULL");
@@ -1063,33 +972,17 @@ extern "C" int lea_conv2d_bnrelu(const void* x, int64_t x_bstride, const float* 
     set_error("lea_conv2d: dtype %d unsupported", dtype);
     return LEA_E_UNSUPPORTED;
   }
-  hipStream_t st = as_stream(stream);
-  if (conv2d_small_ok(cin, cout)) return run_conv2d_small(a, B, st);
-  const Plan p = make_plan_2d(B, cout, H, W);
-  a.ncob = (cout + p.mt * 16 - 1) / (p.mt * 16);
-  switch (p.mt) {
-    case 1: return run_dma2d_mt1(p, a, B, st);
-    case 2: return run_dma2d_mt2(p, a, B, st);
-    case 3: return run_dma2d_mt3(p, a, B, st);
-    default: return run_dma2d_mt4(p, a, B, st);
-  }
+  return run(route(Kind::Conv2D, B, cin, 0, cout, 1, H, W, 3, &a), a, B, as_stream(stream), nullptr);
 }
 
 namespace lea {
 
 // one channel group of lea_conv2d_bnrelu_windowed on the direct engine's 2D tiles
-int run_dma2d(ConvArgs a, int B, hipStream_t st) {
-  const Plan p = make_plan_2d(B, a.cout, a.H, a.W);
-  a.ncob = (a.cout + p.mt * 16 - 1) / (p.mt * 16);
-  switch (p.mt) {
-    case 1: return run_dma2d_mt1(p, a, B, st);
-    case 2: return run_dma2d_mt2(p, a, B, st);
-    case 3: return run_dma2d_mt3(p, a, B, st);
-    default: return run_dma2d_mt4(p, a, B, st);
-  }
+int run_dma2d(const ConvArgs& a, int B, hipStream_t st) {
+  return run(route(Kind::Dma2D, B, a.cin, 0, a.cout, 1, a.H, a.W, 3, &a), a, B, st, nullptr);
 }
 
-constexpr int kWinTile = 16;  // the 2D tiles' width (make_plan_2d): windows round outward to it
+constexpr int kWinTile = 16;  // the 2D tiles' width (route()): windows round outward to it
 
 }  // namespace lea
 
@@ -1136,16 +1029,8 @@ extern "C" int lea_conv2d_bnrelu_windowed(const void* x, int64_t x_bstride, cons
     set_error("lea_conv2d_bnrelu_windowed: dtype %d unsupported", dtype);
     return LEA_E_UNSUPPORTED;
   }
-  ConvArgs a{};
-  a.x = (const float*)x;
-  a.xbs = x_bstride;
-  a.cin1 = cin;
-  a.cin = cin;
-  a.ybs = y_bstride;
-  a.D = 1;
-  a.H = H;
-  a.W = W;
-  a.flags = flags;
+  ConvArgs a = conv_args(x, x_bstride, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, y_bstride, cin,
+                         cout, 1, H, W, flags);
   hipStream_t st = as_stream(stream);
   if (split > 0) {  // channels [0, split): every column
     a.wp = w_packed;
@@ -1170,12 +1055,10 @@ extern "C" int lea_conv2d_bnrelu_windowed(const void* x, int64_t x_bstride, cons
 }
 
 extern "C" const char* lea_conv3d_costvolume_kernel_name(int B, int cout, int D3, int H, int W) {
+  lea::clear_error();
   if (B <= 0 || cout <= 0 || D3 <= 0 || H <= 0 || W <= 0) return nullptr;
-  const lea::Plan p = lea::make_plan(B, cout, D3, H, W, 3, false);
-  if (p.engine != 0) return nullptr;
-  snprintf(lea::g_name, sizeof(lea::g_name), "conv3d_dma_kernel<%d, %d, %d, %d, 3, true>", p.mt, p.nt,
-           p.tw, p.td);
-  return lea::g_name;
+  const lea::Plan p = lea::route(lea::Kind::CostVolume, B, 1, 0, cout, D3, H, W, 3, nullptr);
+  return p.engine == 0 ? lea::plan_name(p) : nullptr;
 }
 
 extern "C" int lea_conv3d_bnrelu_costvolume(const void* left, const void* right, int64_t f_bstride,
@@ -1185,23 +1068,8 @@ extern "C" int lea_conv3d_bnrelu_costvolume(const void* left, const void* right,
                                             int dtype, void* stream) {
   using namespace lea;
   clear_error();
-  ConvArgs a{};
-  a.x = (const float*)left;
-  a.xbs = f_bstride;
-  a.x2 = (const float*)right;
-  a.x2bs = f_bstride;
-  a.cin1 = C;
-  a.wp = w_packed;
-  a.scale = scale;
-  a.shift = shift;
-  a.y = (float*)y;
-  a.ybs = y_bstride;
-  a.cin = 2 * C;
-  a.cout = cout;
-  a.D = D3;
-  a.H = H;
-  a.W = W;
-  a.flags = flags & LEA_RELU;
+  const ConvArgs a = conv_args(left, f_bstride, right, f_bstride, C, w_packed, scale, shift, nullptr, 0, y, y_bstride,
+                               2 * C, cout, D3, H, W, flags & LEA_RELU);
   LEA_CHECK_FLAGS(flags, LEA_RELU, "lea_conv3d_bnrelu_costvolume");
   LEA_CHECK_ARG(left && right && w_packed && y && y != left && y != right,
                 "lea_conv3d_bnrelu_costvolume: null or aliased pointer");
@@ -1219,16 +1087,9 @@ extern "C" int lea_conv3d_bnrelu_costvolume(const void* left, const void* right,
     set_error("lea_conv3d_bnrelu_costvolume: dtype %d unsupported", dtype);
     return LEA_E_UNSUPPORTED;
   }
-  const Plan p = make_plan(B, cout, D3, H, W, 3, false);
+  const Plan p = route(Kind::CostVolume, B, 2 * C, C, cout, D3, H, W, 3, &a);
   LEA_CHECK_ARG(p.engine == 0, "lea_conv3d_bnrelu_costvolume: no DMA plan for cout=%d", cout);
-  a.ncob = (cout + p.mt * 16 - 1) / (p.mt * 16);
-  hipStream_t st = as_stream(stream);
-  switch (p.mt) {
-    case 1: return run_dma_cv_mt1(p, a, B, st);
-    case 2: return run_dma_cv_mt2(p, a, B, st);
-    case 3: return run_dma_cv_mt3(p, a, B, st);
-    default: return run_dma_cv_mt4(p, a, B, st);
-  }
+  return run(p, a, B, as_stream(stream), nullptr);
 }
 
 extern "C" int lea_conv3d_bnrelu_resampled(const void* x, int64_t x_bstride, int Di, int Hi,
@@ -1237,28 +1098,13 @@ extern "C" int lea_conv3d_bnrelu_resampled(const void* x, int64_t x_bstride, int
                                            int64_t r_bstride, void* y, int64_t y_bstride, int B,
                                            int cin, int cout, int D, int H, int W, int k,
                                            unsigned flags, int dtype, void* stream) {
-  lea::ConvArgs a{};
-  a.x = (const float*)x;
-  a.xbs = x_bstride;
-  a.cin1 = cin;
-  a.wp = w_packed;
-  a.scale = scale;
-  a.shift = shift;
-  a.res = (const float*)residual;
-  a.rbs = r_bstride;
-  a.y = (float*)y;
-  a.ybs = y_bstride;
-  a.cin = cin;
-  a.cout = cout;
-  a.D = D;
-  a.H = H;
-  a.W = W;
+  lea::ConvArgs a = lea::conv_args(x, x_bstride, nullptr, 0, 0, w_packed, scale, shift, residual, r_bstride, y,
+                                   y_bstride, cin, cout, D, H, W, flags);
   a.Di = Di;
   a.Hi = Hi;
   a.Wi = Wi;
   a.rd = lea::axis_ratio(Di, D, 1);
   a.rh = lea::axis_ratio(Hi, H, 1);
   a.rw = lea::axis_ratio(Wi, W, 1);
-  a.flags = flags;
   return lea::conv_common(a, B, k, true, dtype, stream);
 }

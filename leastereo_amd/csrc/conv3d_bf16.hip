@@ -1211,10 +1211,19 @@ __global__ __launch_bounds__(512, 2) void conv_bf16_pair_kernel(const Args a, in
   if (part == 1 && s1 > s0) epilogue_b(s1 - 1);
 }
 
+// The kernel one launch runs on, decided once (route()) from the shape, the sources and the
+// tuning hooks; run() launches it or answers its name, the support query reads it, and nothing
+// else reads a routing hook.
+enum class Engine { None, Tile, Stream, Pair, C8, Tile2D };
 struct Plan {
+  Engine e;    // None: LEA_PAIR_SUM has no kernel for the shape.  Tile: conv_bf16_kernel<ks, mt, wc,
+               // th, td, nb, cv>; Tile2D: its 2D form; Stream: conv_bf16_stream_kernel<1, wc, th, nb,
+               // nch>; Pair: conv_bf16_pair_kernel<th, nb, pp>; C8: conv1x1_c8_kernel<wc, ..>
   int ks, mt, wc, th, td, nb;
-  int nsplit;  // > 0: the D-streaming kernel with nsplit column segments along D
-  bool s1x1;   // the streamed 1x1 (conv1x1_c8_kernel)
+  int nch;     // K chunks of nb channel blocks, over both sources
+  int nsplit;  // > 0: the D-streaming plan with nsplit column segments along D
+  bool cv;     // the cost volume is formed in the halo stage
+  bool pp;     // Pair: the plane-paired tile
 };
 
 int g_override[3] = {0, 0, 0};  // th, td, mt (lea_conv3d_bf16_set_tile_override)
@@ -1228,22 +1237,34 @@ LEA_TUNING_INT(lea_conv3d_bf16_set_pair_split, g_pair_split, 3, 0, 3, "%d")
 // corner loads in flight together 4-5 % faster than one; more tiles per wave slower)
 constexpr int g_rs_tpw = 2;
 
-inline Plan plan(int B, int cout, int D, int H, int W, int ks, int cin) {
+// cin2 of the cin input channels come from the second source; pair = LEA_PAIR_SUM (two equal
+// sources, planned for one of them); d2: lea_conv2d_bnrelu_bf16
+Plan route(int B, int cin, int cin2, int cout, int D, int H, int W, int ks, bool pair, bool cv, bool d2 = false) {
   // r01 sweep (tools/conv_sweep.py --bf16, profiles/r01_conv_sweep_bf16.txt): one
   // 16-row tile per wave with the waves splitting the couts beat 32-row tiles on
   // every layer; 4-row tiles win on the small (L2) volumes; the 8-channel-input
   // layers (one short K chunk) want deeper tiles to amortise staging.
-  Plan p;
+  Plan p{};
+  p.e = Engine::Tile;
   p.ks = ks;
+  p.cv = cv;
+  const int pcin = pair ? cin - cin2 : cin;
   const int cobv = cob_of(cout);
   p.mt = 1;
   p.wc = cobv / 16;
-  p.nb = nb_of(cin, ks);
+  p.nb = nb_of(pcin, ks);
+  p.nch = (cin / 8 + p.nb - 1) / p.nb;
   p.td = (ks == 3) ? 2 : 1;
   const long long ncob = (cout + cobv - 1) / cobv;
   auto wgs = [&](int th, int td) {
     return (long long)((W + 15) / 16) * ((H + th - 1) / th) * ((D + td - 1) / td) * B * ncob;
   };
+  if (d2) {
+    p.e = Engine::Tile2D;
+    p.td = 1;
+    p.th = wgs(8, 1) >= 1024 ? 8 : 4;
+    return p;
+  }
   p.th = wgs(8, p.td) < 8192 ? 4 : 8;
   if (ks == 3 && p.nb == 1 && wgs(8, 4) >= 2048) {
     p.th = 8;
@@ -1253,7 +1274,7 @@ inline Plan plan(int B, int cout, int D, int H, int W, int ks, int cin) {
   // fragment read from LDS by two waves instead of four): same-box C4 +0.35 %, C3 +0.55 % over
   // four order-balanced rounds (profiles/r05_conv12_mt2_ab.txt; the first, fixed-order A/B
   // read +1.2 % -- part of that was the second-run bias)
-  if (ks == 3 && cin >= 64 && cobv == 64) {
+  if (ks == 3 && pcin >= 64 && cobv == 64) {
     p.th = 8;
     p.td = 2;
     p.mt = 2;
@@ -1265,151 +1286,183 @@ inline Plan plan(int B, int cout, int D, int H, int W, int ks, int cin) {
     p.mt = std::min(g_override[2], cobv / 16);
     p.wc = cobv / 16 / p.mt;
   }
-  p.nsplit = 0;
-  p.s1x1 = ks == 1 && cin <= 128 && g_stream1x1 && g_variant == 0 && g_override[0] == 0;
+  const bool planner = g_variant == 0 && g_override[0] == 0;
+  if (ks == 1 && pcin <= 128 && g_stream1x1 && planner && !cv) p.e = Engine::C8;
   // (r02 tools/bf16_stream_bench.py: two-chunk layers with 64-cout blocks -- the L2
   // 32->96 sibling groups -- hold 221 VGPRs of weights and accumulators and run slower
   // streamed; they stay on the tile kernel)
-  const bool two_chunks_wide = cin > 8 * p.nb && cobv > 32;
-  if (ks == 3 && cin <= 16 * p.nb && !two_chunks_wide && g_variant == 0 && g_override[0] == 0 && D >= 4) {
+  const bool two_chunks_wide = pcin > 8 * p.nb && cobv > 32;
+  if (ks == 3 && pcin <= 16 * p.nb && !two_chunks_wide && planner && D >= 4) {
     // one or two K chunks (cin <= 32): stream along D; column segments so the grid
     // holds >= 6 workgroups per CU, each walking >= 4 steps
     p.mt = 1;
     p.wc = cobv / 16;
-    p.th = cin <= 8 ? 8 : 4;
+    p.th = pcin <= 8 ? 8 : 4;
     p.td = 2;
     const long long cols = (long long)((W + 15) / 16) * ((H + p.th - 1) / p.th) * B * ncob;
     const int nst = (D + 1) / 2;
     long long ns = (1536 + cols - 1) / cols;
     ns = std::min<long long>(ns, std::max(1, nst / 4));
     p.nsplit = (int)std::max<long long>(ns, 1);
+    // one source, or LEA_PAIR_SUM's two (the ring walks the blocks of both); two sources of
+    // one conv stay on the tile kernel
+    if (!cv && (cin2 == 0 || pair)) p.e = Engine::Stream;
+  }
+  if (pair) {
+    // two equal sources of one K chunk each (the L0 / L1 cell steps), one 16-cout block, on the
+    // D-streaming plan: the split-wave pair kernel (conv a / conv b on separate wave halves)
+    // where lea_conv3d_bf16_set_pair_split puts it, else the two-source streaming kernel
+    if (cout > 16 || p.nsplit <= 0 || pcin > 8 * p.nb) p.e = Engine::None;
+    else if (g_pair_split && p.nch == 2 && ((p.nb == 2 && p.th == 4 && g_pair_split != 3) || (p.nb == 1 && p.th == 8))) {
+      p.e = Engine::Pair;
+      p.pp = p.nb == 1 && g_pair_split >= 2 && cout <= 8;
+    }
   }
   return p;
 }
 
+// The grid of every launch: cout blocks of cob_of(cout), the plan's K chunks, and tiles of 16 x th
+// voxels by td planes (td == 0: the D-streaming kernels' p.nsplit column segments) as one
+// dimension a.nblk -- or (th == 0) the streamed 1x1's walk of the flat run (walk_grid):
+// *g = (workgroups, B * ncob)
+inline int grid(Args& a, int B, const Plan& p, int th, int td, const char* what, dim3* g = nullptr, int* tpw = nullptr) {
+  const int cobv = cob_of(a.cout);
+  a.ncob = (a.cout + cobv - 1) / cobv;
+  a.nchunks = p.nch;
+  if (th == 0) {
+    const long long gx = walk_grid((long long)a.D * a.H * a.W, (long long)B * a.ncob, tpw);
+    LEA_CHECK_ARG(gx < (1LL << 31) && (long long)B * a.ncob <= 65535, "%s: grid too large", what);
+    *g = dim3((unsigned)gx, B * a.ncob);
+    return LEA_OK;
+  }
+  a.tiles_w = (a.W + 15) / 16;
+  a.ntiles = a.tiles_w * ((a.H + th - 1) / th);
+  if (td > 0) a.ndz = (a.D + td - 1) / td;
+  const long long n = (long long)a.ntiles * (td > 0 ? a.ndz : p.nsplit) * B * a.ncob;
+  LEA_CHECK_ARG(n < (1LL << 31), "%s: grid too large", what);
+  a.nblk = (int)n;
+  return LEA_OK;
+}
+
+// One instantiation: launched (over a.nblk workgroups) if the plan names it
+#define LEA_BF_GRID(...) \
+  if (const int rc = name ? LEA_OK : grid(a, B, p, __VA_ARGS__)) return rc
 #define LEA_BF_CASE(KS, MT, WC, TH, TD, NB, CV)                                       \
   if (p.ks == KS && p.mt == MT && p.wc == WC && p.th == TH && p.td == TD && p.nb == NB) { \
-    a.tiles_w = (a.W + 15) / 16;                                                      \
-    a.ntiles = a.tiles_w * ((a.H + TH - 1) / TH);                                     \
-    a.ndz = (a.D + TD - 1) / TD;                                                      \
-    const long long nb_ = (long long)a.ntiles * a.ndz * B * a.ncob;                   \
-    LEA_CHECK_ARG(nb_ < (1LL << 31), "lea_conv3d(bf16): grid too large");             \
-    a.nblk = (int)nb_;                                                                \
-    const size_t lds_ = (size_t)(a.nchunks > 1 ? 2 : 1) * Cfg<KS, MT, WC, TH, TD, NB, CV>::STAGE * 16; \
-    conv_bf16_kernel<KS, MT, WC, TH, TD, NB, CV><<<dim3((unsigned)nb_), kThreads, lds_, st>>>(a); \
-    return launch_status("lea_conv3d(bf16)");                                         \
+    LEA_BF_GRID(TH, TD, "lea_conv3d(bf16)");                                          \
+    LEA_LAUNCH("lea_conv3d(bf16)", dim3((unsigned)a.nblk), kThreads,                  \
+               ((size_t)(a.nchunks > 1 ? 2 : 1) * Cfg<KS, MT, WC, TH, TD, NB, CV>::STAGE * 16), (a), \
+               conv_bf16_kernel<KS, MT, WC, TH, TD, NB, CV>);                         \
   }
 #define LEA_BF_TH(KS, MT, WC, TD, NB, CV) \
   LEA_BF_CASE(KS, MT, WC, 16, TD, NB, CV) LEA_BF_CASE(KS, MT, WC, 8, TD, NB, CV) LEA_BF_CASE(KS, MT, WC, 4, TD, NB, CV)
 #define LEA_BF_MT(KS, TD, NB, CV)                                                         \
   LEA_BF_TH(KS, 1, 1, TD, NB, CV) LEA_BF_TH(KS, 2, 1, TD, NB, CV) LEA_BF_TH(KS, 1, 2, TD, NB, CV) \
   LEA_BF_TH(KS, 2, 2, TD, NB, CV) LEA_BF_TH(KS, 1, 4, TD, NB, CV)
-
-#define LEA_BFS_CASE(WC, TH, NB, NCH)                                                         \
-  if (p.wc == WC && p.th == TH && p.nb == NB && a.nchunks == NCH) {                           \
-    a.tiles_w = (a.W + 15) / 16;                                                              \
-    a.ntiles = a.tiles_w * ((a.H + TH - 1) / TH);                                             \
-    const long long nb_ = (long long)a.ntiles * p.nsplit * B * a.ncob;                        \
-    LEA_CHECK_ARG(nb_ < (1LL << 31), "lea_conv3d(bf16 stream): grid too large");              \
-    a.nblk = (int)nb_;                                                                        \
-    using S_ = SCfg<1, WC, TH, NB, NCH>;                                                      \
-    const size_t lds_ = (size_t)((a.flags & LEA_RESIDUAL) ? S_::LDSW : S_::RINGW) * 16;       \
-    conv_bf16_stream_kernel<1, WC, TH, NB, NCH><<<dim3((unsigned)nb_), kThreads, lds_, st>>>(a, p.nsplit); \
-    return launch_status("lea_conv3d(bf16 stream)");                                         \
-  }
-
-int run(const Plan& p, Args a, int B, hipStream_t st, bool cv) {
-  if (p.s1x1 && !cv) {
-    const long long vox = (long long)a.D * a.H * a.W;
-    const long long tiles = (vox + 15) / 16;
-    // about 8192 waves over the batch and cout blocks, each walking tpw tiles
-    const long long tpw = std::max(1LL, (tiles * B * a.ncob + 8191) / 8192);
-    const long long gx = (tiles + 4 * tpw - 1) / (4 * tpw);
-    LEA_CHECK_ARG(gx < (1LL << 31) && (long long)B * a.ncob <= 65535, "lea_conv3d(bf16 1x1): grid too large");
-    const dim3 grid((unsigned)gx, B * a.ncob);
-    // one-chunk layers and the two-chunk ones with >= 2 cout tiles on the specialised forms;
-    // the two-chunk single-tile layers measured 2 % slower at 6 waves per SIMD than at 4
-    // (r05 tools/rs_probe.py --one, profiles/r05_1x1_rs_probe.txt)
-    const int nch0 = (a.cin / 8 + 3) / 4, nch = (nch0 == 1 || (nch0 == 2 && p.wc >= 2)) ? nch0 : 4;
-#define LEA_1X1(MT_)                                                                            \
-  if (p.wc == MT_) {                                                                            \
-    if (nch == 1) conv1x1_c8_kernel<MT_, 1><<<grid, 256, 0, st>>>(a, (int)tpw);                 \
-    else if (nch == 2) conv1x1_c8_kernel<MT_, 2><<<grid, 256, 0, st>>>(a, (int)tpw);            \
-    else conv1x1_c8_kernel<MT_, 4><<<grid, 256, 0, st>>>(a, (int)tpw);                          \
-  }
-    LEA_1X1(1) LEA_1X1(2) LEA_1X1(4)
-#undef LEA_1X1
-    return launch_status("lea_conv3d(bf16 1x1)");
-  }
-  if ((a.flags & LEA_PAIR_SUM) && g_pair_split && p.nsplit > 0 && a.ncob == 1 && (a.nchunks == 2) &&
-      ((p.nb == 2 && p.th == 4 && g_pair_split != 3) || (p.nb == 1 && p.th == 8))) {
-    // the split-wave pair kernel (conv a / conv b on separate wave halves)
-    a.tiles_w = (a.W + 15) / 16;
-    a.ntiles = a.tiles_w * ((a.H + p.th - 1) / p.th);
-    const long long nb_ = (long long)a.ntiles * p.nsplit * B;
-    LEA_CHECK_ARG(nb_ < (1LL << 31), "lea_conv3d(bf16 pair): grid too large");
-    LEA_CHECK_ARG((long long)(a.cin / 16 + 1) * a.D * a.H * a.W * 16 < 0xFFFFFFF0LL,
-                  "lea_conv3d(bf16 pair): volume too large");
-    a.nblk = (int)nb_;
-    if (p.nb == 2)
-      conv_bf16_pair_kernel<4, 2, false><<<dim3((unsigned)nb_), 512, PCfg<4, 2>::LDSW * 16, st>>>(a, p.nsplit);
-    else if (g_pair_split >= 2 && a.cout <= 8)
-      conv_bf16_pair_kernel<8, 1, true><<<dim3((unsigned)nb_), 512, PCfg<8, 1, true>::LDSW * 16, st>>>(a, p.nsplit);
-    else
-      conv_bf16_pair_kernel<8, 1, false><<<dim3((unsigned)nb_), 512, PCfg<8, 1>::LDSW * 16, st>>>(a, p.nsplit);
-    return launch_status("lea_conv3d(bf16 pair)");
-  }
-  // (one source, or LEA_PAIR_SUM's two: the ring walks the blocks of both)
-  if (p.nsplit > 0 && !cv && (a.cb1 * 8 == a.cin || (a.flags & LEA_PAIR_SUM))) {
-    LEA_CHECK_ARG((long long)std::max(a.cin, a.cout + 7) / 8 * a.D * a.H * a.W * 16 < 0xFFFFFFF0LL,
-                  "lea_conv3d(bf16 stream): volume too large");
-    LEA_BFS_CASE(1, 8, 1, 1) LEA_BFS_CASE(2, 8, 1, 1) LEA_BFS_CASE(4, 8, 1, 1)
-    LEA_BFS_CASE(1, 4, 2, 1) LEA_BFS_CASE(2, 4, 2, 1) LEA_BFS_CASE(4, 4, 2, 1)
-    LEA_BFS_CASE(1, 4, 2, 2) LEA_BFS_CASE(2, 4, 2, 2) LEA_BFS_CASE(1, 8, 1, 2)
-  }
-  if (a.flags & LEA_PAIR_SUM) {
-    set_error("lea_conv3d(bf16): LEA_PAIR_SUM runs on the D-streaming kernel only (cout <= 16, D >= 4)");
-    return LEA_E_UNSUPPORTED;
-  }
-  if (cv) {
-    LEA_BF_MT(3, 2, 2, true)
-    LEA_BF_MT(3, 1, 2, true)
-  } else {
-    LEA_BF_MT(3, 2, 1, false)
-    LEA_BF_MT(3, 2, 2, false)
-    LEA_BF_MT(3, 1, 1, false)
-    LEA_BF_MT(3, 1, 2, false)
-    LEA_BF_MT(3, 4, 1, false)
-    LEA_BF_MT(3, 4, 2, false)
-    LEA_BF_MT(1, 1, 4, false)
-  }
-  set_error("lea_conv3d(bf16): no tile ks=%d mt=%d wc=%d th=%d td=%d nb=%d cv=%d", p.ks, p.mt, p.wc,
-            p.th, p.td, p.nb, (int)cv);
-  return LEA_E_UNSUPPORTED;
-}
-
 #define LEA_BF2D_CASE(WC, TH, NB)                                                           \
   if (p.wc == WC && p.th == TH && p.nb == NB) {                                             \
-    a.tiles_w = (a.W + 15) / 16;                                                            \
-    a.ntiles = a.tiles_w * ((a.H + TH - 1) / TH);                                           \
-    a.ndz = 1;                                                                              \
-    const long long nb_ = (long long)a.ntiles * B * a.ncob;                                 \
-    LEA_CHECK_ARG(nb_ < (1LL << 31), "lea_conv2d(bf16): grid too large");                   \
-    a.nblk = (int)nb_;                                                                      \
-    const size_t lds_ = (size_t)(a.nchunks > 1 ? 2 : 1) * Cfg<3, 1, WC, TH, 1, NB, false, 1>::STAGE * 16; \
-    conv_bf16_kernel<3, 1, WC, TH, 1, NB, false, 1><<<dim3((unsigned)nb_), kThreads, lds_, st>>>(a); \
-    return launch_status("lea_conv2d(bf16)");                                               \
+    LEA_BF_GRID(TH, 1, "lea_conv2d(bf16)");                                                 \
+    LEA_LAUNCH("lea_conv2d(bf16)", dim3((unsigned)a.nblk), kThreads,                        \
+               ((size_t)(a.nchunks > 1 ? 2 : 1) * Cfg<3, 1, WC, TH, 1, NB, false, 1>::STAGE * 16), (a), \
+               conv_bf16_kernel<3, 1, WC, TH, 1, NB, false, 1>);                            \
   }
 #define LEA_BF2D_NB(WC, NB) LEA_BF2D_CASE(WC, 8, NB) LEA_BF2D_CASE(WC, 4, NB)
+#define LEA_BFS_CASE(WC, TH, NB, NCH)                                                         \
+  if (p.wc == WC && p.th == TH && p.nb == NB && p.nch == NCH) {                               \
+    LEA_BF_GRID(TH, 0, "lea_conv3d(bf16 stream)");                                            \
+    LEA_LAUNCH("lea_conv3d(bf16 stream)", dim3((unsigned)a.nblk), kThreads,                   \
+               ((size_t)((a.flags & LEA_RESIDUAL) ? SCfg<1, WC, TH, NB, NCH>::LDSW : SCfg<1, WC, TH, NB, NCH>::RINGW) * 16), \
+               (a, p.nsplit), conv_bf16_stream_kernel<1, WC, TH, NB, NCH>);                   \
+  }
+#define LEA_BFP_CASE(TH, NB, PP)                                                              \
+  if (p.th == TH && p.nb == NB && p.pp == PP)                                                 \
+    LEA_LAUNCH("lea_conv3d(bf16 pair)", dim3((unsigned)a.nblk), 512, (PCfg<TH, NB, PP>::LDSW * 16), (a, p.nsplit), \
+               conv_bf16_pair_kernel<TH, NB, PP>);
+// (one name for every NCH form)
+#define LEA_C8_CASE(WC, NCH)                                                                  \
+  if (p.wc == WC && nch == NCH)                                                               \
+    LEA_LAUNCH_AS("conv1x1_c8_kernel<" #WC ">", "lea_conv3d(bf16 1x1)", g, 256, 0, (a, tpw), conv1x1_c8_kernel<WC, NCH>);
+#define LEA_C8_WC(WC) LEA_C8_CASE(WC, 1) LEA_C8_CASE(WC, 2) LEA_C8_CASE(WC, 4)
 
-int run2d(const Plan& p, Args a, int B, hipStream_t st) {
-  LEA_BF2D_NB(1, 1) LEA_BF2D_NB(1, 2) LEA_BF2D_NB(2, 1) LEA_BF2D_NB(2, 2) LEA_BF2D_NB(4, 1)
-  LEA_BF2D_NB(4, 2)
-  set_error("lea_conv2d(bf16): no tile wc=%d th=%d nb=%d", p.wc, p.th, p.nb);
+// Launch plan p or (name != NULL) answer its kernel's name; LEA_E_UNSUPPORTED for a plan without
+// an instantiation (a tile override can ask for one)
+int run(const Plan& p, Args a, int B, hipStream_t st, const char** name) {
+  switch (p.e) {
+    case Engine::C8: {
+      dim3 g;
+      int tpw = 0;
+      LEA_BF_GRID(0, 0, "lea_conv3d(bf16 1x1)", &g, &tpw);
+      // one-chunk layers and the two-chunk ones with >= 2 cout tiles on the specialised forms;
+      // the two-chunk single-tile layers measured 2 % slower at 6 waves per SIMD than at 4
+      // (r05 tools/rs_probe.py --one, profiles/r05_1x1_rs_probe.txt)
+      const int nch = (p.nch == 1 || (p.nch == 2 && p.wc >= 2)) ? p.nch : 4;
+      LEA_C8_WC(1) LEA_C8_WC(2) LEA_C8_WC(4)
+      break;
+    }
+    case Engine::Pair:
+      LEA_BF_GRID(p.th, 0, "lea_conv3d(bf16 pair)");
+      LEA_CHECK_ARG(name || (long long)(a.cin / 16 + 1) * a.D * a.H * a.W * 16 < 0xFFFFFFF0LL,
+                    "lea_conv3d(bf16 pair): volume too large");
+      LEA_BFP_CASE(4, 2, false) LEA_BFP_CASE(8, 1, true) LEA_BFP_CASE(8, 1, false)
+      break;
+    case Engine::Stream:
+      LEA_CHECK_ARG(name || (long long)std::max(a.cin, a.cout + 7) / 8 * a.D * a.H * a.W * 16 < 0xFFFFFFF0LL,
+                    "lea_conv3d(bf16 stream): volume too large");
+      LEA_BFS_CASE(1, 8, 1, 1) LEA_BFS_CASE(2, 8, 1, 1) LEA_BFS_CASE(4, 8, 1, 1)
+      LEA_BFS_CASE(1, 4, 2, 1) LEA_BFS_CASE(2, 4, 2, 1) LEA_BFS_CASE(4, 4, 2, 1)
+      LEA_BFS_CASE(1, 4, 2, 2) LEA_BFS_CASE(2, 4, 2, 2) LEA_BFS_CASE(1, 8, 1, 2)
+      break;
+    case Engine::Tile2D:
+      LEA_BF2D_NB(1, 1) LEA_BF2D_NB(1, 2) LEA_BF2D_NB(2, 1) LEA_BF2D_NB(2, 2) LEA_BF2D_NB(4, 1)
+      LEA_BF2D_NB(4, 2)
+      set_error("lea_conv2d(bf16): no tile wc=%d th=%d nb=%d", p.wc, p.th, p.nb);
+      return LEA_E_UNSUPPORTED;
+    case Engine::Tile:
+      if (p.cv) {
+        LEA_BF_MT(3, 2, 2, true)
+        LEA_BF_MT(3, 1, 2, true)
+      } else {
+        LEA_BF_MT(3, 2, 1, false)
+        LEA_BF_MT(3, 2, 2, false)
+        LEA_BF_MT(3, 1, 1, false)
+        LEA_BF_MT(3, 1, 2, false)
+        LEA_BF_MT(3, 4, 1, false)
+        LEA_BF_MT(3, 4, 2, false)
+        LEA_BF_MT(1, 1, 4, false)
+      }
+      break;
+    case Engine::None: break;
+  }
+  set_error("lea_conv3d(bf16): no tile ks=%d mt=%d wc=%d th=%d td=%d nb=%d cv=%d", p.ks, p.mt, p.wc,
+            p.th, p.td, p.nb, (int)p.cv);
   return LEA_E_UNSUPPORTED;
 }
 
-thread_local char g_bf_name[96];
+// The operands every entry point shares (cin2 of the cin input channels come from x2)
+inline Args args(const void* x, long long xbs, const void* x2, long long x2bs, int cin2, const void* wp,
+                 const float* scale, const float* shift, const void* res, long long rbs, void* y, long long ybs,
+                 int cin, int cout, int D, int H, int W, unsigned flags) {
+  Args a{};
+  a.x = (const __bf16*)x;
+  a.xbs = xbs;
+  a.x2 = (const __bf16*)x2;
+  a.x2bs = x2bs;
+  a.cb1 = (cin - cin2) / 8;
+  a.wp = (const __bf16*)wp;
+  a.scale = scale;
+  a.shift = shift;
+  a.res = (const __bf16*)res;
+  a.rbs = rbs;
+  a.y = (__bf16*)y;
+  a.ybs = ybs;
+  a.cin = cin;
+  a.cout = cout;
+  a.D = D;
+  a.H = H;
+  a.W = W;
+  a.flags = flags;
+  return a;
+}
 
 }  // namespace bf
 }  // namespace lea
@@ -1455,26 +1508,28 @@ extern "C" int lea_conv3d_pack_weights_bf16(const float* w, void* packed, int co
 }
 
 extern "C" int lea_conv3d_bf16_pair_supported(int B, int cin, int cout, int D, int H, int W) {
-  // the same conditions bf16_conv_common applies to LEA_PAIR_SUM (the tuning
-  // knobs can take a shape off the D-streaming plan)
+  // what bf16_conv_common answers to LEA_PAIR_SUM with two sources of cin channels (ADVICE r05:
+  // the tuning knobs can take a shape off the D-streaming plan)
   if (B <= 0 || cin <= 0 || cout <= 0 || D <= 0 || H <= 0 || W <= 0 || cin % 8 || cout % 8) return 0;
-  const bf::Plan p = bf::plan(B, cout, D, H, W, 3, cin);
-  return cout <= 16 && p.nsplit > 0 && cin <= 8 * p.nb ? 1 : 0;
+  return bf::route(B, 2 * cin, cin, cout, D, H, W, 3, true, false).e != bf::Engine::None;
 }
 
+extern "C" const char* lea_conv3d_launch_kernel_name_bf16(int B, int cin, int cin2, int cout, int D, int H, int W,
+                                                          int k, unsigned flags, int costvolume) {
+  clear_error();
+  const bool pair = flags & LEA_PAIR_SUM;
+  if (B <= 0 || cout <= 0 || cin <= 0 || cin2 < 0 || cin2 >= cin || (k != 1 && k != 3) || D <= 0 || H <= 0 || W <= 0 ||
+      (pair && (2 * cin2 != cin || k != 3 || costvolume || (flags & LEA_RESIDUAL))))
+    return nullptr;
+  const char* name = nullptr;
+  return bf::run(bf::route(B, cin, cin2, cout, D, H, W, k, pair, costvolume != 0), bf::Args{}, 1, nullptr, &name) == LEA_OK
+             ? name : nullptr;
+}
+
+// (one source, no flags)
 extern "C" const char* lea_conv3d_kernel_name_bf16(int B, int cout, int cin, int D, int H, int W,
                                                    int k, int costvolume) {
-  if (B <= 0 || cout <= 0 || cin <= 0 || (k != 1 && k != 3) || D <= 0 || H <= 0 || W <= 0) return nullptr;
-  const bf::Plan p = bf::plan(B, cout, D, H, W, k, cin);
-  if (p.s1x1 && !costvolume)
-    snprintf(bf::g_bf_name, sizeof(bf::g_bf_name), "conv1x1_c8_kernel<%d>", p.wc);
-  else if (p.nsplit > 0 && !costvolume)
-    snprintf(bf::g_bf_name, sizeof(bf::g_bf_name), "conv_bf16_stream_kernel<1, %d, %d, %d, %d>", p.wc, p.th,
-             p.nb, (cin / 8 + p.nb - 1) / p.nb);
-  else
-    snprintf(bf::g_bf_name, sizeof(bf::g_bf_name), "conv_bf16_kernel<%d, %d, %d, %d, %d, %d, %s>",
-             p.ks, p.mt, p.wc, p.th, p.td, p.nb, costvolume ? "true" : "false");
-  return bf::g_bf_name;
+  return lea_conv3d_launch_kernel_name_bf16(B, cin, 0, cout, D, H, W, k, 0, costvolume);
 }
 
 static int bf16_conv_common(bf::Args& a, int B, int k, bool cv, void* stream) {
@@ -1491,13 +1546,12 @@ static int bf16_conv_common(bf::Args& a, int B, int k, bool cv, void* stream) {
   LEA_CHECK_ARG(a.x != (const __bf16*)a.y && a.x2 != (const __bf16*)a.y,
                 "lea_conv3d(bf16): input aliases output");
   const bool pair = a.flags & LEA_PAIR_SUM;
-  bf::Plan p = bf::plan(B, a.cout, a.D, a.H, a.W, k, pair ? a.cb1 * 8 : a.cin);
+  const bf::Plan p = bf::route(B, a.cin, a.cin - a.cb1 * 8, a.cout, a.D, a.H, a.W, k, pair, cv);
   if (pair) {
-    // two equal sources of one K chunk each (the L0 / L1 cell steps), one 16-cout block: the
-    // packed weight is conv a's chunk then conv b's
+    // the packed weight is conv a's chunk then conv b's
     LEA_CHECK_ARG(!(a.flags & LEA_RESIDUAL) && a.x2 && 2 * a.cb1 * 8 == a.cin && k == 3 && !cv,
                   "lea_conv3d(bf16): LEA_PAIR_SUM needs two equal sources and no residual");
-    if (a.cout > 16 || p.nsplit <= 0 || a.cb1 * 8 > 8 * p.nb) {
+    if (p.e == bf::Engine::None) {
       set_error("lea_conv3d(bf16): LEA_PAIR_SUM unsupported for cin=%d cout=%d D=%d", a.cin, a.cout, a.D);
       return LEA_E_UNSUPPORTED;
     }
@@ -1506,10 +1560,7 @@ static int bf16_conv_common(bf::Args& a, int B, int k, bool cv, void* stream) {
   // through 32-bit buffer offsets
   LEA_CHECK_ARG(p.nsplit <= 0 || (long long)std::max(a.cin, a.cout) / 8 * a.D * a.H * a.W * 16 < (1LL << 32),
                 "lea_conv3d(bf16): batch element too large for the D-streaming kernel");
-  const int cobv = bf::cob_of(a.cout);
-  a.ncob = (a.cout + cobv - 1) / cobv;
-  a.nchunks = (a.cin / 8 + p.nb - 1) / p.nb;
-  return bf::run(p, a, B, as_stream(stream), cv);
+  return bf::run(p, a, B, as_stream(stream), nullptr);
 }
 
 // dtype LEA_BF16 counterparts of lea_conv3d_bnrelu / lea_conv3d_bnrelu_costvolume
@@ -1520,25 +1571,8 @@ extern "C" int lea_conv3d_bnrelu_bf16(const void* x, int64_t x_bstride, const vo
                                       int64_t r_bstride, void* y, int64_t y_bstride, int B, int cin,
                                       int cout, int D, int H, int W, int k, unsigned flags,
                                       void* stream) {
-  bf::Args a{};
-  a.x = (const __bf16*)x;
-  a.xbs = x_bstride;
-  a.x2 = (const __bf16*)x2;
-  a.x2bs = x2_bstride;
-  a.cb1 = (cin - cin2) / 8;
-  a.wp = (const __bf16*)w_packed;
-  a.scale = scale;
-  a.shift = shift;
-  a.res = (const __bf16*)residual;
-  a.rbs = r_bstride;
-  a.y = (__bf16*)y;
-  a.ybs = y_bstride;
-  a.cin = cin;
-  a.cout = cout;
-  a.D = D;
-  a.H = H;
-  a.W = W;
-  a.flags = flags;
+  bf::Args a = bf::args(x, x_bstride, x2, x2_bstride, cin2, w_packed, scale, shift, residual, r_bstride, y, y_bstride,
+                        cin, cout, D, H, W, flags);
   clear_error();
   LEA_CHECK_FLAGS(flags, LEA_RELU | LEA_RESIDUAL | LEA_PAIR_SUM, "lea_conv3d_bnrelu_bf16");
   if (cin2 % 8 != 0 || (cin2 > 0 && !x2)) {
@@ -1553,23 +1587,8 @@ extern "C" int lea_conv3d_bnrelu_costvolume_bf16(const void* left, const void* r
                                                  const float* scale, const float* shift, void* y,
                                                  int64_t y_bstride, int B, int C, int cout, int D3,
                                                  int H, int W, unsigned flags, void* stream) {
-  bf::Args a{};
-  a.x = (const __bf16*)left;
-  a.xbs = f_bstride;
-  a.x2 = (const __bf16*)right;
-  a.x2bs = f_bstride;
-  a.cb1 = C / 8;
-  a.wp = (const __bf16*)w_packed;
-  a.scale = scale;
-  a.shift = shift;
-  a.y = (__bf16*)y;
-  a.ybs = y_bstride;
-  a.cin = 2 * C;
-  a.cout = cout;
-  a.D = D3;
-  a.H = H;
-  a.W = W;
-  a.flags = flags & LEA_RELU;
+  bf::Args a = bf::args(left, f_bstride, right, f_bstride, C, w_packed, scale, shift, nullptr, 0, y, y_bstride, 2 * C,
+                        cout, D3, H, W, flags & LEA_RELU);
   clear_error();
   LEA_CHECK_FLAGS(flags, LEA_RELU, "lea_conv3d_bnrelu_costvolume_bf16");
   if (C % 16 != 0) {  // chunks of 2 blocks must not straddle left/right
@@ -1722,24 +1741,8 @@ extern "C" int lea_conv2d_bnrelu_bf16(const void* x, int64_t x_bstride, const vo
                                       int64_t r_bstride, void* y, int64_t y_bstride, int B, int cin,
                                       int cout, int H, int W, unsigned flags, void* stream) {
   clear_error();
-  bf::Args a{};
-  a.x = (const __bf16*)x;
-  a.xbs = x_bstride;
-  a.x2 = (const __bf16*)x;
-  a.cb1 = cin / 8;
-  a.wp = (const __bf16*)w_packed;
-  a.scale = scale;
-  a.shift = shift;
-  a.res = (const __bf16*)residual;
-  a.rbs = r_bstride;
-  a.y = (__bf16*)y;
-  a.ybs = y_bstride;
-  a.cin = cin;
-  a.cout = cout;
-  a.D = 1;
-  a.H = H;
-  a.W = W;
-  a.flags = flags;
+  const bf::Args a = bf::args(x, x_bstride, x, 0, 0, w_packed, scale, shift, residual, r_bstride, y, y_bstride, cin,
+                              cout, 1, H, W, flags);
   LEA_CHECK_ARG(x && w_packed && y && x != y, "lea_conv2d_bnrelu_bf16: null or aliased pointer");
   LEA_CHECK_ARG((scale == nullptr) == (shift == nullptr),
                 "lea_conv2d_bnrelu_bf16: scale/shift must both be set or both NULL");
@@ -1747,16 +1750,5 @@ extern "C" int lea_conv2d_bnrelu_bf16(const void* x, int64_t x_bstride, const vo
   LEA_CHECK_ARG(!(flags & LEA_RESIDUAL) || residual, "lea_conv2d_bnrelu_bf16: LEA_RESIDUAL without residual");
   LEA_CHECK_ARG(B > 0 && cin > 0 && cout > 0 && H > 0 && W > 0 && cin % 8 == 0 && cout % 8 == 0,
                 "lea_conv2d_bnrelu_bf16: bad shape B=%d cin=%d cout=%d H=%d W=%d", B, cin, cout, H, W);
-  const int cobv = bf::cob_of(cout);
-  bf::Plan p;
-  p.ks = 3;
-  p.mt = 1;
-  p.wc = cobv / 16;
-  p.nb = bf::nb_of(cin, 3);
-  p.td = 1;
-  const long long wgs8 = (long long)((W + 15) / 16) * ((H + 7) / 8) * B * ((cout + cobv - 1) / cobv);
-  p.th = wgs8 >= 1024 ? 8 : 4;
-  a.ncob = (cout + cobv - 1) / cobv;
-  a.nchunks = (cin / 8 + p.nb - 1) / p.nb;
-  return bf::run2d(p, a, B, as_stream(stream));
+  return bf::run(bf::route(B, cin, 0, cout, 1, H, W, 3, false, false, true), a, B, as_stream(stream), nullptr);
 }

@@ -485,25 +485,74 @@ __global__ __launch_bounds__(kConvThreads, 2) void conv3d_dma_kernel(const ConvA
   epilogue_dma<3, MT, NT, TW, TD, RES, KD>(a, acc, epi, geo, b);
 }
 
-// A launch plan: which instantiation runs a given shape (also reported by name).
+// A launch plan: which instantiation runs a given shape.  route() (conv3d.hip) decides it once from
+// the shape, the operands and the tuning hooks; run() launches it or, for a name query, answers
+// its kernel's name, and nothing else reads a routing hook.
 struct Plan {
   int engine;  // 0 = dma (k3), 1 = 1x1 streaming, 2 = reg resample, 3 = valu (k3, cout <= 2),
-               // 4 = dma depth-paired, 5 = resampled 1x1 gather-GEMM
+               // 4 = dma depth-paired, 5 = resampled 1x1 gather-GEMM,
+               // 6 = few-channel 2D tile (conv2d_small_kernel<mt, nt>)
   int mt, nt, tw, td;
+  int ks;      // engine 2: the kernel size (1 or 3)
+  int kd;      // engine 0: 3, or 1 = the feature net's 2D tiles
+  bool cv;     // engine 0: the cost volume is formed in the halo stage
+  bool heads, vec;  // engine 1: lea_conv1x1_heads' two-output kernel; the NT-float vector form
 };
 
-// DMA engine: one-dimensional grid, decoded (XCD-aware) inside the kernel.
-template <typename K>
-int launch_dma(K kernel, const ConvArgs& a0, int th, int tw, int td, int B, hipStream_t st) {
-  ConvArgs a = a0;
+// The operands every entry point shares (cin2 of the cin input channels come from x2)
+inline ConvArgs conv_args(const void* x, long long xbs, const void* x2, long long x2bs, int cin2, const float* wp,
+                          const float* scale, const float* shift, const void* res, long long rbs, void* y,
+                          long long ybs, int cin, int cout, int D, int H, int W, unsigned flags) {
+  ConvArgs a{};
+  a.x = (const float*)x;
+  a.xbs = xbs;
+  a.x2 = (const float*)x2;
+  a.x2bs = x2bs;
+  a.cin1 = cin - cin2;
+  a.wp = wp;
+  a.scale = scale;
+  a.shift = shift;
+  a.res = (const float*)res;
+  a.rbs = rbs;
+  a.y = (float*)y;
+  a.ybs = ybs;
+  a.cin = cin;
+  a.cout = cout;
+  a.D = D;
+  a.H = H;
+  a.W = W;
+  a.flags = flags;
+  return a;
+}
+
+// The grid of every launch but the few-channel 2D tile's: cout blocks of cop channels and
+//  * flat > 0: the D*H*W run, 4 waves x `flat` voxels per workgroup (the 1x1 engines); with tpw,
+//    waves that walk *tpw tiles of them (walk_grid) -- *g = (workgroups, B * ncob)
+//  * else tiles of tw x th voxels by td planes: *g = (tiles, planes, B * ncob) for the register-
+//    staged and VALU engines, or (g == NULL) the DMA engine's one dimension a.nblk, decoded
+//    (XCD-aware) inside the kernel
+inline int grid(ConvArgs& a, int B, int cop, int tw, int th, int td, int flat, dim3* g, int* tpw = nullptr) {
+  a.ncob = (a.cout + cop - 1) / cop;
+  const long long bc = (long long)B * a.ncob, vox = (long long)a.D * a.H * a.W;
+  if (flat > 0) {
+    const long long gx = tpw ? walk_grid(vox, bc, tpw) : (vox + 4 * flat - 1) / (4 * flat);
+    LEA_CHECK_ARG(gx < (1LL << 31) && bc <= 65535, "lea_conv3d: grid too large");
+    *g = dim3((unsigned)gx, (unsigned)bc);
+    return LEA_OK;
+  }
   a.tiles_w = a.wtiles > 0 ? a.wtiles : (a.W + tw - 1) / tw;
-  a.ntiles = a.tiles_w * ((a.H + th - 1) / th);
+  const long long nt = (long long)a.tiles_w * ((a.H + th - 1) / th);
   a.ndz = (a.D + td - 1) / td;
-  const long long n = (long long)a.ntiles * a.ndz * B * a.ncob;
+  if (g) {
+    LEA_CHECK_ARG(nt < (1LL << 31) && a.D <= 65535 && bc <= 65535, "lea_conv3d: grid too large");
+    *g = dim3((unsigned)nt, a.ndz, (unsigned)bc);
+    return LEA_OK;
+  }
+  const long long n = nt * a.ndz * bc;
   LEA_CHECK_ARG(n < (1LL << 31), "lea_conv3d: grid too large");
+  a.ntiles = (int)nt;
   a.nblk = (int)n;
-  kernel<<<dim3((unsigned)n), kConvThreads, 0, st>>>(a);
-  return launch_status("lea_conv3d");
+  return LEA_OK;
 }
 
 // Instantiated DMA-engine tiles, per MT (one translation unit each, conv3d_dma_mt*.hip):
@@ -528,72 +577,60 @@ int launch_dma(K kernel, const ConvArgs& a0, int th, int tw, int td, int B, hipS
 
 // Cost-volume-input tiles (matching-net stem0): the planner's 8 x 16 / 4 x 16 tiles.
 #define LEA_DMA_CV_LIST(X, MT) \
-  X(MT, 1, 16, 1, 3) X(MT, 2, 16, 1, 3) X(MT, 1, 16, 2, 3) X(MT, 2, 16, 2, 3)
+  X(MT, 1, 16, 1, 3, true) X(MT, 2, 16, 1, 3, true) X(MT, 1, 16, 2, 3, true) X(MT, 2, 16, 2, 3, true)
 
 // 2D (KD = 1) tiles for the feature net: one plane per workgroup.
-#define LEA_DMA2D_LIST(X, MT) X(MT, 1, 16, 1, 1) X(MT, 2, 16, 1, 1)
-// Depth-paired tiles (KD = 4, couts <= 8; grid steps two planes per workgroup).
-#define LEA_DMA_DP_LIST(X) X(1, 1, 16, 1, 4) X(1, 2, 16, 1, 4)
+#define LEA_DMA2D_LIST(X, MT) X(MT, 1, 16, 1, 1, false) X(MT, 2, 16, 1, 1, false)
+// Depth-paired tiles (KD = 4, couts <= 8; the grid steps two planes per workgroup).
+#define LEA_DMA_DP_LIST(X) X(1, 1, 16, 1, 4, false) X(1, 2, 16, 1, 4, false)
 
-// Per-MT entry points (defined by LEA_DMA_TU in conv3d_dma_mt*.hip).  lds_bytes
-// returns 0 for a tile that is not instantiated; run returns LEA_E_UNSUPPORTED.
-#define LEA_DMA_DECL(MT)                                                  \
-  int dma_lds_bytes_mt##MT(int nt, int tw, int td);                       \
-  int run_dma_mt##MT(const Plan& p, const ConvArgs& a, int B, hipStream_t st);   \
-  int run_dma2d_mt##MT(const Plan& p, const ConvArgs& a, int B, hipStream_t st);
-#define LEA_DMA_DECL_CV(MT) \
-  int run_dma_cv_mt##MT(const Plan& p, const ConvArgs& a, int B, hipStream_t st);
-LEA_DMA_DECL_CV(1)
-LEA_DMA_DECL_CV(2)
-LEA_DMA_DECL_CV(3)
-LEA_DMA_DECL_CV(4)
-#undef LEA_DMA_DECL_CV
-int run_dma_dp(const Plan& p, const ConvArgs& a, int B, hipStream_t st);  // conv3d_dma_mt1.hip
-// the few-channel 2D 3x3 tile (conv2d_small.hip): eligibility and launch
+// Per-MT launch of a DMA-engine plan (engine 0: the 3D, 2D and cost-volume tiles; defined by
+// LEA_DMA_TU in conv3d_dma_mt*.hip), or its kernel's name; LEA_E_UNSUPPORTED for a tile that is
+// not instantiated.  run_dma is the one place that turns p.mt into the unit's call.
+int run_dma_mt1(const Plan& p, ConvArgs a, int B, hipStream_t st, const char** name);
+int run_dma_mt2(const Plan& p, ConvArgs a, int B, hipStream_t st, const char** name);
+int run_dma_mt3(const Plan& p, ConvArgs a, int B, hipStream_t st, const char** name);
+int run_dma_mt4(const Plan& p, ConvArgs a, int B, hipStream_t st, const char** name);
+int run_dma_dp(const Plan& p, ConvArgs a, int B, hipStream_t st, const char** name);  // engine 4, conv3d_dma_mt1.hip
+inline int run_dma(const Plan& p, const ConvArgs& a, int B, hipStream_t st, const char** name) {
+  switch (p.mt) {
+    case 1: return run_dma_mt1(p, a, B, st, name);
+    case 2: return run_dma_mt2(p, a, B, st, name);
+    case 3: return run_dma_mt3(p, a, B, st, name);
+    default: return run_dma_mt4(p, a, B, st, name);
+  }
+}
+// the few-channel 2D 3x3 tile (conv2d_small.hip): eligibility (reads its hook: for route() only),
+// plan and launch
 bool conv2d_small_ok(int cin, int cout);
-int run_conv2d_small(const ConvArgs& a, int B, hipStream_t st);
-LEA_DMA_DECL(1)
-LEA_DMA_DECL(2)
-LEA_DMA_DECL(3)
-LEA_DMA_DECL(4)
-#undef LEA_DMA_DECL
+Plan conv2d_small_plan(int cin, int cout);
+int run_conv2d_small(const Plan& p, const ConvArgs& a, int B, hipStream_t st, const char** name);
 
-#define LEA_DMA_LDS_CASE(MT, NT, TW, TD) \
-  if (nt == NT && tw == TW && td == TD) return 2 * TileCfg<3, MT, NT, TW, TD>::STAGE * 4;
-#define LEA_DMA_RUN_CASE(MT, NT, TW, TD)                                                      \
-  if (p.nt == NT && p.tw == TW && p.td == TD)                                                 \
-    return launch_dma(conv3d_dma_kernel<MT, NT, TW, TD>, a, TileCfg<3, MT, NT, TW, TD>::TH, TW, \
-                      TD, B, st);
-#define LEA_DMA2D_RUN_CASE(MT, NT, TW, TD, KD)                                           \
-  if (p.nt == NT && p.tw == TW && p.td == TD)                                             \
-    return launch_dma(conv3d_dma_kernel<MT, NT, TW, TD, KD>,                              \
-                      a, TileCfg<3, MT, NT, TW, TD, KD>::TH, TW, TD, B, st);
-#define LEA_DMA_DP_RUN_CASE(MT, NT, TW, TD, KD)                                          \
-  if (p.nt == NT && p.tw == TW)                                                           \
-    return launch_dma(conv3d_dma_kernel<MT, NT, TW, TD, KD>,                              \
-                      a, TileCfg<3, MT, NT, TW, TD, KD>::TH, TW, 2, B, st);
-#define LEA_DMA_CV_RUN_CASE(MT, NT, TW, TD, KD)                                          \
-  if (p.nt == NT && p.tw == TW && p.td == TD)                                             \
-    return launch_dma(conv3d_dma_kernel<MT, NT, TW, TD, KD, true>,                        \
-                      a, TileCfg<3, MT, NT, TW, TD, KD>::TH, TW, TD, B, st);
-#define LEA_DMA_TU(MT)                                                            \
-  int dma_lds_bytes_mt##MT(int nt, int tw, int td) {                              \
-    LEA_DMA_LIST_##MT(LEA_DMA_LDS_CASE) return 0;                                 \
-  }                                                                               \
-  int run_dma_mt##MT(const Plan& p, const ConvArgs& a, int B, hipStream_t st) {   \
-    LEA_DMA_LIST_##MT(LEA_DMA_RUN_CASE)                                           \
-    set_error("lea_conv3d: no DMA tile <%d, %d, %d, %d>", MT, p.nt, p.tw, p.td);  \
-    return LEA_E_UNSUPPORTED;                                                     \
-  }                                                                               \
-  int run_dma2d_mt##MT(const Plan& p, const ConvArgs& a, int B, hipStream_t st) { \
-    LEA_DMA2D_LIST(LEA_DMA2D_RUN_CASE, MT)                                        \
-    set_error("lea_conv2d: no DMA tile <%d, %d, %d, 1, 1>", MT, p.nt, p.tw);     \
-    return LEA_E_UNSUPPORTED;                                                     \
-  }                                                                               \
-  int run_dma_cv_mt##MT(const Plan& p, const ConvArgs& a, int B, hipStream_t st) { \
-    LEA_DMA_CV_LIST(LEA_DMA_CV_RUN_CASE, MT)                                      \
-    set_error("lea_conv3d_costvolume: no tile <%d, %d, %d, %d>", MT, p.nt, p.tw, p.td); \
-    return LEA_E_UNSUPPORTED;                                                     \
+// One instantiated tile: launched (DSTEP planes per workgroup) if the plan names it.  The names
+// spell KD and CV out also where the launch leaves them to the template's defaults.
+#define LEA_DMA_CASE(MT, NT, TW, TD, KD, CV, DSTEP)                                               \
+  if (p.nt == NT && p.tw == TW && p.td == TD) {                                                   \
+    if (const int rc = name ? LEA_OK : grid(a, B, MT * 16, TW, TileCfg<3, MT, NT, TW, TD, KD>::TH, DSTEP, 0, nullptr)) \
+      return rc;                                                                                  \
+    LEA_LAUNCH_AS("conv3d_dma_kernel<" #MT ", " #NT ", " #TW ", " #TD ", " #KD ", " #CV ">", "lea_conv3d", \
+                  dim3((unsigned)a.nblk), kConvThreads, 0, (a), conv3d_dma_kernel<MT, NT, TW, TD, KD, CV>); \
+  }
+#define LEA_DMA_RUN_CASE(MT, NT, TW, TD) LEA_DMA_CASE(MT, NT, TW, TD, 3, false, TD)
+#define LEA_DMA_KD_RUN_CASE(MT, NT, TW, TD, KD, CV) LEA_DMA_CASE(MT, NT, TW, TD, KD, CV, TD)
+#define LEA_DMA_DP_RUN_CASE(MT, NT, TW, TD, KD, CV) LEA_DMA_CASE(MT, NT, TW, TD, KD, CV, 2)
+#define LEA_DMA_TU(MT)                                                                      \
+  int run_dma_mt##MT(const Plan& p, ConvArgs a, int B, hipStream_t st, const char** name) { \
+    if (p.cv) {                                                                             \
+      LEA_DMA_CV_LIST(LEA_DMA_KD_RUN_CASE, MT)                                              \
+      set_error("lea_conv3d_costvolume: no tile <%d, %d, %d, %d>", MT, p.nt, p.tw, p.td);   \
+    } else if (p.kd == 1) {                                                                 \
+      LEA_DMA2D_LIST(LEA_DMA_KD_RUN_CASE, MT)                                               \
+      set_error("lea_conv2d: no DMA tile <%d, %d, %d, 1, 1>", MT, p.nt, p.tw);             \
+    } else {                                                                                \
+      LEA_DMA_LIST_##MT(LEA_DMA_RUN_CASE)                                                   \
+      set_error("lea_conv3d: no DMA tile <%d, %d, %d, %d>", MT, p.nt, p.tw, p.td);          \
+    }                                                                                       \
+    return LEA_E_UNSUPPORTED;                                                               \
   }
 
 }  // namespace lea

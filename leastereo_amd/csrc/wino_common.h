@@ -169,17 +169,9 @@ inline int grid(ConvArgs& a, int B, int tw, int th, int td, int cop, int wg_per_
   a.nblk = (int)n;
   return LEA_OK;
 }
-// Launch the kernel named by the macro's tail (template commas and all) over a.nblk workgroups,
-// or, in a name query (name != NULL), answer AS: one expansion serves both.
-#define LEA_WINO_KERNEL_AS(AS, WHAT, THREADS, ...)                      \
-  do {                                                                  \
-    if (name) {                                                         \
-      *name = AS;                                                       \
-      return LEA_OK;                                                    \
-    }                                                                   \
-    __VA_ARGS__<<<dim3((unsigned)a.nblk), THREADS, 0, st>>>(a);         \
-    return launch_status(WHAT);                                         \
-  } while (0)
+// LEA_LAUNCH (common.h) over a.nblk workgroups with the arguments (a)
+#define LEA_WINO_KERNEL_AS(AS, WHAT, THREADS, ...) \
+  LEA_LAUNCH_AS(AS, WHAT, dim3((unsigned)a.nblk), THREADS, 0, (a), __VA_ARGS__)
 #define LEA_WINO_KERNEL(WHAT, THREADS, ...) LEA_WINO_KERNEL_AS(#__VA_ARGS__, WHAT, THREADS, __VA_ARGS__)
 
 // the engines' launches: (route, arguments, batch, stream, name query or NULL)

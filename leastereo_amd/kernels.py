@@ -82,7 +82,7 @@ def _conv_record(b, cin, cout, d, h, w, k, accumulate, in_vox, resampled, name=N
     Winograd F(2,3), times its cout padding); ``esz`` is the activation element size;
     ``nbytes`` replaces the algorithmic byte count (input + output [+ residual] + weights)."""
     if name is None:
-        name = conv_kernel_name(b, cout, d, h, w, k, resampled)
+        name = conv_kernel_name(b, cout, d, h, w, k, resampled, cin)
     if _probe.names is not None and name not in _probe.names:
         return None
     vox = b * d * h * w
@@ -314,8 +314,12 @@ def _second_source(x2, b, spatial, c8=False):
     return x2.data_ptr(), _batch_stride(x2, "x2", c8), x2.shape[1] * (8 if c8 else 1)
 
 
-def conv_kernel_name(b, cout, d, h, w, k, resampled=False):
-    return _decode(_lib.load().lea_conv3d_kernel_name(b, cout, d, h, w, k, 1 if resampled else 0))
+def conv_kernel_name(b, cout, d, h, w, k, resampled=False, cin=None):
+    """The kernel of an f32 conv launch; without ``cin``, of one with at most 128 input channels
+    (a wider resampled 1x1 runs on the register-staged engine)."""
+    if cin is None:
+        return _decode(_lib.load().lea_conv3d_kernel_name(b, cout, d, h, w, k, 1 if resampled else 0))
+    return _decode(_lib.load().lea_conv3d_launch_kernel_name(b, cin, 0, cout, d, h, w, k, 1 if resampled else 0))
 
 
 def build_cost_volume(fl: torch.Tensor, fr: torch.Tensor, maxdisp: int) -> torch.Tensor:
@@ -1352,18 +1356,11 @@ def pack_conv_weight_bf16(w: torch.Tensor) -> torch.Tensor:
     return packed
 
 
-def conv_kernel_name_bf16(b, cout, cin, d, h, w, k, costvolume=False):
-    return _decode(_lib.load().lea_conv3d_kernel_name_bf16(b, cout, cin, d, h, w, k, 1 if costvolume else 0))
-
-
-def _pair_kernel_name_bf16(cb: int) -> str:
-    """The LEA_PAIR_SUM launch's kernel (conv3d_bf16.hip run(): the split-wave kernel unless
-    LEASTEREO_PAIR_SPLIT=0, the two-source D-streaming kernel otherwise) for the probe."""
-    th = 8 if cb == 1 else 4
-    split = os.environ.get("LEASTEREO_PAIR_SPLIT", "3")
-    if split in ("1", "2") or (split == "3" and cb == 1):
-        return f"conv_bf16_pair_kernel<{th}, {cb}, {'true' if split != '1' and cb == 1 else 'false'}>"
-    return f"conv_bf16_stream_kernel<1, 1, {th}, {cb}, 2>"
+def conv_kernel_name_bf16(b, cout, cin, d, h, w, k, costvolume=False, cin2=0, flags=0):
+    """The kernel of a bf16 conv launch (None where the launch refuses); cin2 of the cin input
+    channels come from the second source, flags as the launch's (LEA_PAIR_SUM: the pair launch)."""
+    return _decode(_lib.load().lea_conv3d_launch_kernel_name_bf16(b, cin, cin2, cout, d, h, w, k, flags,
+                                                                  1 if costvolume else 0))
 
 
 def conv3d_bnrelu_bf16(x: torch.Tensor, packed: torch.Tensor, cout: int, k: int,
@@ -1390,7 +1387,7 @@ def conv3d_bnrelu_bf16(x: torch.Tensor, packed: torch.Tensor, cout: int, k: int,
             _flags(relu, rptr is not None, pair_sum),
             probe=lambda: _conv_record(
                 b, cin, cout, d, h, w, k, rptr is not None, b * d * h * w, False,
-                name=(_pair_kernel_name_bf16(cb) if pair_sum else conv_kernel_name_bf16(b, cout, cin, d, h, w, k)),
+                name=conv_kernel_name_bf16(b, cout, cin, d, h, w, k, cin2=cin2, flags=_flags(False, False, pair_sum)),
                 esz=2))
     return out
 
@@ -1398,10 +1395,9 @@ def conv3d_bnrelu_bf16(x: torch.Tensor, packed: torch.Tensor, cout: int, k: int,
 def pair_sum_supported_bf16(x: torch.Tensor, x2: torch.Tensor, out: torch.Tensor) -> bool:
     """Whether conv3d_bnrelu_bf16(..., pair_sum=True) takes these c8 operands: two equal sources
     of one K chunk each (8 or 16 channels), cout <= 16, D >= 4 (the D-streaming kernel)."""
-    if not (x.shape[1] == x2.shape[1] and x.shape[1] in (1, 2) and out.shape[1] * 8 <= 16
-            and x.shape[2] >= 4 and tuple(x.shape[2:5]) == tuple(x2.shape[2:5])):
+    if not (x.shape[1] == x2.shape[1] and tuple(x.shape[2:5]) == tuple(x2.shape[2:5])):
         return False
-    # the library's own plan decides (a tuning override can take the shape off the
+    # the library's own plan decides the rest (a tuning override can take the shape off the
     # D-streaming kernel): ask it rather than fail mid-forward
     b, cb, d, h, w = (int(s) for s in x.shape[:5])
     return bool(_lib.load().lea_conv3d_bf16_pair_supported(b, cb * 8, int(out.shape[1]) * 8, d, h, w))

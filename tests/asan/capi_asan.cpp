@@ -75,6 +75,31 @@ int main() {
   expect_name("cv name", lea_conv3d_costvolume_kernel_name(1, 32, 64, 192, 320), "conv3d_");
   expect_name("2d name", lea_conv2d_kernel_name(2, 32, 192, 320), "conv");
   expect_name("bf16 name", lea_conv3d_kernel_name_bf16(8, 64, 128, 32, 96, 160, 3, 0), "conv");
+  // the queries for a launch's whole argument list: at defaults, under one override (a route
+  // without an instantiation answers NULL, with the error set), and out of range
+  expect_name("launch name", lea_conv3d_launch_kernel_name(1, 64, 0, 16, 16, 48, 80, 1, 1), "conv1x1_rs_f32_kernel<1>");
+  expect_name("launch name wide", lea_conv3d_launch_kernel_name(1, 136, 0, 16, 16, 48, 80, 1, 1), "conv3d_reg_kernel<1,");
+  expect_name("launch name bf16", lea_conv3d_launch_kernel_name_bf16(1, 32, 16, 16, 16, 48, 80, 3, 0, 0),
+              "conv_bf16_kernel<3, 1, 1, 4, 2, 2, false>");
+  expect_name("launch name bf16 pair", lea_conv3d_launch_kernel_name_bf16(1, 16, 8, 8, 16, 48, 80, 3, LEA_PAIR_SUM, 0),
+              "conv_bf16_pair_kernel<8, 1, true>");
+  lea_conv3d_set_tile_override(4, 64, 2);
+  lea_conv3d_bf16_set_tile_override(16, 4, 2);
+  const char* n1 = lea_conv3d_launch_kernel_name(1, 64, 0, 64, 64, 192, 320, 3, 0);
+  expect_err("launch name override", n1 == nullptr ? LEA_E_UNSUPPORTED : LEA_OK, LEA_E_UNSUPPORTED);
+  const char* n2 = lea_conv3d_launch_kernel_name_bf16(1, 64, 32, 32, 64, 192, 320, 3, 0, 1);
+  expect_err("launch name bf16 override", n2 == nullptr ? LEA_E_UNSUPPORTED : LEA_OK, LEA_E_UNSUPPORTED);
+  lea_conv3d_set_tile_override(0, 0, 0);
+  lea_conv3d_bf16_set_tile_override(0, 0, 0);
+  if (lea_conv3d_launch_kernel_name(1, 64, 64, 16, 16, 48, 80, 1, 0) || lea_conv3d_launch_kernel_name(0, 64, 0, 16, 16, 48, 80, 1, 0) ||
+      lea_conv3d_launch_kernel_name(1, 64, -1, 16, 16, 48, 80, 2, 0) ||
+      lea_conv3d_launch_kernel_name_bf16(1, 16, 16, 8, 16, 48, 80, 3, 0, 0) ||
+      lea_conv3d_launch_kernel_name_bf16(1, 24, 8, 8, 16, 48, 80, 3, LEA_PAIR_SUM, 0) ||
+      lea_conv3d_launch_kernel_name_bf16(1, 16, 8, 8, 16, 48, 80, 1, LEA_PAIR_SUM, 0) ||
+      lea_conv3d_launch_kernel_name_bf16(1, 16, 0, 8, -4, 48, 80, 3, 0, 0)) {
+    std::printf("FAIL launch name queries answered out-of-range arguments\n");
+    ++g_fail;
+  }
 
   // every compute entry: null pointers first, then a bad shape / dtype where the
   // pointers are valid host addresses (the checks never dereference them)

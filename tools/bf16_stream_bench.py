@@ -30,7 +30,6 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--batch", type=int, default=8)
     a = ap.parse_args()
-    lib = _lib.load()
     dev = "cuda"
     B = a.batch
     for name, (cin, cout, (d, h, w), acc) in LAYERS.items():
@@ -41,25 +40,24 @@ def main():
         y0 = kernels.to_c8(torch.randn(B, cout, d, h, w, device=dev))
         res = {}
         for v in (1, 0):
-            lib.lea_conv3d_bf16_set_variant(v)
-            y = y0.clone()
-            kernels.conv3d_bnrelu_bf16(x, packed, cout, 3, scale, shift, True, y, acc)
-            res[v] = y
-            yy = y0.clone()
-            for _ in range(2):
-                kernels.conv3d_bnrelu_bf16(x, packed, cout, 3, scale, shift, True, yy, acc)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            for _ in range(a.iters):
-                kernels.conv3d_bnrelu_bf16(x, packed, cout, 3, scale, shift, True, yy, acc)
-            e1.record()
-            torch.cuda.synchronize()
-            ms = e0.elapsed_time(e1) / a.iters
-            nbytes = 2.0 * B * d * h * w * (cin + cout * (2 if acc else 1))
-            print(f"{name:22s} v{v} {kernels.conv_kernel_name_bf16(B, cout, cin, d, h, w, 3):40s} "
-                  f"{ms * 1e3:8.1f} us  {nbytes / ms / 1e6:7.1f} GB/s", flush=True)
-        lib.lea_conv3d_bf16_set_variant(0)
+            with _lib.tuning(lea_conv3d_bf16_set_variant=v):
+                y = y0.clone()
+                kernels.conv3d_bnrelu_bf16(x, packed, cout, 3, scale, shift, True, y, acc)
+                res[v] = y
+                yy = y0.clone()
+                for _ in range(2):
+                    kernels.conv3d_bnrelu_bf16(x, packed, cout, 3, scale, shift, True, yy, acc)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                for _ in range(a.iters):
+                    kernels.conv3d_bnrelu_bf16(x, packed, cout, 3, scale, shift, True, yy, acc)
+                e1.record()
+                torch.cuda.synchronize()
+                ms = e0.elapsed_time(e1) / a.iters
+                nbytes = 2.0 * B * d * h * w * (cin + cout * (2 if acc else 1))
+                print(f"{name:22s} v{v} {kernels.conv_kernel_name_bf16(B, cout, cin, d, h, w, 3):40s} "
+                      f"{ms * 1e3:8.1f} us  {nbytes / ms / 1e6:7.1f} GB/s", flush=True)
         print(f"  bit-identical: {torch.equal(res[0], res[1])}", flush=True)
 
 

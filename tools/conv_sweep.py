@@ -7,7 +7,6 @@ the planner's heuristics in csrc/conv3d.hip are fitted to this table.
   python tools/conv_sweep.py [--iters 10] [--only name,...] [--batch B] [--scale s]
 """
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -22,6 +21,20 @@ TILES = [(nt, tw, td) for td in (1, 2) for nt in (1, 2, 4, 8) for tw in (16, 32,
          if not (tw == 16 and nt > 2)]
 
 
+def timed(launch, iters):
+    """ms per launch, after two warm-up launches."""
+    for _ in range(2):
+        launch()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(iters):
+        launch()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--iters", type=int, default=10)
@@ -31,7 +44,6 @@ def main():
     a = p.parse_args()
     if a.bf16:
         return sweep_bf16(a)
-    lib = _lib.load()
     dev = "cuda"
     only = set(a.only.split(",")) if a.only else None
     out = {}
@@ -47,28 +59,18 @@ def main():
         shift = torch.randn(cout, device=dev, generator=g) * 0.1
         y = torch.zeros(a.batch, cout, d, h, w, device=dev)
         flops = 2.0 * a.batch * d * h * w * cin * cout * 27
-        lib.lea_conv3d_set_tile_override(0, 0, 0)
         default = kernels.conv_kernel_name(a.batch, cout, d, h, w, 3)
         res = {}
         for nt, tw, td in TILES:
-            lib.lea_conv3d_set_tile_override(nt, tw, td)
-            try:
-                for _ in range(2):
-                    kernels.conv3d_bnrelu(x, packed, cout, 3, scale, shift, True, y, acc)
-            except _lib.HipKernelError:
-                continue
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            for _ in range(a.iters):
-                kernels.conv3d_bnrelu(x, packed, cout, 3, scale, shift, True, y, acc)
-            e1.record()
-            torch.cuda.synchronize()
-            ms = e0.elapsed_time(e1) / a.iters
+            with _lib.tuning(lea_conv3d_set_tile_override=(nt, tw, td)):
+                kname = kernels.conv_kernel_name(a.batch, cout, d, h, w, 3)
+                if kname is None:  # a tile that is not instantiated: the launch would refuse
+                    print(f"{name:26s} nt={nt} tw={tw:2d} td={td}  {kname}", flush=True)
+                    continue
+                ms = timed(lambda: kernels.conv3d_bnrelu(x, packed, cout, 3, scale, shift, True, y, acc), a.iters)
             res[f"{nt},{tw},{td}"] = ms
             print(f"{name:26s} nt={nt} tw={tw:2d} td={td}  {ms * 1e3:8.1f} us  "
-                  f"{flops / ms / 1e9:6.1f} TF/s", flush=True)
-        lib.lea_conv3d_set_tile_override(0, 0, 0)
+                  f"{flops / ms / 1e9:6.1f} TF/s  {kname}", flush=True)
         best = min(res, key=res.get)
         print(f"BEST {name}: {best} {res[best] * 1e3:.1f} us (default {default})", flush=True)
         out[name] = {"default": default, "best": best, "times_ms": res}
@@ -76,7 +78,6 @@ def main():
 
 
 def sweep_bf16(a):
-    lib = _lib.load()
     dev = "cuda"
     only = set(a.only.split(",")) if a.only else None
     tiles = [(th, td, mt) for th in (4, 8, 16) for td in (1, 2, 4) for mt in (1, 2)]
@@ -92,28 +93,18 @@ def sweep_bf16(a):
         shift = torch.randn(cout8, device=dev) * 0.1
         y = torch.zeros(a.batch, cout8 // 8, d, h, w, 8, device=dev, dtype=torch.bfloat16)
         flops = 2.0 * a.batch * d * h * w * cin * cout8 * 27
-        lib.lea_conv3d_bf16_set_tile_override(0, 0, 0)
         default = kernels.conv_kernel_name_bf16(a.batch, cout8, cin, d, h, w, 3)
         res = {}
         for th, td, mt in tiles:
-            lib.lea_conv3d_bf16_set_tile_override(th, td, mt)
-            try:
-                for _ in range(2):
-                    kernels.conv3d_bnrelu_bf16(x, packed, cout8, 3, scale, shift, True, y, acc)
-            except _lib.HipKernelError:
-                continue
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            for _ in range(a.iters):
-                kernels.conv3d_bnrelu_bf16(x, packed, cout8, 3, scale, shift, True, y, acc)
-            e1.record()
-            torch.cuda.synchronize()
-            ms = e0.elapsed_time(e1) / a.iters
+            with _lib.tuning(lea_conv3d_bf16_set_tile_override=(th, td, mt)):
+                kname = kernels.conv_kernel_name_bf16(a.batch, cout8, cin, d, h, w, 3)
+                if kname is None:
+                    print(f"{name:26s} th={th:2d} td={td} mt={mt}  {kname}", flush=True)
+                    continue
+                ms = timed(lambda: kernels.conv3d_bnrelu_bf16(x, packed, cout8, 3, scale, shift, True, y, acc), a.iters)
             res[f"{th},{td},{mt}"] = ms
             print(f"{name:26s} th={th:2d} td={td} mt={mt}  {ms * 1e3:8.1f} us  "
-                  f"{flops / ms / 1e9:7.1f} TF/s", flush=True)
-        lib.lea_conv3d_bf16_set_tile_override(0, 0, 0)
+                  f"{flops / ms / 1e9:7.1f} TF/s  {kname}", flush=True)
         best = min(res, key=res.get)
         print(f"BEST {name}: {best} {res[best] * 1e3:.1f} us (default {default})", flush=True)
         out[name] = {"default": default, "best": best, "times_ms": res}

@@ -14,7 +14,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from leastereo_amd import kernels  # noqa: E402
+from leastereo_amd import _lib, kernels  # noqa: E402
 
 B = 8
 CASES = [("L1 16+16->16", 16, (32, 96, 160)), ("L0 8+8->8", 8, (64, 192, 320))]
@@ -56,16 +56,13 @@ def main():
         def two():
             kernels.conv3d_bnrelu_bf16(xa, pa, c, 3, sc[:c], sh[:c], True, y2)
             kernels.conv3d_bnrelu_bf16(xb, pb, c, 3, sc[c:], sh[c:], True, y2, accumulate=True)
-        from leastereo_amd import _lib
-        lib = _lib.load()
-        lib.lea_conv3d_bf16_set_pair_split(0)
-        t_pair0 = timed(pair, a.iters)
-        lib.lea_conv3d_bf16_set_pair_split(1)
-        t_pair1 = timed(pair, a.iters)
+        with _lib.tuning(lea_conv3d_bf16_set_pair_split=0):
+            t_pair0 = timed(pair, a.iters)
+        with _lib.tuning(lea_conv3d_bf16_set_pair_split=1):
+            t_pair1 = timed(pair, a.iters)
         y1b = y1.clone()
-        lib.lea_conv3d_bf16_set_pair_split(2)
-        t_pair, t_two = timed(pair, a.iters), timed(two, a.iters)
-        lib.lea_conv3d_bf16_set_pair_split(3)  # the default again
+        with _lib.tuning(lea_conv3d_bf16_set_pair_split=2):
+            t_pair, t_two = timed(pair, a.iters), timed(two, a.iters)
         print(f"{name:14s} pair (both convs per wave) {t_pair0:8.1f} us ({3 * (B * d * h * w * c * 2) / t_pair0 / 1e6:5.2f} TB/s)")
         print(f"{name:14s} pair (split, no PP)        {t_pair1:8.1f} us ({3 * (B * d * h * w * c * 2) / t_pair1 / 1e6:5.2f} TB/s)"
               f"   max|PP - no PP|/max {float((y1.float() - y1b.float()).abs().max() / y1b.float().abs().max()):.2e}")
