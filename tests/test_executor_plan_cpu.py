@@ -24,6 +24,7 @@ from leastereo_amd.config import LEAStereoArgs, default_arch_args
 from leastereo_amd.model import LEAStereo
 from leastereo_amd.weights import synthetic_state_dict
 from oracle import torch_ref as ref
+from tests.arch_variants import FEATURE_PATHS, MATCHING_PATHS, PLANNED, arch_with, random_genotype
 from tests.executor_stands import Stand
 from tests.golden_util import arch, normal
 
@@ -120,3 +121,66 @@ def test_matching_executor_plan_matches_oracle(tmp_path, fake, monkeypatch, geno
     assert got.shape == want.shape
     err = float((got - want).abs().max())
     assert err <= 1e-5 * float(want.abs().max()), err
+
+
+# ---- a seeded sweep of random genotypes x level paths (tests/arch_variants.random_genotype: each
+# step 1-3 of its branches, a random primitive per row; the row order within a step shuffled for
+# every other draw, as the shipped file's is), the route switches drawn with them
+def _cpu_model(tmp_path, a):
+    args = LEAStereoArgs(maxdisp=48)
+    for k in ("net_arch_fea", "cell_arch_fea", "net_arch_mat", "cell_arch_mat"):
+        setattr(args, k, str(tmp_path / (k + ".npy")))
+        np.save(getattr(args, k), a[k])
+    m = LEAStereo(default_arch_args(args), "cpu")
+    sd = synthetic_state_dict({k: tuple(v.shape) for k, v in m.state_dict().items()}, bn_file=None)
+    m.load_state_dict(sd, strict=True)
+    return m.double().eval(), {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()}
+
+
+def _draw(seed, paths):
+    rng = np.random.default_rng(seed)
+    geno = random_genotype(rng, shuffle=bool(seed % 2))
+    path = sorted(paths, key=str)[int(rng.integers(len(paths)))]
+    return rng, geno, path
+
+
+@pytest.mark.parametrize("seed", range(30))
+def test_feature_executor_random_genotype_matches_oracle(tmp_path, fake, monkeypatch, seed):
+    rng, geno, path = _draw(4100 + seed, FEATURE_PATHS)
+    monkeypatch.setattr(ex.FeatureExecutor, "PAIR_S0", bool(rng.integers(2)))
+    a = arch_with(arch(), fea_geno=geno, fea_path=path)
+    m, sd64 = _cpu_model(tmp_path, a)
+    fe = ex.FeatureExecutor(m.feature)
+    for i, pair in fe.s0_pair.items():
+        assert not ({k for k, _ in fe.s1_group.get(i, [])} & {k for k, _ in pair})
+    x = normal(4200 + seed, (2, 3, 48, 96)).double()
+    with torch.no_grad():
+        got = fe.run(x)
+        want = ref.feature_forward(sd64, x, a["net_arch_fea"], a["cell_arch_fea"])
+    assert got.shape == want.shape
+    err = float((got - want).abs().max())
+    assert err <= 1e-5 * float(want.abs().max()), (geno, path, err)
+
+
+@pytest.mark.parametrize("seed", range(30))
+def test_matching_executor_random_genotype_matches_oracle(tmp_path, fake, monkeypatch, seed):
+    rng, geno, path = _draw(4300 + seed, MATCHING_PATHS)
+    monkeypatch.setattr(ex.MatchingExecutor, "PAIR_STEPS", bool(rng.integers(2)))
+    monkeypatch.setattr(ex.MatchingExecutor, "SPLIT_S1_GROUP48", bool(rng.integers(2)))
+    monkeypatch.setattr(ex, "CV_STEM", False)
+    a = arch_with(arch(), mat_geno=geno, mat_path=path)
+    m, sd64 = _cpu_model(tmp_path, a)
+    me = ex.MatchingExecutor(m.matching)
+    # the routes that depend on the level path alone
+    plan = PLANNED[path]
+    assert {i for i in range(12) if f"cells.{i}.share" in me.p} == plan["share"]
+    assert {i for i in range(12) if f"cells.{i}.fanout" in me.p} == plan["fanout"]
+    assert me._conv1_takes_down((8, 16, 32)) == plan["conv1_down"]
+    assert me._cell0_takes_down((16, 32, 64)) == plan["cell0_down"]
+    x = normal(4400 + seed, (1, 64, 16, 32, 64)).double()
+    with torch.no_grad():
+        got = me.run(x)
+        want = ref.matching_forward(sd64, x, a["net_arch_mat"], a["cell_arch_mat"])
+    assert got.shape == want.shape
+    err = float((got - want).abs().max())
+    assert err <= 1e-5 * float(want.abs().max()), (geno, path, err)

@@ -1,11 +1,18 @@
 """Pin the CPU oracle (oracle/torch_ref.py) against golden vectors produced by
-running the reference itself (tools/gen_golden.py).  CPU only."""
+running the reference itself (tools/gen_golden.py; architectures other than the shipped
+one: tools/gen_golden_arch.py).  CPU only."""
+import json
+import os
+
 import numpy as np
 import pytest
 import torch
 
 from oracle import torch_ref as ref
-from tests.golden_util import arch, golden, meta, normal, state_dict
+from leastereo_amd.config import LEAStereoArgs, default_arch_args
+from leastereo_amd.model import LEAStereo
+from leastereo_amd.weights import state_dict_sha256, synthetic_state_dict
+from tests.golden_util import GOLD, arch, golden, meta, normal, state_dict
 
 CASES = meta()["cases"]
 
@@ -73,3 +80,33 @@ def test_e2e(name):
     d32 = st["disp"]
     assert ref.epe(d32, torch.from_numpy(g[name + "/disp32"])) < 1e-4
     assert ref.epe(d32, torch.from_numpy(g[name + "/disp64"])) < 1e-4
+
+
+with open(os.path.join(GOLD, "arch_variants.json")) as _f:
+    ARCH_CASES = json.load(_f)["cases"]
+ARCH_KEYS = ("net_arch_fea", "cell_arch_fea", "net_arch_mat", "cell_arch_mat")
+
+
+@pytest.mark.parametrize("name", sorted(ARCH_CASES))
+def test_arch_variants(tmp_path, name):
+    """Genotypes and level paths other than the shipped ones: the oracle in float32 against the
+    reference's float32 feature map and matching cost, at test_e2e's tolerances.  The weights are
+    the recipe without the calibrated BN file, on the shapes of the model built from the case's
+    four arrays (held to the hash of what the reference's own model was loaded with)."""
+    c = ARCH_CASES[name]
+    a = {k: np.array(c[k]) for k in ARCH_KEYS}
+    args = LEAStereoArgs(maxdisp=c["maxdisp"])
+    for k in ARCH_KEYS:
+        setattr(args, k, str(tmp_path / (k + ".npy")))
+        np.save(getattr(args, k), a[k])
+    m = LEAStereo(default_arch_args(args), "cpu")
+    sd = synthetic_state_dict({k: tuple(v.shape) for k, v in m.state_dict().items()}, bn_file=None)
+    assert len(sd) == c["n_tensors"] and state_dict_sha256(sd) == c["state_dict_sha256"]
+    shape = (c["batch"], 3, c["height"], c["width"])
+    left, right = normal(c["seeds"][0], shape), normal(c["seeds"][1], shape)
+    g = golden("arch_variants")
+    with torch.no_grad():
+        st = ref.leastereo_forward(sd, left, right, c["maxdisp"], a, return_stages=True)
+    assert list(st["fea_l"].shape) == c["shapes"]["fea_l"] and list(st["matching"].shape) == c["shapes"]["matching"]
+    np.testing.assert_allclose(st["fea_l"].numpy(), g[name + "/fea_l"], rtol=1e-4, atol=1e-4)
+    np.testing.assert_allclose(st["matching"].numpy(), g[name + "/matching"], rtol=1e-4, atol=1e-3)
