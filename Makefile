@@ -41,9 +41,9 @@ build/asan/%.o: leastereo_amd/csrc/%.hip $(wildcard leastereo_amd/csrc/*.h) incl
 # linked with every unit: capi the ABI at large, disp_stats lea_disparity_regression_stats, lr the
 # left-right check, loss the median and edge loss, transform the training transform, photo
 # photometric consistency, scene whole-scene inference, refine the refinement, speckle the filter,
-# pointcloud the point cloud, rectify the rectification, warp the view synthesis
+# pointcloud the point cloud, rectify the rectification, warp the view synthesis, dsm the surface model
 ASANDRIVERS := capi_asan disp_stats_asan lr_asan loss_asan transform_asan photo_asan scene_asan refine_asan \
-               speckle_asan pointcloud_asan rectify_asan warp_asan
+               speckle_asan pointcloud_asan rectify_asan warp_asan dsm_asan
 
 $(ASANDRIVERS:%=build/asan/%_main.o): build/asan/%_main.o: tests/asan/%.cpp include/leastereo_hip.h include/leastereo_hip_tuning.h
 	@mkdir -p build/asan

@@ -646,6 +646,99 @@ int lea_forward_warp_f32(const float* image, int64_t image_bstride, const float*
                          float fill_value, float* warped, float* zview, uint8_t* state,
                          float* source, void* stream);
 
+/* Surface model (additive: the ABI number stays 14): point clouds rasterised into a regular
+ * ground grid that keeps, per cell, the highest surface seen there (a digital surface model)
+ * and the colour or the row of that surface (an orthophoto).  The grid is a persistent
+ * accumulator: any number of lea_dsm_splat_f32 calls add clouds to it, lea_dsm_resolve_f32 reads
+ * it out without changing it, lea_dsm_clear empties it.  No entry synchronises the host,
+ * allocates or reads anything back; all three are capturable.
+ *
+ * The key.  A surface is keys: uint64 [B, GH, GW]; 0 is an empty cell.  A hit of height z with a
+ * 32-bit payload has the key (ord(z) << 32) | payload, where ord maps the bits b of a float32 to
+ * ~b for a negative (sign bit set, -0.0 included) and to b | 0x80000000 otherwise: unsigned order
+ * on ord is numeric order on z, with -0.0 just below +0.0.  z is finite, so ord(z) >= 0x00800000
+ * and a hit is never 0.  A cell holds the unsigned 64-bit maximum of the keys of the hits that
+ * cover it: the highest surface, and among equal heights the larger payload.  A maximum does
+ * not depend on the order of its operands, so a grid is the same bits call after call, whatever
+ * the scheduling, the order in which clouds are added, and the form of the scatter.
+ *
+ * lea_dsm_splat_f32.  points: f32 [B, rows, 3] (an organised cloud flattened, or compact rows).
+ * count: int32 [B] on the device or NULL; rows at and beyond min(max(count[b], 0), rows) are not
+ * read (NULL: all rows).  colours: uint8 [B, rows, 3] or NULL.  G: f32 [12] per item on the
+ * device, a row-major 3 x 4 matrix, item b's at G + b * g_bstride (floats; 0 = one matrix for
+ * all, else >= 12), read at every launch and replay.  radius: in cells,
+ * 0 <= radius <= LEA_DSM_MAX_RADIUS.  row_width: 0, or the width of the image the rows are the
+ * pixels of (0 .. rows), a performance hint alone: the result does not depend on it.  staging:
+ * LEA_DSM_STAGING_AUTO, _GLOBAL or _LDS; the result does not depend on it either.
+ * Per row (X, Y, Z), every product and sum a separately rounded float32 operation, in this order:
+ *   u = ((G[0][0] * X + G[0][1] * Y) + G[0][2] * Z) + G[0][3]
+ *   v = ((G[1][0] * X + G[1][1] * Y) + G[1][2] * Z) + G[1][3]
+ *   z = ((G[2][0] * X + G[2][1] * Y) + G[2][2] * Z) + G[2][3]
+ * The row is skipped when X, Y, Z, u, v or z is not finite or |u| or |v| exceeds 2^30 (compared
+ * as floats, before any conversion to an integer).  Cell i has its centre at the integer i.  The
+ * row covers columns floorf((u - radius) + 0.5f) .. floorf((u + radius) + 0.5f) and rows
+ * floorf((v - radius) + 0.5f) .. floorf((v + radius) + 0.5f), clipped to the grid: at most 5 x 5
+ * cells, the nearest cell (floorf(u + 0.5f), floorf(v + 0.5f)) alone at radius 0.
+ * Payload: with colours R << 16 | G << 8 | B; without, 0xFFFFFFFF - row (row within the item),
+ * so that the smallest row wins among equal heights and lea_dsm_resolve_f32 gives it back.
+ * hits: int32 [B, GH, GW] or NULL; hits[nearest cell] += 1 (an integer atomic add) for every row
+ * that is not skipped and whose nearest cell is in the grid, whatever the radius.
+ * The two forms of the scatter.  Global: one 64-bit atomic max on keys per covered cell.
+ * LDS-staged: a workgroup takes 1024 rows (consecutive, or a 32 x 32 pixel patch with
+ * row_width > 0) and the bounding box of the cells they cover; a box of at most 4096 cells is
+ * zeroed in LDS (48 KB with the counts: three workgroups a CU), takes the hits with LDS
+ * atomics and is flushed as contiguous runs of global atomics, non-empty cells only; a larger
+ * box takes the global form.  The two give identical bits on every input.  Auto is the staged
+ * form where it was measured not slower on model-like fields ("Surface model"): with
+ * row_width > 0; the global form for runs of rows.
+ * Any contents of points, count, G and colours are memory-safe (NaN, infinities, 1e30,
+ * denormals, negative counts).  One launch; no lock, no spin, no workgroup waits for another, no
+ * float atomics.
+ * LEA_E_INVALID, before any launch: a null points, G or keys; B, rows, GH or GW < 1 (or B above
+ * 65535, B*GH*GW or B*rows above 2^31 - 1); row_width outside 0 .. rows; a G stride that is
+ * neither 0 nor >= 12; radius NaN or outside 0 .. LEA_DSM_MAX_RADIUS; staging outside 0 .. 2;
+ * keys not 8-byte aligned; points, G, count or hits not 4-byte aligned; keys or hits overlapping
+ * an input or each other.
+ *
+ * lea_dsm_resolve_f32.  keys as above, never written.  hits: the surface's counts or NULL; not
+ * read, only kept apart from the outputs.  iterations (0 .. 1024) fill passes, each reading the
+ * buffer the pass before wrote (the first reads keys): a cell empty at the start of the pass with
+ * at least min_neighbours (1 .. 8) non-empty cells among its 8 neighbours inside the grid takes
+ * the smallest of their keys (the lowest surface beside it, the background, as the left-right
+ * fill and the forward warp choose; among equal heights the smaller payload); every other cell
+ * keeps its key.  Then, per cell with key k after the passes:
+ *   height (f32)        the float whose ord is k >> 32, bit for bit; nodata where k = 0
+ *   rgb    (u8 [.., 3]) bits 16-23, 8-15, 0-7 of k; (0, 0, 0) where k = 0
+ *   source (int32)      0xFFFFFFFF - (k & 0xFFFFFFFF); -1 where k = 0
+ *   state  (u8)         0 measured (keys non-zero), 1 filled, 2 empty
+ * each [B, GH, GW], each optional through NULL (never written), at least one required; rgb and
+ * source are the two readings of one payload, at most one of them.  workspace:
+ * lea_dsm_resolve_workspace_bytes(B, GH, GW) bytes on the device (0 for a non-positive size),
+ * 8-byte aligned, contents need not be initialised; may be NULL with iterations = 0.
+ * iterations + 1 launches, no atomics.
+ * LEA_E_INVALID, before any launch: a null keys; every output null; both rgb and source; B, GH or
+ * GW < 1 (or beyond the limits above); iterations outside 0 .. 1024; min_neighbours outside
+ * 1 .. 8; a null workspace with iterations > 0; keys or the workspace not 8-byte aligned; height,
+ * source or hits not 4-byte aligned; an output overlapping keys, hits, the workspace or another
+ * output; the workspace overlapping keys or hits.
+ *
+ * lea_dsm_clear.  keys, and hits where given, set to 0.  One launch.  LEA_E_INVALID, before the
+ * launch: a null keys; B, GH or GW < 1 (or beyond the limits above); misaligned keys or hits;
+ * hits overlapping keys. */
+#define LEA_DSM_MAX_RADIUS 2
+#define LEA_DSM_STAGING_AUTO 0
+#define LEA_DSM_STAGING_GLOBAL 1
+#define LEA_DSM_STAGING_LDS 2
+int lea_dsm_splat_f32(const float* points, const int32_t* count, const uint8_t* colours,
+                      const float* G, int64_t g_bstride, int B, int rows, int row_width,
+                      float radius, int staging, int GH, int GW, uint64_t* keys, int32_t* hits,
+                      void* stream);
+size_t lea_dsm_resolve_workspace_bytes(int B, int GH, int GW);
+int lea_dsm_resolve_f32(const uint64_t* keys, const int32_t* hits, int B, int GH, int GW,
+                        int iterations, int min_neighbours, float nodata, void* workspace,
+                        float* height, uint8_t* rgb, int32_t* source, uint8_t* state, void* stream);
+int lea_dsm_clear(uint64_t* keys, int32_t* hits, int B, int GH, int GW, void* stream);
+
 /* ---- bf16 path (BASELINE configs 3 and 4) ----
  * Activations are bf16 in the "c8" layout: NCDHW with channels blocked by 8
  * innermost, x[b][c/8][d][h][w][c%8] (one voxel's 8 channels = one 16-byte word;

@@ -95,6 +95,11 @@ SIGNATURES = {
     # view synthesis: forward warp with occlusion and fill (csrc/forward_warp.hip)
     "lea_forward_warp_f32": (_i, [_p, _i64, _p, _i64, _p, _p, _i, _i, _i, _i, ctypes.c_float, ctypes.c_float, _i,
                                   ctypes.c_float, _p, _p, _p, _p, _p]),
+    # surface model: z-buffered DSM and orthophoto from clouds (csrc/dsm.hip)
+    "lea_dsm_splat_f32": (_i, [_p, _p, _p, _p, _i64, _i, _i, _i, ctypes.c_float, _i, _i, _i, _p, _p, _p]),
+    "lea_dsm_resolve_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "lea_dsm_resolve_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, ctypes.c_float, _p, _p, _p, _p, _p, _p]),
+    "lea_dsm_clear": (_i, [_p, _p, _i, _i, _i, _p]),
     # bf16 path (c8 layout)
     "lea_conv3d_packed_elems_bf16": (ctypes.c_size_t, [_i, _i, _i]),
     "lea_conv3d_pack_weights_bf16": (_i, [_p, _p, _i, _i, _i, _p]),

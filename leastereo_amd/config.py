@@ -155,5 +155,19 @@ def obtain_predict_args(argv=None):
                              "right image (not in the reference)")
     parser.add_argument("--view_fill", type=int, default=1, choices=(0, 1),
                         help="1: the holes of --novel_view take the background beside them, 0: they stay black")
+    parser.add_argument("--dsm", type=int, default=0,
+                        help="1: also write {index}_dsm.npy (float32 heights, NaN = nodata), {index}_dsm.png, "
+                             "{index}_ortho.png, {index}_dsm_state.png and {index}_dsm.json: the digital surface "
+                             "model and orthophoto of the map --pointcloud would take, on a ground grid under a "
+                             "camera looking straight down; needs --pc_focal and --pc_baseline, or --calib (not in "
+                             "the reference)")
+    parser.add_argument("--dsm_cell", type=float, default=0.0, metavar="C",
+                        help="cell size of --dsm in the baseline's unit (0 = the ground sample distance at the "
+                             "farthest point)")
+    parser.add_argument("--dsm_radius", type=float, default=0.5, metavar="R",
+                        help="footprint radius of a point under --dsm, in cells, 0 .. 2")
+    parser.add_argument("--dsm_fill", type=int, default=0, metavar="T",
+                        help="fill passes of --dsm: an empty cell with three or more measured neighbours takes the "
+                             "lowest of them")
     add_leastereo_args(parser)
     return parser.parse_args(argv)

@@ -48,6 +48,11 @@ Restates the host-side steps around ``LEAStereo.forward`` (predict.py:144-243):
                        before the transform or the scene path; --pointcloud 1 then takes focal,
                        baseline and principal point from the rectification and leaves out the left
                        pixels that have no source
+  * ``dsm_options`` / ``dsm_of_map`` / ``save_dsm``  not in the reference: --dsm 1 [--dsm_cell C
+                       --dsm_radius R --dsm_fill T] rasterises the cloud of the map --pointcloud
+                       would take into a z-buffered ground grid on the device (``dsm.Surface``)
+                       and writes {index}_dsm.npy / _dsm.png / _ortho.png / _dsm_state.png /
+                       _dsm.json; needs the calibration --pointcloud needs.
   * ``novel_view_options`` / ``novel_view_of_map`` / ``save_view``  not in the reference: --novel_view S
                        [--view_fill 0|1] warps the decoded left image forward to baseline fraction S
                        (``kernels.forward_warp``) through the best map the other flags made -- the
@@ -389,6 +394,13 @@ def pointcloud_of_map(disp, exclude, left_u8, focal, baseline, cx=None, cy=None,
     ``cx_right`` the right view's principal point and ``valid`` [h, w] its validity map: pixels
     without a source give no point.  Returns ``kernels.HostPointCloud`` (count, xyz, rgb, index,
     normals)."""
+    return _cloud_of_map(disp, exclude, left_u8, focal, baseline, cx, cy, max_depth, normals, device, cx_right,
+                         valid)[0].to_host()
+
+
+def _cloud_of_map(disp, exclude, left_u8, focal, baseline, cx, cy, max_depth, normals, device, cx_right, valid):
+    """The device ``kernels.PointCloud`` of ``pointcloud_of_map``, its float64 Q, and the excluded
+    pixels as a host bool map (None without any)."""
     from . import kernels
     from .pointcloud import q_matrix
     h, w = left_u8.shape[:2]
@@ -403,7 +415,92 @@ def pointcloud_of_map(disp, exclude, left_u8, focal, baseline, cx=None, cy=None,
     img = _device_u8(left_u8[y0:y0 + mh, x0:x0 + mw], device)
     cloud = kernels.reproject(d, Q, img, e, min_disp=focal * baseline / max_depth if max_depth > 0 else 0.0,
                               normals=normals)
-    return cloud.to_host()
+    return cloud, Q, e
+
+
+def dsm_options(opt):
+    """--dsm 1 [--dsm_cell C --dsm_radius R --dsm_fill T] as a dict (calib: the dict of
+    ``pointcloud_options``, cell: None for the ground sample distance at the far disparity,
+    radius, fill); None when the flag is off (the other three are then not looked at).  Needs
+    the calibration --pointcloud needs (--pc_focal and --pc_baseline, or --calib) and refuses a
+    cell that is not a finite number >= 0, a radius outside 0 .. 2, a fill count outside
+    0 .. 1024 and --satellite."""
+    import argparse
+    if not getattr(opt, "dsm", 0):
+        return None
+    from .dsm import MAX_FILL, MAX_RADIUS
+    if getattr(opt, "satellite", 0):
+        raise NotImplementedError("--dsm writes its files beside the --sceneflow outputs only")
+    try:
+        calib = pointcloud_options(argparse.Namespace(**dict(vars(opt), pointcloud=1)))
+    except ValueError as e:
+        raise ValueError(f"--dsm needs the calibration of --pointcloud: {e}") from None
+    if not 0 <= opt.dsm_cell < float("inf"):
+        raise ValueError(f"--dsm_cell {opt.dsm_cell}: a cell size > 0 in the baseline's unit, or 0 for the ground "
+                         f"sample distance at the farthest point")
+    if not 0 <= opt.dsm_radius <= MAX_RADIUS:
+        raise ValueError(f"--dsm_radius {opt.dsm_radius}: a footprint radius in cells, 0 .. {MAX_RADIUS}")
+    if not 0 <= opt.dsm_fill <= MAX_FILL:
+        raise ValueError(f"--dsm_fill {opt.dsm_fill}: a number of fill passes, 0 .. {MAX_FILL}")
+    return dict(calib=calib, cell=float(opt.dsm_cell) or None, radius=float(opt.dsm_radius), fill=int(opt.dsm_fill))
+
+
+DSM_MAX_CELLS = 1 << 28  # of the grid --dsm makes for one pair
+
+
+def dsm_of_map(disp, exclude, left_u8, calib, cell=None, radius=0.5, fill=0, device="cuda", cx_right=None,
+               valid=None):
+    """The surface model of a written map: ``pointcloud_of_map``'s cloud, kept on the device, on
+    the bounding grid (``dsm.grid_from_view``) of the view between the smallest and the largest
+    disparity that gives a point (the smallest is focal * baseline / max_depth with a depth
+    limit), the camera looking straight down: height = -Z, in the baseline's unit.  ``calib`` is
+    the dict of ``pointcloud_options`` with focal and baseline filled in.  Returns (height
+    [GH, GW] float32, NaN for nodata; ortho [GH, GW, 3] uint8; state [GH, GW] uint8; meta: G,
+    cell, origin, size) as numpy arrays and a dict."""
+    from . import dsm
+    focal, baseline, max_depth = calib["focal"], calib["baseline"], calib["max_depth"]
+    cloud, Q, e = _cloud_of_map(disp, exclude, left_u8, focal, baseline, calib["cx"], calib["cy"], max_depth, False,
+                                device, cx_right, valid)
+    d = np.asarray(disp, dtype=np.float32)
+    lo = focal * baseline / max_depth if max_depth > 0 else 0.0
+    ok = np.isfinite(d) & (d > lo)
+    if e is not None:
+        ok &= e.cpu().numpy() == 0
+    if not ok.any():
+        raise ValueError("--dsm: no pixel of the map gives a point")
+    far, near = float(d[ok].min()), float(d[ok].max())
+    if far == near:
+        near = far * 2.0
+    mh, mw = d.shape
+    G, gh, gw = dsm.grid_from_view(Q, mh, mw, (far, near), cell)
+    if gh * gw > DSM_MAX_CELLS:
+        raise ValueError(f"--dsm: the grid would be {gh} x {gw} cells; give a larger --dsm_cell or a --pc_max_depth")
+    surface = dsm.Surface(gh, gw, device)
+    maps = surface.add_cloud(cloud, G, radius=radius).resolve(fill_iterations=fill)
+    size = 1.0 / float(G[0, 0])
+    meta = dict(G=[[float(v) for v in row] for row in G], cell=size,
+                origin=[-float(G[0, 3]) * size, -float(G[1, 3]) * size, 0.0], size=[gh, gw])
+    return maps.height.cpu().numpy(), maps.rgb.cpu().numpy(), maps.state.cpu().numpy(), meta
+
+
+def save_dsm(prefix, height, ortho, state, meta):
+    """<prefix>_dsm.npy (float32, NaN for nodata), <prefix>_dsm.png (the heights min-max 8-bit,
+    nodata black), <prefix>_ortho.png, <prefix>_dsm_state.png (8-bit: measured 0, filled 127,
+    empty 255) and <prefix>_dsm.json (G, cell, origin, size)."""
+    import json
+
+    from PIL import Image
+    np.save(prefix + "_dsm.npy", height.astype(np.float32))
+    seen = np.isfinite(height)
+    grey = np.zeros(height.shape, np.float64)
+    if seen.any():
+        lo, hi = float(height[seen].min()), float(height[seen].max())
+        grey[seen] = (height[seen] - lo) / (hi - lo) if hi > lo else 1.0
+    save_float_png(prefix + "_dsm.png", grey)
+    Image.fromarray(ortho).save(prefix + "_ortho.png")
+    save_float_png(prefix + "_dsm_state.png", occlusion_u8(state))
+    with open(prefix + "_dsm.json", "w") as f:
+        json.dump(meta, f, indent=1)
 
 
 def save_pointcloud(prefix, cloud):
@@ -652,6 +749,7 @@ def main(argv=None):
     cloud_opt = pointcloud_options(opt)
     rect_opt = rectify_options(opt)
     view_opt = novel_view_options(opt)
+    dsm_opt = dsm_options(opt)
     if not torch.cuda.is_available():
         raise RuntimeError("leastereo_amd runs on a ROCm device only")
     set_rectifier(None if rect_opt is None else make_rectifier(**rect_opt))
@@ -742,6 +840,21 @@ def main(argv=None):
             save_pointcloud(os.path.join(opt.save_path, f"{index}"), cloud)
             print(f"{index}: point cloud of {cloud.xyz.shape[0]} points "
                   f"({100.0 * cloud.xyz.shape[0] / best.size:.2f} % of the pixels)")
+        if dsm_opt is not None:  # from the map --pointcloud takes, at its size
+            flagged = None if lr is None else lr[2] != 0
+            if speckle is not None:
+                flagged = removed if flagged is None else (flagged | removed)
+            best, flagged = (refined[0], None) if refined is not None else (disp, flagged)
+            if rect_opt is None:
+                surface = dsm_of_map(best, flagged, load_images(leftname, rightname)[0], **dsm_opt)
+            else:  # the rectification is the calibration, as for --pointcloud
+                pair, r = last_rectified(), _rectifier.rect
+                surface = dsm_of_map(best, flagged, pair.left, **dict(
+                    dsm_opt, calib=dict(dsm_opt["calib"], focal=r.focal, baseline=r.baseline, cx=r.cx, cy=r.cy),
+                    cx_right=r.cx_right, valid=pair.valid[0]))
+            save_dsm(os.path.join(opt.save_path, f"{index}"), *surface)
+            print(f"{index}: surface model of {surface[3]['size'][0]} x {surface[3]['size'][1]} cells of "
+                  f"{surface[3]['cell']:g}; {100.0 * float((surface[2] == 2).mean()):.2f} % of the cells are empty")
         if view_opt is not None:  # from the best map the other flags made, at its size
             flagged = None if lr is None else lr[2] != 0
             if speckle is not None:

@@ -387,6 +387,35 @@ def points_scene(result: SceneResult, Q, left_u8=None, use: str = "refined", ref
 
 
 @torch.no_grad()
+def dsm_scene(result: SceneResult, Q, left_u8=None, grid=None, cell: float = None, radius: float = 0.5,
+              use: str = "refined", fill_iterations: int = 0, min_neighbours: int = 3, disp_range=None,
+              pose=None, surface=None, **kw):
+    """The surface model of a ``SceneResult`` (``dsm.Surface``), once, at scene size, after the
+    blend, through ``points_scene`` (never per tile, for the reason given there: the overlaps
+    would give their points twice).  ``grid`` is (G, GH, GW); None: ``dsm.grid_from_view`` of the
+    scene between the disparities ``disp_range`` = (far, near), with ``cell`` and ``pose``.
+    ``radius``: the footprint of a point in cells.  ``surface``: a ``dsm.Surface`` of the grid's
+    size to add the scene to (a mosaic of several scenes; it is not cleared), None: a new one.
+    ``kw``: the other keywords of ``points_scene``.  Returns ``dsm.SurfaceMaps`` (``rgb`` with
+    ``left_u8``, else ``source``: rows of the scene's compact cloud)."""
+    from . import dsm
+    if grid is None:
+        if disp_range is None:
+            raise ValueError("dsm_scene: without a grid the two disparities disp_range = (far, near) that bound it "
+                             "are needed")
+        h, w = result.disp.shape
+        grid = dsm.grid_from_view(Q.cpu().numpy() if isinstance(Q, torch.Tensor) else Q, h, w, disp_range, cell, pose)
+    G, gh, gw = grid
+    cloud = points_scene(result, Q, left_u8, use=use, **kw)
+    if surface is None:
+        surface = dsm.Surface(gh, gw, result.disp.device)
+    elif (surface.gh, surface.gw, surface.batch) != (gh, gw, None):
+        raise ValueError(f"dsm_scene: the surface is {surface.gh} x {surface.gw} (batch {surface.batch}), the grid "
+                         f"{gh} x {gw} without a batch")
+    return surface.add_cloud(cloud, G, radius=radius).resolve(fill_iterations, min_neighbours)
+
+
+@torch.no_grad()
 def view_scene(result: SceneResult, left_u8, s: float = 1.0, use: str = "refined", refined: torch.Tensor = None,
                refine: dict = None, **kw):
     """``kernels.forward_warp`` of a ``SceneResult``, once, at scene size, after the blend: the
